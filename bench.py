@@ -3,6 +3,7 @@
 BASELINE.json's metric, on N MI355X GPUs of one node.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode vgl|vl] [--res lo|ref|hi] [--dtype bf16|fp16|f32|split16]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one iteration of the reference loop body
@@ -11,6 +12,12 @@ One "step" = one iteration of the reference loop body
 parameters), synthetic inputs.  Each rank serves its own independent request (weak scaling,
 no collective inside the step); rank 0's weights reach the other ranks by ONE RCCL broadcast at start-up.
 Inputs are resident in HBM when the timed region starts.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times ONE window of exactly --steps steps and prints the line.  --full adds everything else:
+the median of WINDOWS windows, the per-kernel profile and roofline, the CPU oracle baseline, the per-request set-up cost and
+`tolerance_mode`.  --dump-outputs DIR writes what the timed path returned after its last step (rank 0's latents; with --block,
+a fixed sample of the block's output) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output
+for output.
 """
 import argparse
 import json
@@ -39,7 +46,8 @@ PEAK_TFLOPS = 2500.0          # dense bf16/fp16 MFMA peak, MI355X_MICROARCH.md (
 PEAK_TFLOPS_F32 = 157.3       # f32-input MFMA (v_mfma_f32_32x32x2_f32): the fp32 vector rate, same guide
 PEAK_TFLOPS_SPLIT16 = PEAK_TFLOPS / 3    # split16: every product block is three fp16 MFMAs (a_lo b_hi + a_hi b_lo + a_hi b_hi)
 TOLERANCE_MODE_FILE = "r6_bench_lo_split16.json"   # the bench line of the mode that meets rtol 1e-3 / atol 1e-4 (python bench.py --dtype split16)
-WINDOWS = 3                   # timed windows of --steps steps each; ms_per_step is their median
+WINDOWS = 3                   # --full: timed windows of --steps steps each; ms_per_step is their median
+DUMP_BYTES = 64 << 20         # --dump-outputs: at most this many bytes over all arrays
 FRAMES, CTX_TOKENS, CTX_DIM, STEPS_PER_REQUEST = 14, 78, 1024, 25
 TRAFFIC_FILE = "r6_hbm_traffic.json"     # written by tools/profile_round.sh (rocprofv3 --pmc passes), stamped with the kernel-source hash
 
@@ -116,6 +124,22 @@ def advance(loop, args, n, fresh=False):
         if loop.step_index == loop.num_steps or (fresh and i == 0):
             loop.begin(**args)
         loop.step()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy, float64 kept, everything else as float32.  An array larger
+    than its share of DUMP_BYTES is replaced by a fixed sample of its elements (sorted indices from a seeded generator, the same
+    in every run), flattened."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
 
 
 def kernel_profile(loop, args):
@@ -252,6 +276,8 @@ def block_main(a, dtype, device, peak) -> int:
         graph.replay()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / a.steps * 1e3
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"block_out": out})
     ops.PROFILE = []
     run()
     torch.cuda.synchronize()
@@ -341,8 +367,13 @@ def main():
                     help="l0hi: time ONE L0 TransformerSpatioTemporalModel at 64x112 latents (BASELINE's spatio-temporal-attention block) instead of the step")
     ap.add_argument("--attn", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: spatial self-attention on OCP e4m3 operands with fp8 MFMA (BASELINE config 5; 16-bit elsewhere)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: median of three timed windows, per-kernel profile + roofline, CPU oracle baseline, "
+                         "per-request set-up cost, tolerance_mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="--full without the per-kernel profile and roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--stub-cpu", action="store_true",
                     help="launcher self-test (tests/test_bench_launch_cpu.py): gloo ranks time a sleep instead of the GPU loop")
     a = ap.parse_args()
@@ -406,13 +437,14 @@ def main():
             torch.cuda.synchronize()
 
     advance(loop, args, a.warmup)
-    # WINDOWS timed windows of exactly --steps steps, each bracketed by barrier + synchronize on both sides and reduced to the MAX over
-    # ranks; the line reports the MEDIAN window (boxes of the pool differ by 3-6 %, one 0.6 s window cannot resolve 0.1 ms levers) and
-    # lists all of them in config.ms_per_step_windows
+    # timed windows of exactly --steps steps, each bracketed by barrier + synchronize on both sides and reduced to the MAX over ranks.
+    # A plain run times one window; --full times WINDOWS of them and reports the MEDIAN (boxes of the pool differ by 3-6 %, one 0.6 s
+    # window cannot resolve 0.1 ms levers), listing all of them in config.ms_per_step_windows
     from this_and_that_vdm_amd.dist import max_over_ranks
     gdev = "cpu" if one_gpu else device
+    windows = WINDOWS if a.full else 1
     window_dt, window_own = [], []
-    for _ in range(WINDOWS):
+    for _ in range(windows):
         fence()
         t0 = time.perf_counter()
         advance(loop, args, a.steps, fresh=True)    # >= one begin() per 25 steps inside the timed region
@@ -420,13 +452,18 @@ def main():
         own = time.perf_counter() - t0
         window_own.append(own)
         window_dt.append(max_over_ranks(own, gdev))
-    order = sorted(range(WINDOWS), key=lambda i: window_dt[i])
-    mid = order[WINDOWS // 2]
+    order = sorted(range(windows), key=lambda i: window_dt[i])
+    mid = order[windows // 2]
     dt, dt_own = window_dt[mid], window_own[mid]
-    tb = time.perf_counter()                        # what one request set-up costs on its own (reported, already inside dt above)
-    loop.begin(**args)
-    torch.cuda.synchronize()
-    begin_ms = (time.perf_counter() - tb) * 1e3
+    latents = loop.result().clone()                 # what the caller of the last timed step receives (begin() below overwrites it)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"latents": latents})
+    begin_ms = None
+    if a.full:
+        tb = time.perf_counter()                    # what one request set-up costs on its own (reported, already inside dt above)
+        loop.begin(**args)
+        torch.cuda.synchronize()
+        begin_ms = (time.perf_counter() - tb) * 1e3
     allv = gather_floats([dt_own / a.steps * 1e3, float(checksum % (1 << 52)), getattr(build_models, "prepare_s", 0.0), bcast_s or 0.0], gdev)
     per_rank_ms, checksums = [v[0] for v in allv], [int(v[1]) for v in allv]
     per_rank_pack_s, per_rank_bcast_s = [v[2] for v in allv], [v[3] for v in allv]
@@ -436,10 +473,10 @@ def main():
         torch.distributed.all_reduce(ones)
         rccl_ranks = {"backend": torch.distributed.get_backend(), "ranks_in_all_reduce": int(ones.item()),
                       "world_size": torch.distributed.get_world_size()}
-    finite = bool(torch.isfinite(loop.result()).all().item())
+    finite = bool(torch.isfinite(latents).all().item())
 
     roofline, extras = None, {}
-    if rank == 0 and not a.no_kernel_profile:
+    if rank == 0 and a.full and not a.no_kernel_profile:
         agg = kernel_profile(loop, args)
         tot_flops = sum(v[1] for v in agg.values())
         name, (cnt, fl, sec) = max(agg.items(), key=lambda kv: kv[1][2])
@@ -467,7 +504,7 @@ def main():
                                       "tflops": v[1] / v[2] / 1e12} for k, v in sorted(agg.items(), key=lambda kv: -kv[1][2])}
         extras["executed_tflop_per_step"] = tot_flops / 1e12
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.mode, a.res)
 
     if rank == 0:
@@ -491,7 +528,8 @@ def main():
                        "step_mfma_frac_of_peak": step_tflop / (ms * 1e-3) / peak,
                        # ... and on the flops the step actually launches (the zero-context shortcut skips the uncond half's cross-attention)
                        "step_mfma_frac_executed": (extras["executed_tflop_per_step"] / (ms * 1e-3) / peak) if "executed_tflop_per_step" in extras else None,
-                       "ms_per_step_windows": [d / a.steps * 1e3 for d in window_dt], "ms_per_step_is": f"median of {WINDOWS} windows of {a.steps} steps",
+                       "ms_per_step_windows": [d / a.steps * 1e3 for d in window_dt],
+                       "ms_per_step_is": f"median of {windows} windows of {a.steps} steps" if windows > 1 else f"one window of {a.steps} steps",
                        "rccl_ranks": rccl_ranks,
                        "weight_broadcast_s": max(per_rank_bcast_s) if world > 1 else None, "rendezvous_s": rendezvous_s if world > 1 else None,
                        "weight_packing_s_per_rank": per_rank_pack_s if world > 1 else getattr(build_models, "prepare_s", None),
@@ -500,7 +538,7 @@ def main():
                        "weights_identical_on_all_ranks": len(set(checksums)) == 1, "kernel_source_sha16": csrc_hash(), **extras},
             "roofline": roofline, "cpu_baseline": cpu,
         }
-        if a.dtype in ("bf16", "fp16"):             # the 16-bit modes do not meet the north-star tolerance: show the mode that does, side by side
+        if a.full and a.dtype in ("bf16", "fp16"):  # the 16-bit modes do not meet the north-star tolerance: show the mode that does, side by side
             out["tolerance_mode"] = tolerance_mode(a.mode, a.res)
         print(json.dumps(out))
     if world > 1:

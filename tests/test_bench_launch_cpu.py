@@ -47,3 +47,20 @@ def test_rank_without_a_peer_fails_loud_with_a_json_error_line():
     assert len(lines) == 1
     err = json.loads(lines[0])["error"]
     assert "rank 1" in err and "init_process_group" in err
+
+
+def test_dump_outputs_keeps_small_arrays_and_samples_large_ones_the_same_way_every_run(tmp_path, monkeypatch):
+    """--dump-outputs: float32 (float64 kept), an array over its share of the byte budget becomes a fixed seeded sample."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 12)
+    small = torch.arange(12, dtype=torch.bfloat16).reshape(3, 4)
+    big = torch.randn(10000, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (3, 4) and np.array_equal(s, small.float().numpy())
+    b = np.load(tmp_path / "a" / "big.npy")
+    assert b.dtype == np.float64 and b.nbytes == (1 << 11) and np.isin(b, big.numpy()).all()
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))

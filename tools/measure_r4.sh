@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU-box pass that produces the round-4 measurement set under gpurun_out/profiles/ (copied into profiles/ afterwards).
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/profiles; P=gpurun_out/profiles
-b() { python bench.py "$@" 2>/dev/null | tail -1; }
+b() { python bench.py --full "$@" 2>/dev/null | tail -1; }
 b > $P/r4_bench_lo.json
 b --mode vl --no-cpu-baseline > $P/r4_bench_vl.json
 b --dtype fp16 --no-cpu-baseline > $P/r4_bench_lo_fp16.json

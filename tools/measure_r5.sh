@@ -2,7 +2,7 @@
 # One GPU-box pass that produces the round-5 measurement set under gpurun_out/profiles/ (copied into profiles/ afterwards).
 # profiles/r5_hbm_traffic.json must already belong to the current kernel sources (tools/profile_round.sh; bench.py checks the stamp).
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/profiles; P=gpurun_out/profiles
-b() { python bench.py "$@" 2>/dev/null | tail -1; }
+b() { python bench.py --full "$@" 2>/dev/null | tail -1; }
 b > $P/r5_bench_lo.json
 b --mode vl --no-cpu-baseline > $P/r5_bench_vl.json
 b --dtype fp16 --no-cpu-baseline > $P/r5_bench_lo_fp16.json

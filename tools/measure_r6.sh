@@ -4,7 +4,7 @@
 # quotes a measurement of the same call and the same kernel sources; profiles/r6_hbm_traffic.json must already belong to the current
 # kernel sources (tools/profile_round.sh; bench.py checks the stamp).
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/profiles; P=gpurun_out/profiles
-b() { python bench.py "$@" 2>/dev/null | tail -1; }
+b() { python bench.py --full "$@" 2>/dev/null | tail -1; }
 b --dtype split16 --no-cpu-baseline --steps 10 --warmup 3 > $P/r6_bench_lo_split16.json; cp $P/r6_bench_lo_split16.json profiles/r6_bench_lo_split16.json
 b --dtype f32 --no-cpu-baseline --steps 5 --warmup 2 > $P/r6_bench_lo_f32.json
 b > $P/r6_bench_lo.json

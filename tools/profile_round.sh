@@ -11,7 +11,7 @@ extra="$*"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out gpurun_out/profiles
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- \
-  python bench.py --steps 5 --warmup 2 --res $res --no-cpu-baseline --no-kernel-profile $extra > $out/stats.log 2>&1
+  python bench.py --full --steps 5 --warmup 2 --res $res --no-cpu-baseline --no-kernel-profile $extra > $out/stats.log 2>&1
 cp "$(find $out/stats -name '*kernel_stats.csv' | head -1)" gpurun_out/profiles/${tag}_kernel_stats.csv
 python tools/trace_agg.py "$(find $out/stats -name '*kernel_trace.csv' | head -1)" --steps 5 > gpurun_out/profiles/${tag}_kernel_by_grid.txt
 tail -1 $out/stats.log | cut -c1-160
