@@ -53,6 +53,14 @@ const char* tt_last_error(void);
  *                             (unet_spatio_temporal_condition.py:455,528; temporal_controlnet.py:580).
  *   mode 2  Conv3d (3,1,1)    TemporalResnetBlock.conv1/conv2 (diffusers; reached from
  *                             unet_3d_blocks.py:1891-2316): 3 taps along the frame axis.
+ *   mode 3  Conv2d 3x3,       the VAE encoder's Downsample2D(use_conv=True, padding=0) (diffusers; reached from
+ *           zero padding      vae.encode, svd/pipeline_stable_video_diffusion_controlnet.py:200,652):
+ *           left 0 / right 1  F.pad(x, (0,1,0,1)) + conv(stride, padding=0) in one launch.  Output (y, x), tap (ky, kx)
+ *           top 0 / bottom 1  reads input pixel (y*stride + ky, x*stride + kx); pixels with index >= hin / win read as zero.
+ *                             Same fields and weight layout as mode 1 (nimg, hin, win, hout, wout, stride); upsample
+ *                             must be 0 (TT_EINVAL).  Built only for the tile configurations the planner gives mode-3
+ *                             problems: a tile override (tt_gemm_set_tile_override / TT_GEMM_CFG) naming another
+ *                             configuration makes tt_gemm / tt_gemm_plan return TT_EUNSUPPORTED for mode 3.
  * W is [n, taps*(k0+k1)] row-major with k index (tap, source, channel); two sources implement
  * torch.cat([h, skip], dim=1) (unet_3d_blocks.py:2242,2352) without a concat buffer.
  * Epilogue, in this order (every term optional):
@@ -69,8 +77,8 @@ typedef struct TtGemmArgs {
   int64_t lda0, lda1;                  /* row strides, elements */
   const void* w; int64_t ldw;          /* [n, taps*(k0+k1)] */
   int32_t m, n;                        /* n multiple of 4 */
-  int32_t mode;                        /* 0 linear, 1 conv3x3, 2 tconv3 */
-  int32_t nimg, hin, win, hout, wout, stride, upsample;   /* mode 1 (hin/win = stored input size) */
+  int32_t mode;                        /* 0 linear, 1 conv3x3, 2 tconv3, 3 conv3x3 padded bottom / right only */
+  int32_t nimg, hin, win, hout, wout, stride, upsample;   /* modes 1 and 3 (hin/win = stored input size) */
   int32_t frames, hw;                  /* mode 2: row = (b*frames + f)*hw + p */
   const float* bias;
   float acc_scale;

@@ -60,6 +60,9 @@ constexpr TileCfg kCfgs[] = {        // keep in step with launch<Tag>() in gemm_
 };
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
+// taps per output row: 9 for both 3x3 gathers (mode 1: pad 1 all round, mode 3: pad on the bottom / right only), 3 for the temporal conv
+inline int gemm_taps(int mode) { return mode == 1 || mode == 3 ? 9 : (mode == 2 ? 3 : 1); }
+
 int g_forced_cfg = -2;
 int forced_cfg() {
   if (g_forced_cfg == -2) { const char* e = getenv("TT_GEMM_CFG"); g_forced_cfg = e ? atoi(e) : -1; }
@@ -239,7 +242,7 @@ static void w320_init() {
 // what both kernels of gemm_w320.hip need of a problem
 static bool w320_eligible(const TtGemmArgs* a) {
   w320_init();
-  if (!g_w320 || forced_cfg() >= 0 || a->dtype == TT_F32 || a->n % 320 || (a->k0 & 63) || (a->k1 & 63) || (a->mode == 1 ? 9 : a->mode == 2 ? 3 : 1) * (a->k0 + a->k1) < 128 || a->geglu ||
+  if (!g_w320 || forced_cfg() >= 0 || a->mode == 3 || a->dtype == TT_F32 || a->n % 320 || (a->k0 & 63) || (a->k1 & 63) || gemm_taps(a->mode) * (a->k0 + a->k1) < 128 || a->geglu ||
       a->out_fp8 || a->out_f32 || a->out_col_hw || a->ln_fold > 1 || (a->ln_fold && (a->mode != 0 || a->k1)))
     return false;
   if (a->mode == 1 && (a->stride != 1 || a->upsample || a->hin != a->hout || a->win != a->wout || a->win >= 32768 || a->hin >= 32768)) return false;
@@ -286,7 +289,7 @@ int w320_split(const TtGemmArgs* a) {
   if (!w320_eligible(a) || !(g_w320 & 8) || a->ln_fold || a->mode == 2 || w320_route(a)) return 0;
   const long tiles = (long)ceil_div(a->m, 128) * (a->n / 320);
   if ((g_w320 & 4) && (a->mode != 1 || tiles < 64)) return 0;
-  const long slabs = (long)(a->mode == 1 ? 9 : 1) * (a->k0 + a->k1) / 64;
+  const long slabs = (long)gemm_taps(a->mode) * (a->k0 + a->k1) / 64;
   long s = 256 / tiles;
   const long by_k = slabs / (a->mode == 1 ? 20 : 32);
   if (s > by_k) s = by_k;
@@ -323,6 +326,16 @@ static void pp_split(const TtGemmArgs* a, int rows, TtGemmArgs* head, TtGemmArgs
 
 // tile shapes whose fused-LayerNorm variants are built (launch<Tag>() in gemm_kernel.h): the ones the planner picks
 static bool ln_capable(int cfg) { return cfg == 1 || cfg == 2 || cfg == 3 || cfg == 7 || cfg == 9 || cfg == 11 || cfg == 16; }
+// 16-bit tile shapes whose mode-3 gather is built (M3OK in launch<Tag>(); TT_F32: both of its shapes): what mode3_plan maps every
+// plan of a mode-3 problem onto.  A forced tile shape outside this set is refused (TT_EUNSUPPORTED), never replaced.
+static bool mode3_capable(int cfg) { return cfg == 1 || cfg == 2 || cfg == 11 || cfg == 16; }
+static Plan mode3_plan(const TtGemmArgs* a, Plan pl) {
+  if (a->mode != 3 || a->dtype == TT_F32 || forced_cfg() >= 0 || mode3_capable(pl.cfg)) return pl;
+  if (pl.cfg == 20) return Plan{16, pl.splitk};          // (TT_GEMM_DEEP=2: the 4-deep ring's split plan instead of the 128-deep K steps)
+  const long b128 = (long)ceil_div(a->m, 128) * ceil_div(a->n, 128), b12864 = (long)ceil_div(a->m, 128) * ceil_div(a->n, 64);
+  return Plan{b128 >= 384 ? 11 : (b12864 >= 384 ? 1 : 2), 1};   // (the wide / N = 160 t shapes: make_plan's choice for the other sizes)
+}
+static bool mode3_served(const TtGemmArgs* a, const Plan& pl) { return a->mode != 3 || a->dtype == TT_F32 || mode3_capable(pl.cfg); }
 static Plan plan_for(const TtGemmArgs* a) {
   if (a->dtype == TT_F32) {
     // split16: the 64 x 64 tiles' 32 x 32 wave tiles convert two operand fragments per product block (VALU-bound, ~110 TFLOP/s against
@@ -346,7 +359,7 @@ static Plan plan_for(const TtGemmArgs* a) {
       static int sk = -1;
       if (sk < 0) { const char* e = getenv("TT_F32_SPLITK"); sk = e ? atoi(e) : 1; }
       const long b128 = (long)ceil_div(a->m, 128) * ceil_div(a->n, 128);
-      const long kt = (long)(a->mode == 1 ? 9 : (a->mode == 2 ? 3 : 1)) * (a->k0 + a->k1) / 32;
+      const long kt = (long)gemm_taps(a->mode) * (a->k0 + a->k1) / 32;
       if (sk && !a->geglu && !a->ln_fold && !a->out_col_hw && b128 < split_min && kt >= 64) {
         long sp = 448 / b128;
         if (sp > kt / 16) sp = kt / 16;
@@ -356,7 +369,7 @@ static Plan plan_for(const TtGemmArgs* a) {
     }
     return Plan{plan_f32(a->m, a->n, f32_split() ? split_min : 256), 1};
   }
-  const int taps = a->mode == 1 ? 9 : (a->mode == 2 ? 3 : 1);
+  const int taps = gemm_taps(a->mode);
   const bool allow = !a->geglu && !a->ln_fold && !a->out_fp8;       // a K slice would see only part of a LayerNorm row
   const bool k128 = (a->k0 & 127) == 0 && (a->k1 & 127) == 0;
   Plan pl = make_plan(a->m, a->n, (long)taps * (a->k0 + a->k1), allow, !(a->residual || a->blend || a->rowvec), a->mode == 0, k128);
@@ -366,13 +379,13 @@ static Plan plan_for(const TtGemmArgs* a) {
     pl = make_plan(a->m, a->n, (long)taps * (a->k0 + a->k1), false, !(a->residual || a->blend || a->rowvec), a->mode == 0);
     g_forced_cfg = keep;
   }
-  return pl;
+  return mode3_plan(a, pl);
 }
 
 // the plan of a problem whose split plan cannot be served (no / too small a workspace)
 static Plan unsplit_plan(const TtGemmArgs* a) {
   if (a->dtype == TT_F32) return Plan{plan_f32(a->m, a->n, 256), 1};
-  return Plan{make_plan(a->m, a->n, 0, false, !(a->residual || a->blend || a->rowvec)).cfg, 1};
+  return mode3_plan(a, Plan{make_plan(a->m, a->n, 0, false, !(a->residual || a->blend || a->rowvec)).cfg, 1});
 }
 
 extern "C" int tt_gemm_plan(const TtGemmArgs* a, int32_t cfg[7]) {
@@ -399,6 +412,8 @@ extern "C" int tt_gemm_plan(const TtGemmArgs* a, int32_t cfg[7]) {
   if (pl.splitk > 1 && (!a->ws || (size_t)a->ws_bytes < (size_t)pl.splitk * a->m * a->n * sizeof(float) ||
                         (long)pl.splitk * a->m * a->n * 4 >= (1L << 31)))
     pl = unsplit_plan(a);
+  if (!mode3_served(a, pl))
+    TT_FAIL(TT_EUNSUPPORTED, "tt_gemm_plan: forced tile configuration %d has no mode-3 variant (mode 3 is built for 1, 2, 11, 16)", pl.cfg);
   const TileCfg& t = a->dtype == TT_F32 ? kCfgsF32[pl.cfg] : kCfgs[pl.cfg];
   cfg[0] = t.bm; cfg[1] = t.bn; cfg[2] = t.bk; cfg[3] = t.nst; cfg[4] = t.wgm; cfg[5] = t.wgn; cfg[6] = pl.splitk;
   return TT_OK;
@@ -453,6 +468,7 @@ extern "C" size_t tt_gemm_ws_bytes(const TtGemmArgs* a) {
   if (const int rows = pp_split_rows(a)) { TtGemmArgs head, tail; pp_split(a, rows, &head, &tail); return tt_gemm_ws_bytes(&tail); }
   if (const int split = w320_split(a)) return (size_t)split * a->m * a->n * sizeof(float);
   const Plan pl = plan_for(a);
+  if (!mode3_served(a, pl)) return 0;                       // (tt_gemm refuses the problem)
   return pl.splitk > 1 ? (size_t)pl.splitk * a->m * a->n * sizeof(float) : 0;
 }
 
@@ -463,7 +479,8 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
   if ((a->k0 & 7) || (a->k1 & 7) || (a->n & 3)) TT_FAIL(TT_EINVAL, "tt_gemm: k0/k1 must be multiples of 8 and n of 4");
   if ((a->lda0 & 7) || (a->k1 && (a->lda1 & 7)) || (a->ldw & 7)) TT_FAIL(TT_EINVAL, "tt_gemm: row strides must be multiples of 8 elements");
   if (a->k1 && !a->a1) TT_FAIL(TT_EINVAL, "tt_gemm: k1 > 0 without a1");
-  if (a->mode < 0 || a->mode > 2) TT_FAIL(TT_EINVAL, "tt_gemm: bad mode %d", a->mode);
+  if (a->mode < 0 || a->mode > 3) TT_FAIL(TT_EINVAL, "tt_gemm: bad mode %d", a->mode);
+  if (a->mode == 3 && a->upsample) TT_FAIL(TT_EINVAL, "tt_gemm: mode 3 (bottom / right zero padding) has no fused upsample");
   if (const int rows = pp_split_rows(a)) {                  // whole tile rows -> persistent kernel, the ragged rest -> tiled kernel
     TtGemmArgs head, tail;
     pp_split(a, rows, &head, &tail);
@@ -510,7 +527,7 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
     if ((a->presplit & 1) && a->mode != 0) TT_FAIL(TT_EINVAL, "tt_gemm: a pre-split A operand is a Linear operand (mode 0)");
   }
   p.gn_out = (char*)a->gn_out; p.ld_gn = a->ld_gn; p.gn_gamma = a->gn_gamma; p.gn_beta = a->gn_beta; p.gn_eps = a->gn_eps; p.gn_silu = a->gn_silu;
-  if (p.mode == 1) {
+  if (p.mode == 1 || p.mode == 3) {
     if (p.nimg <= 0 || p.hin <= 0 || p.win <= 0 || p.hout <= 0 || p.wout <= 0 || p.stride < 1)
       TT_FAIL(TT_EINVAL, "tt_gemm: conv geometry");
     if ((long)p.nimg * p.hout * p.wout != p.m) TT_FAIL(TT_EINVAL, "tt_gemm: m != nimg*hout*wout");
@@ -518,9 +535,9 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
   if (p.mode == 2) {
     if (p.frames <= 0 || p.hw <= 0 || p.m % ((long)p.frames * p.hw)) TT_FAIL(TT_EINVAL, "tt_gemm: tconv geometry");
   }
-  p.taps = p.mode == 1 ? 9 : (p.mode == 2 ? 3 : 1);
+  p.taps = gemm_taps(p.mode);
   {
-    const long rows = p.mode == 1 ? (long)p.nimg * p.hin * p.win : (long)p.m;
+    const long rows = p.mode == 1 || p.mode == 3 ? (long)p.nimg * p.hin * p.win : (long)p.m;
     const long a0b = ((rows - 1) * p.lda0 + p.k0) * es, a1b = p.k1 ? ((rows - 1) * p.lda1 + p.k1) * es : 16;
     const long wb = ((long)(p.n - 1) * p.ldw + (long)p.taps * (p.k0 + p.k1)) * es;
     if (a0b >= (1L << 31) || a1b >= (1L << 31) || wb >= (1L << 31))
@@ -572,6 +589,8 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
     pl = unsplit_plan(a);            // no workspace: un-split plan (still correct)
   if (pl.splitk > 1 && (long)pl.splitk * a->m * a->n * 4 >= (1L << 31))
     pl = unsplit_plan(a);            // slabs beyond the 32-bit offsets: un-split plan
+  if (!mode3_served(a, pl))
+    TT_FAIL(TT_EUNSUPPORTED, "tt_gemm: forced tile configuration %d has no mode-3 variant (mode 3 is built for 1, 2, 11, 16)", pl.cfg);
   p.splitk = pl.splitk;
   p.group_m_override = group_m_override(); p.group_m = 1;
   p.ws = (float*)a->ws;

@@ -284,6 +284,9 @@ constexpr int gemm_min_waves(int BM, int BN, int CPR, int NST, int NT) {
 
 // KMODE: 0 Linear, 1 conv3x3, 2 temporal conv, and two Linear variants with a fused LayerNorm (transformer blocks):
 //   3  out = LN(A rows) W^T        4  out = A LN(W rows)^T   (the swapped V^T projection: the tokens are the "W" operand)
+//   5  conv3x3 with zero padding on the bottom / right only (tt_gemm mode 3: the VAE encoder's Downsample2D(padding=0) after
+//      F.pad(x, (0, 1, 0, 1))): the mode-1 gather with tap (ky, kx) reading pixel (y*stride + ky, x*stride + kx), built only for
+//      the tile shapes the planner gives mode-3 problems (M3OK in launch_cfg)
 // The caller folds gamma into the weights, centres them over k (rows sum to zero, so the mean of x drops out of x W^T) and
 // folds beta into the bias; what remains is the per-token 1/sigma.  Every lane sees ALL K values of "its" operand row pass
 // through its registers as MFMA fragments (row l31, chunk parity hi), so sum and sum of squares cost two packed dot
@@ -299,8 +302,9 @@ void gemm_kernel(const GemmP p) {
   constexpr int KMODE = KMODE_ & 7;
   static_assert(SPLIT || (!PRE_A && !PRE_B), "pre-split operands belong to the split variants");
   static_assert(!SPLIT || std::is_same<Tag, f32_tag>::value, "split products are a TT_F32 mode");
-  constexpr int MODE = KMODE >= 3 ? 0 : KMODE;         // gather mode
-  constexpr int LN = KMODE >= 3 ? KMODE - 2 : 0;       // 0 none, 1 statistics of A rows, 2 of W rows
+  constexpr bool PAD_BR = KMODE == 5;                  // mode-3 conv: taps start at the output pixel's own (strided) position
+  constexpr int MODE = PAD_BR ? 1 : (KMODE >= 3 ? 0 : KMODE);                   // gather mode
+  constexpr int LN = KMODE == 3 || KMODE == 4 ? KMODE - 2 : 0;                  // 0 none, 1 statistics of A rows, 2 of W rows
   TL(0);
   kernarg_touch<sizeof(GemmP)>();
   typedef typename Elem<Tag>::quad_t quad_t;
@@ -420,11 +424,13 @@ void gemm_kernel(const GemmP p) {
           bool ok = a_valid[i];
           long row;
           if constexpr (MODE == 1) {
-            const int dy = s_tap / 3 - 1, dx = s_tap - (dy + 1) * 3 - 1;
+            constexpr int OFF = PAD_BR ? 0 : 1;          // taps -1..1 (pad 1 all round) or 0..2 (pad on the bottom / right only)
+            const int dy = s_tap / 3 - OFF, dx = s_tap - (dy + OFF) * 3 - OFF;
             int iy = a_y[i] * p.stride + dy, ix = a_x[i] * p.stride + dx;
-            const int hv = p.upsample ? p.hin * 2 : p.hin, wv = p.upsample ? p.win * 2 : p.win;
+            const bool up = !PAD_BR && p.upsample;     // (tt_gemm refuses upsample with mode 3)
+            const int hv = up ? p.hin * 2 : p.hin, wv = up ? p.win * 2 : p.win;
             ok = ok && iy >= 0 && iy < hv && ix >= 0 && ix < wv;
-            if (p.upsample) { iy >>= 1; ix >>= 1; }
+            if (up) { iy >>= 1; ix >>= 1; }
             row = ((long)a_img[i] * p.hin + iy) * p.win + ix;
           } else {
             const int f = a_img[i] + s_tap - 1;
@@ -1509,7 +1515,7 @@ void launch_mode(const GemmP& p, hipStream_t st) {
 }
 
 // LNOK: also instantiate the fused-LayerNorm variants (only the tile shapes the planner picks; gemm.hip keeps LayerNorm
-// problems on them)
+// problems on them).  M3OK: likewise the mode-3 gather (KMODE 5; gemm.hip: mode3_capable)
 // multiply-shift pairs of every launch-uniform divisor the kernel meets (tile order, K split, conv / frame geometry, row groups)
 static inline void fill_fastdivs(GemmP& p) {
   p.fd_splitk = make_fastdiv(p.splitk);
@@ -1525,7 +1531,7 @@ static inline void fill_fastdivs(GemmP& p) {
   p.fd_rv_mod = make_fastdiv(p.rowvec_mod > 0 ? p.rowvec_mod : 1);
 }
 
-template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN, bool LNOK = false>
+template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN, bool LNOK = false, bool M3OK = false>
 void launch_cfg(GemmP& p, hipStream_t st) {
   p.tiles_m = ceil_div(p.m, BM);
   p.tiles_n = ceil_div(p.n, BN);
@@ -1546,6 +1552,18 @@ void launch_cfg(GemmP& p, hipStream_t st) {
   p.nk0 = ceil_div(p.k0, BK); p.nk1 = p.k1 ? ceil_div(p.k1, BK) : 0;
   p.kt_total = p.taps * (p.nk0 + p.nk1);
   fill_fastdivs(p);
+  if (p.mode == 3) {                         // routed explicitly: the switches below send unknown modes elsewhere
+    if constexpr (M3OK) {
+      if constexpr (std::is_same<Tag, f32_tag>::value) {
+        if (p.f32_split) {                   // split-fp16 products (convs: only the weight is ever pre-split)
+          if (p.presplit & 2) launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 13 + 16>(p, st); else launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 13>(p, st);
+          return;
+        }
+      }
+      launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 5>(p, st);
+    }
+    return;                                  // (tt_gemm refuses mode 3 on tile shapes without the variant before it gets here)
+  }
   if constexpr (std::is_same<Tag, f32_tag>::value) {
     if (p.f32_split) {                       // tt_gemm_set_f32_split(1): the split-fp16 product variants (KMODE + 8)
       // KMODE + 8 (split products) + 16 (W pre-split: packed weights) / + 32 (A pre-split: the swapped V^T projection's weights)
@@ -1596,8 +1614,8 @@ template <typename Tag>
 void launch(GemmP& p, int cfg, hipStream_t st) {          // cfg = index into kCfgs (gemm.hip)
   switch (cfg) {
     case 0: launch_cfg<Tag, 128, 128, 64, 2, 2, 2>(p, st); break;
-    case 1: launch_cfg<Tag, 128, 64, 64, 3, 2, 2, true>(p, st); break;
-    case 2: launch_cfg<Tag, 64, 64, 64, 4, 2, 2, true>(p, st); break;
+    case 1: launch_cfg<Tag, 128, 64, 64, 3, 2, 2, true, true>(p, st); break;
+    case 2: launch_cfg<Tag, 64, 64, 64, 4, 2, 2, true, true>(p, st); break;
     case 3: launch_cfg<Tag, 256, 128, 32, 3, 4, 2, true>(p, st); break;
     case 4: launch_cfg<Tag, 256, 256, 32, 3, 2, 4>(p, st); break;
     case 5: launch_cfg<Tag, 128, 128, 32, 3, 2, 2>(p, st); break;
@@ -1606,12 +1624,12 @@ void launch(GemmP& p, int cfg, hipStream_t st) {          // cfg = index into kC
     case 8: launch_cfg<Tag, 128, 320, 32, 3, 4, 2>(p, st); break;
     case 9: launch_cfg<Tag, 256, 256, 64, 2, 2, 4, true>(p, st); break;
     case 10: launch_cfg<Tag, 128, 128, 64, 4, 2, 2>(p, st); break;
-    case 11: launch_cfg<Tag, 128, 128, 64, 2, 4, 2, true>(p, st); break;
+    case 11: launch_cfg<Tag, 128, 128, 64, 2, 4, 2, true, true>(p, st); break;
     case 12: launch_cfg<Tag, 256, 160, 32, 3, 8, 1>(p, st); break;
     case 13: launch_cfg<Tag, 256, 128, 32, 4, 4, 2>(p, st); break;
     case 14: launch_cfg<Tag, 128, 128, 32, 5, 4, 2>(p, st); break;
     case 15: launch_cfg<Tag, 128, 128, 64, 3, 4, 2>(p, st); break;
-    case 16: launch_cfg<Tag, 128, 128, 64, 4, 4, 2, true>(p, st); break;
+    case 16: launch_cfg<Tag, 128, 128, 64, 4, 4, 2, true, true>(p, st); break;
     case 17: launch_cfg<Tag, 256, 256, 32, 4, 2, 4>(p, st); break;
     case 18: launch_cfg<Tag, 256, 128, 64, 2, 4, 2>(p, st); break;
     case 19: launch_cfg<Tag, 256, 128, 32, 5, 4, 2>(p, st); break;

@@ -141,7 +141,8 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
     gn = (gamma, beta, eps, silu) next to stats = S: the parameters of THAT GroupNorm.  Where the launch ends in a split-K reduction pass
     (the two coarsest UNet levels) the pass also normalises (TtGemmArgs.gn_out): the result is attached (``out._tt_gn``) and groupnorm()
     with the same parameters returns it without a launch; elsewhere `gn` is ignored and the statistics route above applies.
-    conv = (nimg, hin, win, hout, wout, stride, upsample); tconv = (frames, hw).
+    conv = (nimg, hin, win, hout, wout, stride, upsample) for mode 1 (3x3, zero padding 1 all round) and mode 3 (3x3, zero padding on the
+    bottom / right only: F.pad(x, (0, 1, 0, 1)) + conv(padding=0), the VAE encoder's downsample; upsample 0); tconv = (frames, hw).
     ln_fold: 1 = rows of a0 / 2 = rows of w are LayerNorm inputs (weights pre-folded by packing.fold_layernorm).
     out_fp8: the output is stored as OCP e4m3 (torch.float8_e4m3fn), the operand format of attention(..., fp8 path)."""
     lib = _lib.load()
@@ -155,7 +156,7 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
     n = w.shape[0]
     g.w, g.ldw, g.n = _p(w), ldw, n
     g.mode = mode
-    if mode == 1:
+    if mode in (1, 3):
         g.nimg, g.hin, g.win, g.hout, g.wout, g.stride, g.upsample = conv
         mm = conv[0] * conv[3] * conv[4]
     elif mode == 2:
@@ -218,7 +219,7 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
     if ev is not None:
         cfg = (C.c_int32 * 7)()
         lib.tt_gemm_plan(C.byref(g), cfg)
-        taps = 9 if mode == 1 else (3 if mode == 2 else 1)
+        taps = 9 if mode in (1, 3) else (3 if mode == 2 else 1)
         tag = _TAG[g.dtype]
         if cfg[3] == 0 and cfg[1] == 320:            # the 256 x 320 big-tile kernel (gemm_w320.hip)
             kname = f"gemm_w320{'h' if cfg[0] == 128 else ''}_kernel<{tag}, {mode}, {int(bool(ln_fold))}>"
@@ -227,7 +228,9 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
         elif cfg[0] == 32 and cfg[1] == 320:        # the opt-in streaming kernel for the 320 x 320 linears
             kname = f"sq320_kernel<{tag}, {'true' if residual is not None else 'false'}>"
         else:
-            kmode = (mode if not ln_fold else 2 + ln_fold) + (8 if (g.dtype == TT_F32 and _F32_SPLIT) else 0)     # + 8: split-fp16 products
+            kmode = (5 if mode == 3 else mode if not ln_fold else 2 + ln_fold) + (8 if (g.dtype == TT_F32 and _F32_SPLIT) else 0)     # + 8: split-fp16 products
+            if mode == 3:                            # (the mode-3 gather, gemm_kernel.h KMODE 5: + 16 when the weight arrives pre-split)
+                kmode += 16 if g.presplit & 2 else 0
             kname = f"gemm_kernel<{tag}, {', '.join(str(v) for v in cfg[:6])}, {kmode}>"
         _prof_end(ev, kname, 2.0 * g.m * n * taps * (g.k0 + g.k1),
                   shape=(mode, g.m, n, taps * (g.k0 + g.k1), int(geglu), int(residual is not None)))

@@ -14,9 +14,11 @@ SpatioTemporalResBlock here = the UNet's (layers.py) without a time embedding, A
 switch_spatial_to_temporal_mix=True).  The mid-block attention has ONE head of 512 channels, outside tt_attention's 64 / 128:
 per frame  scores = tt_gemm(Q, K, fp32 out, scale d^-1/2) -> tt_softmax_rows -> tt_gemm(P, V^T)  (V's bias rides on to_out's
 bias: softmax rows sum to 1).  The encoder side (one image + the gesture frames per request, reference :168-188,:652) is not on
-the hot path and stays with the caller's stock module: ``AutoencoderKLTemporalDecoder(encoder=stock_vae)`` /
+the hot path.  By default it stays with the caller's stock module: ``AutoencoderKLTemporalDecoder(encoder=stock_vae)`` /
 ``from_pretrained(folder, encoder=stock_vae)`` / ``.with_encoder(stock_vae)`` make ``encode()`` delegate to it, so ONE object
-serves the pipeline's ``vae=`` argument for both directions (test_code/inference.py:169-176 passes one ``vae``).
+serves the pipeline's ``vae=`` argument for both directions (test_code/inference.py:169-176 passes one ``vae``).  With
+``native_encoder=True`` the model owns diffusers' ``encoder`` / ``quant_conv`` sub-modules instead and ``encode()`` runs them on the
+same kernels (vae_encoder.py).
 """
 from __future__ import annotations
 
@@ -30,7 +32,8 @@ import torch.nn as nn
 from .. import ops
 from ..packing import pack_conv3x3, pack_tconv3
 from .layers import Geom, PackRegistry, SpatioTemporalResBlock, Upsample2D, _f32, _Packable
-from .modeling_utils import ConfigMixin, ModelMixin, register_to_config
+from .modeling_utils import CONFIG_NAME, ConfigMixin, ModelMixin, register_to_config
+from .vae_encoder import DiagonalGaussianDistribution, Encoder
 
 
 def _res(cin: int, cout: int) -> SpatioTemporalResBlock:
@@ -202,16 +205,27 @@ class AutoencoderKLTemporalDecoder(ModelMixin, ConfigMixin):
     ``.latent_dist`` -- diffusers' own AutoencoderKLTemporalDecoder); without one it raises.  The stock module is NOT a
     sub-module (no parameters of it appear in ``state_dict()`` / ``parameters()``), but ``.to()`` / ``.half()`` / ``.float()``
     reach it too, so the pipeline's force_upcast round trip (reference :556-571: vae.to(fp32) -> encode -> vae.to(fp16)) encodes
-    in fp32 exactly as with the stock class."""
+    in fp32 exactly as with the stock class.
+
+    ``native_encoder=True`` (a config entry: ``save_pretrained`` keeps it; ``from_pretrained(folder, native_encoder=True)`` turns it on
+    for a stock diffusers ``vae/`` folder) adds diffusers' ``encoder`` (Encoder, double_z) and ``quant_conv`` (1x1, 2L -> 2L): the state
+    dict then has diffusers' full key layout (``encoder.*``, ``quant_conv.*``, ``decoder.*``), loads strictly over all of it, and
+    ``encode(x)`` runs on the MI355X (vae_encoder.py) -- no stock module (``encoder=`` is refused)."""
 
     _config_exclude = ("encoder",)          # a module, not a config entry (save_pretrained writes config.json from self.config)
 
     @register_to_config
     def __init__(self, in_channels: int = 3, out_channels: int = 3, block_out_channels: Tuple[int, ...] = (128, 256, 512, 512),
                  layers_per_block: int = 2, latent_channels: int = 4, sample_size: int = 768, scaling_factor: float = 0.18215,
-                 force_upcast: bool = True, encoder=None):
+                 force_upcast: bool = True, encoder=None, native_encoder: bool = False):
         super().__init__()
+        if native_encoder and encoder is not None:
+            raise ValueError("native_encoder=True runs encode() on the model's own encoder: do not pass a stock encoder= as well")
         self.decoder = TemporalDecoder(latent_channels, out_channels, tuple(block_out_channels), layers_per_block)
+        self.native_encoder = bool(native_encoder)
+        if self.native_encoder:
+            self.encoder = Encoder(in_channels, latent_channels, tuple(block_out_channels), layers_per_block)
+            self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
         self.compute_dtype: Optional[torch.dtype] = None      # None: the parameter dtype if 16-bit, else bf16; float32 = TT_F32 mode
         self._packed_key = None
         self.__dict__["_stock_encoder"] = None
@@ -219,6 +233,8 @@ class AutoencoderKLTemporalDecoder(ModelMixin, ConfigMixin):
 
     def with_encoder(self, encoder):
         """``encoder``: the caller's stock VAE (or any object with ``encode(x) -> .latent_dist``); None removes it."""
+        if encoder is not None and self.native_encoder:
+            raise ValueError("this model runs its own encoder (native_encoder=True): a stock encoder cannot be attached")
         if encoder is not None and not callable(getattr(encoder, "encode", None)):
             raise TypeError("encoder must provide encode(x) returning an object with .latent_dist (diffusers' AutoencoderKLTemporalDecoder)")
         self.__dict__["_stock_encoder"] = encoder              # outside nn.Module's registry on purpose (see the class docstring)
@@ -226,7 +242,20 @@ class AutoencoderKLTemporalDecoder(ModelMixin, ConfigMixin):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *args, encoder=None, **kwargs):
-        """diffusers-format folder (vae/ of an SVD checkpoint: encoder.* / quant_conv.* entries are ignored) + the stock encoder."""
+        """diffusers-format folder (vae/ of an SVD checkpoint) + the stock encoder: encoder.* / quant_conv.* entries are ignored --
+        or, with ``native_encoder=True`` (keyword or config entry), loaded into the model's own encoder."""
+        import json
+        import os
+        path = pretrained_model_name_or_path
+        sub = kwargs.get("subfolder", args[0] if args else None)
+        cfg_file = os.path.join(os.path.join(path, sub) if sub else path, CONFIG_NAME)
+        if os.path.isfile(cfg_file):
+            with open(cfg_file) as f:
+                cfg = json.load(f)
+            native = kwargs.get("native_encoder", cfg.get("native_encoder", False))
+            kinds = cfg.get("down_block_types")
+            if native and kinds is not None and any(k != "DownEncoderBlock2D" for k in kinds):
+                raise ValueError(f"native_encoder: {cfg_file} names down_block_types {kinds}; only DownEncoderBlock2D is implemented")
         model = super().from_pretrained(pretrained_model_name_or_path, *args, **kwargs)
         return model.with_encoder(encoder)
 
@@ -243,11 +272,17 @@ class AutoencoderKLTemporalDecoder(ModelMixin, ConfigMixin):
             if p0.device.type != "cuda":
                 raise RuntimeError("AutoencoderKLTemporalDecoder: the decoder runs on the MI355X only (no CPU fallback)")
             self.decoder.pack(PackRegistry(), key[1])
+            if self.native_encoder:
+                self.encoder.pack(PackRegistry(), key[1], self.quant_conv)
             self._packed_key = key
         return self
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        """Accepts a full diffusers AutoencoderKLTemporalDecoder state dict: encoder.* / quant_conv.* entries are ignored."""
+        """Accepts a full diffusers AutoencoderKLTemporalDecoder state dict: encoder.* / quant_conv.* entries are ignored -- unless
+        native_encoder=True, where every entry is loaded (strict over encoder.*, quant_conv.* and decoder.*)."""
+        if self.native_encoder:
+            self._packed_key = None
+            return super().load_state_dict(state_dict, strict=strict, **kw)
         sd = {k: v for k, v in state_dict.items() if k.startswith("decoder.")}
         self._packed_key = None
         return super().load_state_dict(sd, strict=strict, **kw)
@@ -260,13 +295,50 @@ class AutoencoderKLTemporalDecoder(ModelMixin, ConfigMixin):
         return super()._apply(fn, *a, **k)
 
     def encode(self, x, *a, **k):
-        """Delegated to the stock module given as ``encoder=`` (one image + the gesture frames per request, off the hot path)."""
+        """Delegated to the stock module given as ``encoder=`` (one image + the gesture frames per request, off the hot path);
+        with native_encoder=True see _encode_native."""
+        if self.native_encoder:
+            return self._encode_native(x, *a, **k)
         stock = self.__dict__.get("_stock_encoder")
         if stock is None:
             raise NotImplementedError("AutoencoderKLTemporalDecoder.encode: no stock encoder attached -- build the model with "
                                       "encoder=<the diffusers VAE> (or call .with_encoder(vae)); the native kernels cover the decoder side "
                                       "(decode_latents, reference :257-283), the encoder runs once per request in the caller's module")
         return stock.encode(x, *a, **k)
+
+    def encode_chunk_size(self, h: int, w: int) -> int:
+        """images per encoder pass at h x w: every token tensor of a pass stays under tt_gemm's 2 GiB operand limit"""
+        es = 4 if self._run_dtype() == torch.float32 else 2
+        per_image = self.encoder.max_tokens_bytes(h, w, es)
+        if per_image >= (1 << 31) - 1:
+            raise NotImplementedError(f"VAE encoder at {h}x{w}: one image's activations exceed the 2 GiB operand limit of tt_gemm")
+        return ((1 << 31) - 1) // per_image
+
+    @torch.no_grad()
+    def _encode_native(self, x: torch.Tensor, return_dict: bool = True, chunk_size: Optional[int] = None):
+        """x [N, C, H, W] (any float dtype; H, W multiples of 8) -> ``.latent_dist`` (DiagonalGaussianDistribution over the moments, in
+        the parameter dtype).  The batch runs in passes of ``chunk_size`` images (default: as many as the 2 GiB operand limit allows);
+        images are independent, so a result does not depend on the chunking beyond the storage rounding of split-K plans."""
+        if x.dim() != 4 or x.shape[1] != self.config.in_channels:
+            raise ValueError(f"encode: expected [N, {self.config.in_channels}, H, W], got {tuple(x.shape)}")
+        n, _, h, w = x.shape
+        down = 2 ** (len(self.encoder.down_blocks) - 1)
+        if h % 8 or w % 8 or h % down or w % down:
+            raise ValueError(f"encode: height and width must be multiples of 8 and of {down}, got {h}x{w}")
+        if (h // down) * (w // down) % 4:
+            raise NotImplementedError(f"encode: the mid-block attention needs (h*w) / {down * down} to be a multiple of 4, got {h}x{w}")
+        dev, dtype = next(self.parameters()).device, next(self.parameters()).dtype
+        if dev.type != "cuda":
+            raise RuntimeError("AutoencoderKLTemporalDecoder: the encoder runs on the MI355X only (no CPU fallback)")
+        self.prepare()
+        chunk = self.encode_chunk_size(h, w) if chunk_size is None else int(chunk_size)
+        if chunk < 1:
+            raise ValueError(f"encode: chunk_size must be >= 1, got {chunk_size}")
+        run = self._run_dtype()
+        parts = [self.encoder(x[i:i + chunk].to(dev), run) for i in range(0, n, chunk)]
+        moments = (parts[0] if len(parts) == 1 else torch.cat(parts)).to(dtype)
+        dist = DiagonalGaussianDistribution(moments)
+        return SimpleNamespace(latent_dist=dist) if return_dict else (dist,)
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, num_frames: int = 1, return_dict: bool = True):
