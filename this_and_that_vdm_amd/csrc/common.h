@@ -202,12 +202,16 @@ __device__ __forceinline__ f32pk_t gelu_sig_pk(f32pk_t x) {
 }
 
 // GELU without transcendentals (round 6; bf16 storage in the persistent GEGLU kernel only): Phi(x) ~ 0.5 + xc P(xc^2), xc = clamp(x, +-3.75),
-// P of degree 6 in x^2 (least-squares / Lawson fit on Chebyshev nodes: max |dPhi| = 5.6e-5, max |x dPhi| = 3.9e-4 over |x| <= 12 in fp32
-// arithmetic -- an order below bf16's 2^-9 output rounding wherever the output exceeds 0.1, absolute 4e-4 at most elsewhere; beyond the clamp
-// Phi stays at 0.99997 / 3.2e-5, a relative 3e-5 on gelu(x) ~ x).  v_exp_f32 and v_rcp_f32 issue at a quarter of the VALU rate: the sigmoid
-// form above costs 4 packed-equivalent VALU + 2 transcendentals per value = 48 clocks, this one 9 packed instructions + 2 clamps per PAIR = 22.
+// P of degree 6 in x^2 (least-squares / Lawson fit on Chebyshev nodes: max |dPhi| = 5.6e-5 over |x| <= 3.75 in fp32 arithmetic).  Beyond the
+// clamp Phi stays at 0.99997 / 3.2e-5, so the factor in front is xm = max(x, -3.75), not x: x * 3.2e-5 would leak 3.2e-5 |x| below -3.75,
+// where gelu is 0 (-3.2e-3 at x = -100); xm caps that at 3.75 * 3.2e-5 = 1.2e-4.  Error: <= 3.9e-4 absolute over |x| <= 12 (the worst at
+// x = 12: 12 * 3.2e-5), <= 4e-4 absolute + 3.2e-5 relative on the whole line (an order below bf16's 2^-9 output rounding wherever the output
+// exceeds 0.1) -- tests/test_error_bounds_cpu.py and the GELU sweep of tests/test_error_bounds_gpu.py.  v_exp_f32 and v_rcp_f32 issue at a
+// quarter of the VALU rate: the sigmoid form above costs 4 packed-equivalent VALU + 2 transcendentals per value = 48 clocks, this one
+// 9 packed instructions + 2 clamps + 2 max per PAIR = 24.
 __device__ __forceinline__ f32pk_t gelu_poly_pk(f32pk_t x) {
   const f32pk_t xc = {__builtin_amdgcn_fmed3f(x.x, -3.75f, 3.75f), __builtin_amdgcn_fmed3f(x.y, -3.75f, 3.75f)};
+  const f32pk_t xm = {fmaxf(x.x, -3.75f), fmaxf(x.y, -3.75f)};
   const f32pk_t t = xc * xc;
   f32pk_t q = t * 3.9124383732769275e-08f + -2.3762543150951387e-06f;
   q = q * t + 6.234781903913245e-05f;
@@ -215,7 +219,7 @@ __device__ __forceinline__ f32pk_t gelu_poly_pk(f32pk_t x) {
   q = q * t + 0.009362553246319294f;
   q = q * t + -0.06578987091779709f;
   q = q * t + 0.39870646595954895f;
-  return x * (xc * q + 0.5f);
+  return xm * (xc * q + 0.5f);
 }
 
 // ---------------------------------------------------------------- LDS tile staging (global -> LDS DMA)
