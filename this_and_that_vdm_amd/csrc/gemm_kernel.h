@@ -1515,7 +1515,7 @@ void launch_mode(const GemmP& p, hipStream_t st) {
 }
 
 // LNOK: also instantiate the fused-LayerNorm variants (only the tile shapes the planner picks; gemm.hip keeps LayerNorm
-// problems on them).  M3OK: likewise the mode-3 gather (KMODE 5; gemm.hip: mode3_capable)
+// problems on them).  M3OK: likewise the mode-3 gather (KMODE 5).  Both are columns of the tile table below.
 // multiply-shift pairs of every launch-uniform divisor the kernel meets (tile order, K split, conv / frame geometry, row groups)
 static inline void fill_fastdivs(GemmP& p) {
   p.fd_splitk = make_fastdiv(p.splitk);
@@ -1610,31 +1610,55 @@ void launch_sq320(const GemmP& p, hipStream_t st) {
   hipLaunchKernelGGL((sq320_kernel<Tag, HAS_RES, HAS_RV>), dim3(ntiles < 256 ? ntiles : 256), dim3(SQ_NT), lds, st, p);
 }
 
-template <typename Tag>
-void launch(GemmP& p, int cfg, hipStream_t st) {          // cfg = index into kCfgs (gemm.hip)
-  switch (cfg) {
-    case 0: launch_cfg<Tag, 128, 128, 64, 2, 2, 2>(p, st); break;
-    case 1: launch_cfg<Tag, 128, 64, 64, 3, 2, 2, true, true>(p, st); break;
-    case 2: launch_cfg<Tag, 64, 64, 64, 4, 2, 2, true, true>(p, st); break;
-    case 3: launch_cfg<Tag, 256, 128, 32, 3, 4, 2, true>(p, st); break;
-    case 4: launch_cfg<Tag, 256, 256, 32, 3, 2, 4>(p, st); break;
-    case 5: launch_cfg<Tag, 128, 128, 32, 3, 2, 2>(p, st); break;
-    case 6: launch_cfg<Tag, 256, 128, 64, 3, 4, 2>(p, st); break;
-    case 7: launch_cfg<Tag, 128, 160, 64, 2, 4, 1, true>(p, st); break;
-    case 8: launch_cfg<Tag, 128, 320, 32, 3, 4, 2>(p, st); break;
-    case 9: launch_cfg<Tag, 256, 256, 64, 2, 2, 4, true>(p, st); break;
-    case 10: launch_cfg<Tag, 128, 128, 64, 4, 2, 2>(p, st); break;
-    case 11: launch_cfg<Tag, 128, 128, 64, 2, 4, 2, true, true>(p, st); break;
-    case 12: launch_cfg<Tag, 256, 160, 32, 3, 8, 1>(p, st); break;
-    case 13: launch_cfg<Tag, 256, 128, 32, 4, 4, 2>(p, st); break;
-    case 14: launch_cfg<Tag, 128, 128, 32, 5, 4, 2>(p, st); break;
-    case 15: launch_cfg<Tag, 128, 128, 64, 3, 4, 2>(p, st); break;
-    case 16: launch_cfg<Tag, 128, 128, 64, 4, 4, 2, true, true>(p, st); break;
-    case 17: launch_cfg<Tag, 256, 256, 32, 4, 2, 4>(p, st); break;
-    case 18: launch_cfg<Tag, 256, 128, 64, 2, 4, 2>(p, st); break;
-    case 19: launch_cfg<Tag, 256, 128, 32, 5, 4, 2>(p, st); break;
-    default: launch_cfg<Tag, 128, 128, 128, 2, 4, 2>(p, st); break;
-  }
+// ---- the tile table: every tile shape of gemm_kernel is written down here, once.  X(index, BM, BN, BK, NST, WGM, WGN, LNOK, M3OK);
+// launch<Tag>() below, the planner's kCfgs[] / kCfgsF32[] and its "is the fused-LayerNorm / mode-3 variant built" answers
+// (gemm.hip: ln_capable, mode3_capable) are all generated from these two lists, so they cannot drift apart.
+#define TT_GEMM_TILES(X) \
+  X( 0, 128, 128,  64, 2, 2, 2, false, false)   /* 4 waves, 64 KiB, 2 blocks/CU */ \
+  X( 1, 128,  64,  64, 3, 2, 2, true,  true )   /* 72 KiB */ \
+  X( 2,  64,  64,  64, 4, 2, 2, true,  true )   /* small problems, deep ring (64 KiB) */ \
+  X( 3, 256, 128,  32, 3, 4, 2, true,  false)   /* 8 waves, 72 KiB -> 2 blocks/CU */ \
+  X( 4, 256, 256,  32, 3, 2, 4, false, false)   /* 8 waves, 96 KiB */ \
+  X( 5, 128, 128,  32, 3, 2, 2, false, false)   /* 48 KiB -> 3 blocks/CU */ \
+  X( 6, 256, 128,  64, 3, 4, 2, false, false)   /* 8 waves, 144 KiB */ \
+  X( 7, 128, 160,  64, 2, 4, 1, true,  false)   /* N = 320 without tile waste, wave tile 32x160, 72 KiB */ \
+  X( 8, 128, 320,  32, 3, 4, 2, false, false)   /* 8 waves, wave tile 32x160, 84 KiB */ \
+  X( 9, 256, 256,  64, 2, 2, 4, true,  false)   /* 8 waves, wave tile 128x64, 128 KiB, plain double buffer */ \
+  X(10, 128, 128,  64, 4, 2, 2, false, false)   /* 128 KiB, 1 block/CU, prefetch distance 3 */ \
+  X(11, 128, 128,  64, 2, 4, 2, true,  true )   /* 8 waves (wave tile 32x64), 64 KiB -> 16 waves/CU */ \
+  X(12, 256, 160,  32, 3, 8, 1, false, false)   /* N = 320/960, 8 waves (wave tile 32x160), 78 KiB -> 2 blocks/CU */ \
+  X(13, 256, 128,  32, 4, 4, 2, false, false)   /* like 3 with one more stage (96 KiB, 1 block/CU) */ \
+  X(14, 128, 128,  32, 5, 4, 2, false, false)   /* 8 waves, 80 KiB, prefetch distance 4 (x32) -> 2 blocks/CU */ \
+  X(15, 128, 128,  64, 3, 4, 2, false, false)   /* 8 waves, 96 KiB, prefetch distance 2 -> 1 block/CU */ \
+  X(16, 128, 128,  64, 4, 4, 2, true,  true )   /* 8 waves, 128 KiB, prefetch distance 3 -> 1 block/CU */ \
+  X(17, 256, 256,  32, 4, 2, 4, false, false)   /* 8 waves, wave tile 128x64, 128 KiB: three 32 KiB tiles in flight */ \
+  X(18, 256, 128,  64, 2, 4, 2, false, false)   /* 8 waves, wave tile 64x64, 96 KiB, plain double buffer */ \
+  X(19, 256, 128,  32, 5, 4, 2, false, false)   /* 8 waves, wave tile 64x64, 120 KiB: four 24 KiB tiles in flight */ \
+  X(20, 128, 128, 128, 2, 4, 2, false, false)   /* 8 waves, 128-deep K steps (256-byte rows), 128 KiB double buffer: half the barriers per MFMA (opt-in, see make_plan) */
+// TT_F32 (reference-precision mode): two tile shapes of the same kernel template.  BK counts elements, so 32 fp32
+// elements give the 128-byte tile rows of the 16-bit BK = 64 configurations.
+#define TT_GEMM_TILES_F32(X) \
+  X( 0, 128, 128,  32, 2, 2, 2, true,  true ) \
+  X( 1,  64,  64,  32, 4, 2, 2, true,  true )
+
+struct TileCfg { int idx, bm, bn, bk, nst, wgm, wgn; bool ln, m3; };
+#define TT_TILE_ROW(i, bm, bn, bk, nst, wgm, wgn, ln, m3) {i, bm, bn, bk, nst, wgm, wgn, ln, m3},
+constexpr TileCfg kCfgs[] = {TT_GEMM_TILES(TT_TILE_ROW)};
+constexpr TileCfg kCfgsF32[] = {TT_GEMM_TILES_F32(TT_TILE_ROW)};
+#undef TT_TILE_ROW
+constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+template <int N> constexpr bool tiles_in_order(const TileCfg (&t)[N]) {
+  for (int i = 0; i < N; ++i) if (t[i].idx != i) return false;
+  return true;
 }
+static_assert(tiles_in_order(kCfgs) && tiles_in_order(kCfgsF32), "a tile's index is its position in the table (the planner and launch() both go by it)");
+
+// cfg = index into the table of Tag's storage type; an index outside it launches nothing (the planner hands out none)
+#define TT_TILE_CASE(i, bm, bn, bk, nst, wgm, wgn, ln, m3) case i: launch_cfg<Tag, bm, bn, bk, nst, wgm, wgn, ln, m3>(p, st); break;
+template <typename Tag>
+void launch(GemmP& p, int cfg, hipStream_t st) {
+  switch (cfg) { TT_GEMM_TILES(TT_TILE_CASE) }
+}
+template <> void launch<f32_tag>(GemmP& p, int cfg, hipStream_t st);      // TT_GEMM_TILES_F32: defined in its own unit, gemm_inst_f32.hip
 
 }  // namespace ttg
