@@ -9,6 +9,7 @@
 //   the same LDS-DMA + swizzle as the GEMM.  K tile rows are permuted on the READ side (pi below) so
 //   that accumulator register r of a lane is key 16*(lane>>5)+r: P needs no data movement at all.
 //   Online softmax in fp32 with exp2; masked keys get -inf, running max starts at -1e30 (no NaN).
+#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 
@@ -37,32 +38,6 @@ struct AttnP {
 
 constexpr int QB = 128;   // queries per block
 constexpr int KB = 64;    // keys per tile
-
-// sum and sum of squares of one 16-byte operand chunk (fused LayerNorm statistics of the fused query projection; the same packed
-// dot products as gemm_kernel.h's ln_stat)
-typedef __attribute__((ext_vector_type(2))) _Float16 at_half2;
-typedef __attribute__((ext_vector_type(2))) __bf16 at_bf162;
-template <typename Tag> __device__ __forceinline__ void ln_stat_attn(const raw_u32x4_t& f, float& s, float& q) {}
-template <> __device__ __forceinline__ void ln_stat_attn<bf16_tag>(const raw_u32x4_t& f, float& s, float& q) {
-  const at_bf162 one = __builtin_bit_cast(at_bf162, 0x3F803F80u);
-  const unsigned w[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const at_bf162 x = __builtin_bit_cast(at_bf162, w[d]);
-    s = __builtin_amdgcn_fdot2_f32_bf16(x, one, s, false);
-    q = __builtin_amdgcn_fdot2_f32_bf16(x, x, q, false);
-  }
-}
-template <> __device__ __forceinline__ void ln_stat_attn<f16_tag>(const raw_u32x4_t& f, float& s, float& q) {
-  const at_half2 one = __builtin_bit_cast(at_half2, 0x3C003C00u);
-  const unsigned w[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const at_half2 x = __builtin_bit_cast(at_half2, w[d]);
-    s = __builtin_amdgcn_fdot2(x, one, s, false);
-    q = __builtin_amdgcn_fdot2(x, x, q, false);
-  }
-}
 
 // raw v_exp_f32: inputs here are <= 0 or -inf (exp2(-inf) = 0), no denormal/range fix-ups needed
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -98,6 +73,184 @@ __device__ __forceinline__ Bid3 xcd_remap3() {
   return o;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The pieces attn_kernel, attn_pipe_kernel and attn8_kernel share: one copy each, force-inlined.  The three kernels run the same
+// algorithm on the same lane layout (lane = one query, half hi, 16 keys of each 32-key block), so whatever does not depend on the
+// operand format or on the order of a tile's raw reads and waits lives here.
+
+// K-tile row read by MFMA row i = l31 so that accumulator reg r <-> key 16*hi + r  (see header)
+__device__ __forceinline__ int key_perm(int l31) { return 16 * ((l31 >> 2) & 1) + (l31 & 3) + 4 * (l31 >> 3); }
+
+// Q^T fragments straight from global (QES bytes per stored element): lane (query row qrow, half hi) holds the 16-byte chunks 2 n + hi
+// of its head's D elements; rows beyond lq read as zeros
+template <int QES, int D>
+__device__ __forceinline__ void load_q_frags(const AttnP& p, int seq, int head, int qrow, bool qok, int hi, uint4 (&qf)[D * QES / 32]) {
+  const char* qp = p.q + (((long)seq * p.lq + (qok ? qrow : 0)) * p.ldq + head * D) * QES;
+#pragma unroll
+  for (int n = 0; n < D * QES / 32; ++n) qf[n] = qok ? *(const uint4*)(qp + (n * 2 + hi) * 16) : make_uint4(0, 0, 0, 0);
+}
+
+// VR operand layout: the two per-lane addresses of the transposing reads (tile half `half` of a fragment's 8 keys); see attn_kernel's header
+__device__ __forceinline__ void vr_read_addrs(int lane, unsigned lds_base, unsigned (&out)[2]) {
+  const int gi = lane & 15, gg = lane >> 4, r2 = gi >> 2;
+  const int base = ((gg & 1) * 2 + ((gi & 3) >> 1)) ^ ((gi >> 3) & 1);
+#pragma unroll
+  for (int half = 0; half < 2; ++half)
+    out[half] = lds_base + (gg >> 1) * 2048 + r2 * 128 + half * 512 + ((base ^ (half << 1)) << 4) + (gi & 1) * 8;
+}
+
+// K / V^T staging by buffer_load ... lds (EB bytes per element: 1 = e4m3, 2, 4): per-lane 32-bit byte offsets computed once, the tile
+// position is a scalar offset, out-of-range rows/columns land beyond num_records and read as zeros (same scheme as gemm.hip).
+// A stage of the ring is the K tile ([64 keys][D], 16-byte chunks swizzled per row) followed by the V^T tile ([D][64 keys]; VR: V itself,
+// rows = keys like the K tile).
+template <int EB, int D, bool VR>
+struct KvStage {
+  static constexpr int EPC = 16 / EB;                                   // elements per 16-byte chunk
+  static constexpr int KCPR = D / EPC, VCPR = KB / EPC;                 // 16-B chunks per K-tile row (row = key, D elements) / per V^T-tile row (row = d, 64 keys)
+  static constexpr int K_BYTES = KB * D * EB, V_BYTES = D * KB * EB, STAGE = K_BYTES + V_BYTES;
+  static constexpr int KPT = (KB * KCPR) / 256, VPT = (D * VCPR) / 256;  // chunks per thread
+  static constexpr int INV = (int)0x80000000;
+  static_assert(KPT >= 1 && VPT >= 1, "tile smaller than the block");
+  const AttnP& p;
+  char* const ring;                                                     // this wave's first piece of stage 0
+  const __amdgpu_buffer_rsrc_t rk, rv;
+  int kvo[KPT], kr[KPT], vvo[VPT], vc[VPT];
+  const int k_rows_left;                                                // rows of K that exist from kbase on
+  const long v_cols_left;
+  __device__ __forceinline__ KvStage(const AttnP& p_, char* smem, int tid, int wid, int head, int kbase, int vbase)
+      : p(p_), ring(smem + wid * 1024),
+        rk(__builtin_amdgcn_make_buffer_rsrc((void*)p_.k, 0, p_.k_bytes, 0x00020000)),
+        rv(__builtin_amdgcn_make_buffer_rsrc((void*)p_.vt, 0, p_.vt_bytes, 0x00020000)),
+        k_rows_left(p_.k_rows_total - kbase), v_cols_left(p_.vt_cols_total - vbase) {
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      const int slot = i * 256 + tid;
+      const int r = slot / KCPR, c = (slot % KCPR) ^ tile_swz<KCPR>(r);
+      kr[i] = r;
+      kvo[i] = (int)((((long)kbase + r) * p.ldk + head * D + c * EPC) * EB);
+    }
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      const int slot = i * 256 + tid;
+      const int r = slot / VCPR, c = (slot % VCPR) ^ tile_swz<VCPR>(r);
+      if constexpr (VR) {                                      // rows = keys, like the K tile
+        vc[i] = r;
+        vvo[i] = (int)((((long)vbase + r) * p.ldvt + head * D + c * EPC) * EB);
+      } else {
+        vc[i] = c * EPC;
+        vvo[i] = (int)(((long)(head * D + r) * p.ldvt + vbase + c * EPC) * EB);
+      }
+    }
+  }
+  __device__ __forceinline__ void stage(int buf, int tile) const {
+    const int j0 = tile * KB;
+    char* lk_ = ring + buf * STAGE;
+    char* lv_ = ring + buf * STAGE + K_BYTES;
+    const int soff_k = __builtin_amdgcn_readfirstlane((int)((long)j0 * p.ldk * EB));
+    const int soff_v = VR ? __builtin_amdgcn_readfirstlane((int)((long)j0 * p.ldvt * EB)) : j0 * EB;
+    const bool edge = j0 + KB > k_rows_left || j0 + KB > v_cols_left;    // uniform: only the last tile(s)
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      int v = kvo[i];
+      if (edge && j0 + kr[i] >= k_rows_left) v = INV;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)(lk_ + i * 4096), 16, v, soff_k, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      int v = vvo[i];
+      if (edge && j0 + vc[i] >= v_cols_left) v = INV;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(lv_ + i * 4096), 16, v, soff_v, 0, 0);
+    }
+  }
+};
+
+// The tile loop: unrolled by two over the buffer parity (buffer and K / V split sit in the read instructions' immediates); only the
+// last tile can hold keys >= lk and only it is compiled with the masking.  tile(t, buffer parity, masked).
+template <typename F>
+__device__ __forceinline__ void for_each_tile(int ntiles, int lk, F&& tile) {
+  const bool ragged = (lk % KB) != 0;
+  const int full = ragged ? ntiles - 1 : ntiles;
+  int t = 0;
+  for (; t + 1 < full; t += 2) {
+    tile(t, std::integral_constant<int, 0>{}, std::false_type{});
+    tile(t + 1, std::integral_constant<int, 1>{}, std::false_type{});
+  }
+  if (t < full) {
+    tile(t, std::integral_constant<int, 0>{}, std::false_type{});
+    if (ragged) tile(t + 1, std::integral_constant<int, 1>{}, std::true_type{});
+  } else if (ragged) {
+    tile(t, std::integral_constant<int, 0>{}, std::true_type{});
+  }
+}
+
+// the ragged last tile t: keys >= lk score -inf (lane: keys t*KB + kb*32 + hi*16 + r)
+__device__ __forceinline__ void mask_ragged(f32x16_t (&s)[2], int t, int hi, int lk) {
+  const int j0 = t * KB;
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int j = j0 + kb * 32 + hi * 16 + r;
+      if (j >= lk) s[kb][r] = -INFINITY;
+    }
+}
+
+// Slow path of the lazy softmax reference (attn_kernel's tile has the whole idea): the tile's true maximum becomes the reference,
+// l_run and the NO output accumulators (SP: the cross-term accumulators ox as well) are rescaled to it.  The caller re-exponentiates
+// its scores against the new m_run in its own format.
+template <int NO, bool WITH_OX = false>
+__device__ __forceinline__ void softmax_rescale(const f32x16_t (&s)[2], float scale_log2e, float& m_run, float& l_run, f32x16_t (&o)[NO],
+                                                f32x16_t* ox = nullptr) {
+  float mx = s[0][0];
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const float m_new = fmaxf(m_run, mx * scale_log2e);       // per query: both lane halves agree
+  const float alpha = fast_exp2(m_run - m_new);             // 1 for the queries whose reference stays
+  l_run *= alpha;
+#pragma unroll
+  for (int i = 0; i < NO; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o[i][r] *= alpha; if constexpr (WITH_OX) ox[i][r] *= alpha; }
+  m_run = m_new;
+}
+
+// Epilogue: lane holds query l31, d = db*32 + 8g + 4hi + {0..3}.  Stored directly an instruction would write 16 bytes to each of
+// 32 rows; instead the wave's 32 x D outputs go through a private LDS strip (the K/V ring is free once every wave has passed the
+// barrier in here) and leave as full rows: 8 (D = 64, 16-bit) or more lanes cover one row's D*ES contiguous bytes.  Block qblk owns
+// query rows (qblk * QB + i) * qstride + qcls (mask 2: one residue class; everything else 1, 0).
+template <typename Tag, int D>
+__device__ __forceinline__ void attn_store_rows(const AttnP& p, char* smem, const f32x16_t (&o)[D / 32], float l_run, int wid, int lane,
+                                                int seq, int head, int qblk, int qstride, int qcls) {
+  typedef typename Elem<Tag>::quad_t quad_t;
+  constexpr int ES = Elem<Tag>::ES;
+  const int l31 = lane & 31, hi = lane >> 5;
+  const float l_tot = l_run + __shfl_xor(l_run, 32);
+  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+  __syncthreads();                                     // every wave is done with the K / V tiles
+  constexpr int ROWB_O = D * ES, CPR_O = ROWB_O / 16;  // output row bytes per head, 16-byte chunks per row
+  char* strip = smem + wid * (32 * ROWB_O);
+#pragma unroll
+  for (int db = 0; db < D / 32; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int byte = (db * 32 + 8 * g + 4 * hi) * ES;   // this lane's 4 consecutive d of query row l31
+      const float v4[4] = {o[db][g * 4] * inv, o[db][g * 4 + 1] * inv, o[db][g * 4 + 2] * inv, o[db][g * 4 + 3] * inv};
+      *(quad_t*)(strip + l31 * ROWB_O + (((byte >> 4) ^ (l31 & (CPR_O - 1))) << 4) + (byte & 15)) = f32_to_quad<Tag>(v4);
+    }
+  constexpr int RPP = 64 / CPR_O;                      // rows per pass
+  const int oc = lane % CPR_O, orow = lane / CPR_O;
+#pragma unroll
+  for (int pass = 0; pass < 32 / RPP; ++pass) {
+    const int r = pass * RPP + orow;
+    const uint4 v = *(const uint4*)(strip + r * ROWB_O + ((oc ^ (r & (CPR_O - 1))) << 4));
+    const int qr = (qblk * QB + wid * 32 + r) * qstride + qcls;
+    if (qr < p.lq) *(uint4*)(p.out + (((long)seq * p.lq + qr) * p.ldo + head * D) * ES + oc * 16) = v;
+  }
+}
+
 // QP (cross-attention, D = 64, 16-bit storage): the block computes its own queries.  Q_h[128 x 64] = LN(x rows) Wq_h^T + bq_h is a
 // 128 x 64 x C mini-GEMM in front of the key loop (x rows and the head's 64 rows of Wq staged slab by slab through a 3-deep
 // LDS ring; LayerNorm folded into Wq by the caller, 1/sigma from the operand fragments as in tt_gemm ln_fold = 1) whose
@@ -124,15 +277,9 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
   // at 61 % matrix-pipe use, the kernel sits at 47 %.)
   kernarg_touch<sizeof(AttnP)>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef typename Elem<Tag>::quad_t quad_t;
   constexpr int ES = Elem<Tag>::ES, EPC = Elem<Tag>::EPC;   // bytes per element, elements per 16-byte chunk
-  constexpr int KCPR = D / EPC;               // 16-B chunks per K-tile row (row = key, D elements)
-  constexpr int VCPR = KB / EPC;              // 16-B chunks per V^T-tile row (row = d, 64 keys)
-  constexpr int K_BYTES = KB * D * ES;
-  constexpr int V_BYTES = D * KB * ES;        // rows = d (D rows), 64 keys per row
-  constexpr int STAGE = K_BYTES + V_BYTES;
-  constexpr int KPT = (KB * KCPR) / 256;      // K chunks per thread
-  constexpr int VPT = (D * VCPR) / 256;       // Vt chunks per thread
+  typedef KvStage<ES, D, VR> Stage;
+  constexpr int KCPR = Stage::KCPR, VCPR = Stage::VCPR, K_BYTES = Stage::K_BYTES, STAGE = Stage::STAGE;
   constexpr int DS = KCPR / 2, DB = D / 32;   // operand reads per K row (one chunk per lane half), 32-wide d blocks
   constexpr int PH = 16 / EPC;                // P chunks per lane per 32-key block
 
@@ -165,9 +312,7 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
   const bool qok = qrow < p.lq;
   uint4 qf[DS];
   if constexpr (!QP) {
-    const char* qp = p.q + (((long)seq * p.lq + (qok ? qrow : 0)) * p.ldq + head * D) * ES;
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds) qf[ds] = qok ? *(const uint4*)(qp + (ds * 2 + hi) * 16) : make_uint4(0, 0, 0, 0);
+    load_q_frags<ES, D>(p, seq, head, qrow, qok, hi, qf);
   } else {
     static_assert(!QP || (D == 64 && ES == 2 && MASK != 0), "fused query projection: cross-attention, head dimension 64, 16-bit storage");
     constexpr int QSLAB = QB * 128 + 64 * 128, QNST = 3;      // 16 KiB of x rows + 8 KiB of Wq rows per 64-deep slab
@@ -228,7 +373,7 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
       lds_wait<0>();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        ln_stat_attn<Tag>(xf[ks], ls, lq2);
+        ln_stat<Tag>(xf[ks], ls, lq2);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           qa[j] = Cvt<Tag>::mfma32(make_uint4(wf[j][ks].x, wf[j][ks].y, wf[j][ks].z, wf[j][ks].w),
@@ -253,53 +398,7 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
     }
   }
 
-  // staging by buffer_load ... lds: per-lane 32-bit byte offsets computed once, the tile position is a scalar offset,
-  // out-of-range rows/columns land beyond num_records and read as zeros (same scheme as gemm.hip).
-  constexpr int INV = (int)0x80000000;
-  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)p.k, 0, p.k_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)p.vt, 0, p.vt_bytes, 0x00020000);
-  int kvo[KPT], kr[KPT], vvo[VPT], vc[VPT];
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    const int slot = i * 256 + tid;
-    const int r = slot / KCPR, c = (slot % KCPR) ^ tile_swz<KCPR>(r);
-    kr[i] = r;
-    kvo[i] = (int)((((long)kbase + r) * p.ldk + head * D + c * EPC) * ES);
-  }
-#pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int slot = i * 256 + tid;
-    const int r = slot / VCPR, c = (slot % VCPR) ^ tile_swz<VCPR>(r);
-    if constexpr (VR) {                                      // rows = keys, like the K tile
-      vc[i] = r;
-      vvo[i] = (int)((((long)vbase + r) * p.ldvt + head * D + c * EPC) * ES);
-    } else {
-      vc[i] = c * EPC;
-      vvo[i] = (int)(((long)(head * D + r) * p.ldvt + vbase + c * EPC) * ES);
-    }
-  }
-  const int k_rows_left = p.k_rows_total - kbase;            // rows of K that exist from kbase on
-  const long v_cols_left = p.vt_cols_total - vbase;
-  auto stage = [&](int buf, int tile) {
-    const int j0 = tile * KB;
-    char* lk_ = smem + buf * STAGE + wid * 1024;
-    char* lv_ = smem + buf * STAGE + K_BYTES + wid * 1024;
-    const int soff_k = __builtin_amdgcn_readfirstlane((int)((long)j0 * p.ldk * ES));
-    const int soff_v = VR ? __builtin_amdgcn_readfirstlane((int)((long)j0 * p.ldvt * ES)) : j0 * ES;
-    const bool edge = j0 + KB > k_rows_left || j0 + KB > v_cols_left;    // uniform: only the last tile(s)
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-      int v = kvo[i];
-      if (edge && j0 + kr[i] >= k_rows_left) v = INV;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)(lk_ + i * 4096), 16, v, soff_k, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-      int v = vvo[i];
-      if (edge && j0 + vc[i] >= v_cols_left) v = INV;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(lv_ + i * 4096), 16, v, soff_v, 0, 0);
-    }
-  };
+  const Stage kv(p, smem, tid, wid, head, kbase, vbase);
 
   f32x16_t o[DB];
 #pragma unroll
@@ -323,8 +422,7 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
     }
   }
 
-  // K-tile row read by MFMA row i = l31 so that accumulator reg r <-> key 16*hi + r  (see header)
-  const int pi = 16 * ((l31 >> 2) & 1) + (l31 & 3) + 4 * (l31 >> 3);
+  const int pi = key_perm(l31);
 
   // ---- LDS addresses of the fragments this lane reads from a K / V^T tile.  The swizzle XOR depends on the lane's row, so
   // it cannot sit in the instruction's immediate; the stage (buffer parity) and the K/V split can -- the tile loop is
@@ -343,15 +441,8 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
 #pragma unroll
       for (int k = 0; k < 2 * PH; ++k) vaddr[db][k] = lds_base + tile_off<VCPR>(db * 32 + l31, (k / PH) * (32 / EPC) + hi * PH + k % PH);
   }
-  // VR: the two per-lane addresses of the transposing reads (tile half `half` of a fragment's 8 keys); see the kernel's header
   unsigned vr_addr[2] = {0u, 0u};
-  if constexpr (VR) {
-    const int gi = lane & 15, gg = lane >> 4, r2 = gi >> 2;
-    const int base = ((gg & 1) * 2 + ((gi & 3) >> 1)) ^ ((gi >> 3) & 1);
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-      vr_addr[half] = lds_base + (gg >> 1) * 2048 + r2 * 128 + half * 512 + ((base ^ (half << 1)) << 4) + (gi & 1) * 8;
-  }
+  if constexpr (VR) vr_read_addrs(lane, lds_base, vr_addr);
   auto k_addr = [&](int kb, int ds) -> unsigned {
     if constexpr (PRE) return kaddr[kb][ds]; else return lds_base + tile_off<KCPR>(kb * 32 + pi, ds * 2 + hi);
   };
@@ -373,7 +464,7 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
     constexpr int KOFF = BUF * STAGE, VOFF = BUF * STAGE + K_BYTES;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's share of tile t has landed ...
     __syncthreads();                                           // ... and everybody's; the other buffer is free
-    if (t + 1 < ntiles) stage(BUF ^ 1, t + 1);
+    if (t + 1 < ntiles) kv.stage(BUF ^ 1, t + 1);
     raw_u32x4_t fa[4], fb[4];                                  // two fragment batches (K first, then V^T)
     auto read_k = [&](int i, raw_u32x4_t (&f)[4]) {
 #pragma unroll
@@ -445,16 +536,7 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
     }
     // ---- mask + online softmax (lane: one query, keys j0 + kb*32 + hi*16 + r).  Raw scores stay unscaled: the
     // 1/sqrt(d)*log2(e) factor c is folded into the exponent, p = exp2(s*c - m*c), one FMA per score.
-    if constexpr (MASKED) {
-      const int j0 = t * KB;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = j0 + kb * 32 + hi * 16 + r;
-          if (j >= p.lk) s[kb][r] = -INFINITY;
-        }
-    }
+    if constexpr (MASKED) mask_ragged(s, t, hi, p.lk);
     // LAZY reference point, OPTIMISTIC evaluation.  Softmax is invariant to the subtracted constant, so the running "max" m_run
     // only has to keep exp2 in range.  Fast path: exponentiate against the m_run we have and look at the row sum -- if every
     // lane's partial sum of this tile is <= 2^14, no P exceeds 2^14 (fine for fp32 sums and 16-bit P) and the tile is done
@@ -479,21 +561,7 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
     };
     exponentiate(m_run);
     if (__any(!(psum <= PSUM_OK))) {                            // (also catches inf / NaN)
-      float mx = s[0][0];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mxs = mx * p.scale_log2e;
-      const float m_new = fmaxf(m_run, mxs);                    // per query: both lane halves agree
-      const float alpha = fast_exp2(m_run - m_new);             // 1 for the queries whose reference stays
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < DB; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o[i][r] *= alpha; if constexpr (SP) ox[i][r] *= alpha; }
-      m_run = m_new;
+      softmax_rescale<DB, SP>(s, p.scale_log2e, m_run, l_run, o, ox);
       exponentiate(m_run);
     }
     l_run += psum;
@@ -552,52 +620,16 @@ __global__ __launch_bounds__(256, (D == 64 && Elem<Tag>::ES == 2) ? 2 : 1) void 
     }
   };
 
-  stage(0, 0);
-  const bool ragged = (p.lk % KB) != 0;                         // only the last tile can hold keys >= lk
-  const int full = ragged ? ntiles - 1 : ntiles;
-  int t = 0;
-  for (; t + 1 < full; t += 2) {
-    tile(t, std::integral_constant<int, 0>{}, std::false_type{});
-    tile(t + 1, std::integral_constant<int, 1>{}, std::false_type{});
-  }
-  if (t < full) {
-    tile(t, std::integral_constant<int, 0>{}, std::false_type{});
-    if (ragged) tile(t + 1, std::integral_constant<int, 1>{}, std::true_type{});
-  } else if (ragged) {
-    tile(t, std::integral_constant<int, 0>{}, std::true_type{});
-  }
-  // ---- finalize: lane holds query l31, d = db*32 + 8g + 4hi + {0..3}.  Stored directly an instruction would write 16
-  // bytes to each of 32 rows; instead the wave's 32 x D outputs go through a private LDS strip (the K/V ring is free
-  // now) and leave as full rows: 8 (D = 64) or 16 lanes cover one row's D*2 contiguous bytes.
+  kv.stage(0, 0);
+  for_each_tile(ntiles, p.lk, tile);
   if constexpr (SP) {
 #pragma unroll
     for (int i = 0; i < DB; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[i][r] = fmaf(ox[i][r], 32.0f, o[i][r] * 65536.0f);
   }
-  float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  __syncthreads();                                     // every wave is done with the K / V tiles
-  constexpr int ROWB_O = D * ES, CPR_O = ROWB_O / 16;  // output row bytes per head, 16-byte chunks per row
-  char* strip = smem + wid * (32 * ROWB_O);
-  static_assert(4 * 32 * ROWB_O <= 2 * STAGE, "output strips do not fit the K/V ring");
-#pragma unroll
-  for (int db = 0; db < DB; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int byte = (db * 32 + 8 * g + 4 * hi) * ES;   // this lane's 4 consecutive d of query row l31
-      const float v4[4] = {o[db][g * 4] * inv, o[db][g * 4 + 1] * inv, o[db][g * 4 + 2] * inv, o[db][g * 4 + 3] * inv};
-      *(quad_t*)(strip + l31 * ROWB_O + (((byte >> 4) ^ (l31 & (CPR_O - 1))) << 4) + (byte & 15)) = f32_to_quad<Tag>(v4);
-    }
-  constexpr int RPP = 64 / CPR_O;                      // rows per pass
-  const int oc = lane % CPR_O, orow = lane / CPR_O;
-#pragma unroll
-  for (int pass = 0; pass < 32 / RPP; ++pass) {
-    const int r = pass * RPP + orow;
-    const uint4 v = *(const uint4*)(strip + r * ROWB_O + ((oc ^ (r & (CPR_O - 1))) << 4));
-    const int qr = (qblk * QB + wid * 32 + r) * qstride + qcls;
-    if (qr < p.lq) *(uint4*)(p.out + (((long)seq * p.lq + qr) * p.ldo + head * D) * ES + oc * 16) = v;
-  }
+  static_assert(4 * 32 * D * ES <= 2 * STAGE, "output strips do not fit the K/V ring");
+  attn_store_rows<Tag, D>(p, smem, o, l_run, wid, lane, seq, head, qblk, qstride, qcls);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -622,7 +654,6 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnP p) {
   static_assert(Elem<Tag>::ES == 2, "16-bit storage");
   kernarg_touch<sizeof(AttnP)>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef typename Elem<Tag>::quad_t quad_t;
   constexpr int D = 64, ES = 2, EPC = 8, CPR = 8;            // 128-byte tile rows (K: [64 keys][64 d]; V the same, keys as rows)
   constexpr int K_BYTES = KB * D * ES, V_BYTES = KB * D * ES, PT = (KB * CPR) / 256;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -636,13 +667,10 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnP p) {
   const int qrow = blk.x * QB + wid * 32 + l31;
   const bool qok = qrow < p.lq;
   uint4 qf[4];
-  {
-    const char* qp = p.q + (((long)seq * p.lq + (qok ? qrow : 0)) * p.ldq + head * D) * ES;
-#pragma unroll
-    for (int ds = 0; ds < 4; ++ds) qf[ds] = qok ? *(const uint4*)(qp + (ds * 2 + hi) * 16) : make_uint4(0, 0, 0, 0);
-  }
+  load_q_frags<ES, D>(p, seq, head, qrow, qok, hi, qf);
   const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)p.k, 0, p.k_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)p.vt, 0, p.vt_bytes, 0x00020000);
+  // (Its own two stagers, not KvStage: K(t+1) and V(t) are staged in different iterations into separate rings, and whole tiles need no edge handling.)
   int kvo[PT], vvo[PT];
 #pragma unroll
   for (int i = 0; i < PT; ++i) {
@@ -676,19 +704,13 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnP p) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) P[c] = make_uint4(0, 0, 0, 0);
 
-  const int pi = 16 * ((l31 >> 2) & 1) + (l31 & 3) + 4 * (l31 >> 3);          // (attn_kernel: accumulator register r <-> key 16 hi + r)
+  const int pi = key_perm(l31);
   const unsigned lds_base = lds_addr(smem);
   unsigned kaddr[4];                                         // key block 0; key block 1 is + 32 rows = + 4096 bytes (the swizzle only sees row bits 1-3)
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) kaddr[ds] = lds_base + tile_off<CPR>(pi, ds * 2 + hi);
   unsigned vr_addr[2];
-  {
-    const int gi = lane & 15, gg = lane >> 4, r2 = gi >> 2;
-    const int base = ((gg & 1) * 2 + ((gi & 3) >> 1)) ^ ((gi >> 3) & 1);
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-      vr_addr[half] = lds_base + (gg >> 1) * 2048 + r2 * 128 + half * 512 + ((base ^ (half << 1)) << 4) + (gi & 1) * 8;
-  }
+  vr_read_addrs(lane, lds_base, vr_addr);
   constexpr float PSUM_OK = 16384.0f;
 
   auto tile = [&](int t, auto buf_tag, auto pv_tag) {
@@ -774,21 +796,8 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnP p) {
     } else {
       exp_chunk(2); exp_chunk(3);
     }
-    if (__any(!(psum <= PSUM_OK))) {                            // the tile outgrew the reference (always on the first tile): attn_kernel's slow path
-      float mx = sc[0][0];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[kb][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float m_new = fmaxf(m_run, mx * p.scale_log2e);
-      const float alpha = fast_exp2(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-      m_run = m_new;
+    if (__any(!(psum <= PSUM_OK))) {                            // the tile outgrew the reference (always on the first tile)
+      softmax_rescale<2>(sc, p.scale_log2e, m_run, l_run, o);
       psum = 0.f;
       exp_chunk(0); exp_chunk(1); exp_chunk(2); exp_chunk(3);
     }
@@ -834,29 +843,7 @@ __global__ __launch_bounds__(256, 2) void attn_pipe_kernel(const AttnP p) {
   };
   if ((nt - 1) & 1) final_pv(B1{}); else final_pv(B0{});
 
-  // ---- finalize (attn_kernel's: the wave's 32 x 64 outputs leave through a private LDS strip as whole rows)
-  const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  __syncthreads();
-  constexpr int ROWB_O = D * ES, CPR_O = ROWB_O / 16;
-  char* strip = smem + wid * (32 * ROWB_O);
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int byte = (db * 32 + 8 * g + 4 * hi) * ES;
-      const float v4[4] = {o[db][g * 4] * inv, o[db][g * 4 + 1] * inv, o[db][g * 4 + 2] * inv, o[db][g * 4 + 3] * inv};
-      *(quad_t*)(strip + l31 * ROWB_O + (((byte >> 4) ^ (l31 & (CPR_O - 1))) << 4) + (byte & 15)) = f32_to_quad<Tag>(v4);
-    }
-  constexpr int RPP = 64 / CPR_O;
-  const int oc = lane % CPR_O, orow = lane / CPR_O;
-#pragma unroll
-  for (int pass = 0; pass < 32 / RPP; ++pass) {
-    const int r = pass * RPP + orow;
-    const uint4 v = *(const uint4*)(strip + r * ROWB_O + ((oc ^ (r & (CPR_O - 1))) << 4));
-    const int qr = blk.x * QB + wid * 32 + r;
-    if (qr < p.lq) *(uint4*)(p.out + (((long)seq * p.lq + qr) * p.ldo + head * D) * ES + oc * 16) = v;
-  }
+  attn_store_rows<Tag, D>(p, smem, o, l_run, wid, lane, seq, head, blk.x, 1, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -877,13 +864,9 @@ template <typename Tag, int D>
 __global__ __launch_bounds__(256, 2) void attn8_kernel(const AttnP p) {
   kernarg_touch<sizeof(AttnP)>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef typename Elem<Tag>::quad_t quad_t;
-  constexpr int ES = Elem<Tag>::ES;             // OUTPUT element size
-  constexpr int KCPR = D / 16, VCPR = KB / 16;  // 16-byte chunks per K row (D e4m3) / V^T row (64 keys)
-  constexpr int K_BYTES = KB * D, V_BYTES = D * KB, STAGE = K_BYTES + V_BYTES;
-  constexpr int KPT = (KB * KCPR) / 256, VPT = (D * VCPR) / 256;
+  typedef KvStage<1, D, false> Stage;             // e4m3 operands; the OUTPUT element size is Elem<Tag>::ES
+  constexpr int KCPR = Stage::KCPR, VCPR = Stage::VCPR, K_BYTES = Stage::K_BYTES, STAGE = Stage::STAGE;
   constexpr int JJ = D / 32, DB = D / 32;       // chunk reads per K row per lane, 32-wide d blocks
-  static_assert(KPT >= 1 && VPT >= 1, "tile smaller than the block");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
@@ -894,58 +877,15 @@ __global__ __launch_bounds__(256, 2) void attn8_kernel(const AttnP p) {
   const int qrow = qblk * QB + wid * 32 + l31;
   const bool qok = qrow < p.lq;
   uint4 qf[JJ];
-  {
-    const char* qp = p.q + ((long)seq * p.lq + (qok ? qrow : 0)) * p.ldq + head * D;
-#pragma unroll
-    for (int jj = 0; jj < JJ; ++jj) qf[jj] = qok ? *(const uint4*)(qp + (2 * jj + hi) * 16) : make_uint4(0, 0, 0, 0);
-  }
-  constexpr int INV = (int)0x80000000;
-  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)p.k, 0, p.k_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)p.vt, 0, p.vt_bytes, 0x00020000);
-  int kvo[KPT], kr[KPT], vvo[VPT], vc[VPT];
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    const int slot = i * 256 + tid;
-    const int r = slot / KCPR, c = (slot % KCPR) ^ tile_swz<KCPR>(r);
-    kr[i] = r;
-    kvo[i] = (int)(((long)kbase + r) * p.ldk + head * D + c * 16);
-  }
-#pragma unroll
-  for (int i = 0; i < VPT; ++i) {
-    const int slot = i * 256 + tid;
-    const int r = slot / VCPR, c = (slot % VCPR) ^ tile_swz<VCPR>(r);
-    vc[i] = c * 16;
-    vvo[i] = (int)((long)(head * D + r) * p.ldvt + vbase + c * 16);
-  }
-  const int k_rows_left = p.k_rows_total - kbase;
-  const long v_cols_left = p.vt_cols_total - vbase;
-  auto stage = [&](int buf, int tile) {
-    const int j0 = tile * KB;
-    char* lk_ = smem + buf * STAGE + wid * 1024;
-    char* lv_ = smem + buf * STAGE + K_BYTES + wid * 1024;
-    const int soff_k = __builtin_amdgcn_readfirstlane((int)((long)j0 * p.ldk));
-    const int soff_v = j0;
-    const bool edge = j0 + KB > k_rows_left || j0 + KB > v_cols_left;
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-      int v = kvo[i];
-      if (edge && j0 + kr[i] >= k_rows_left) v = INV;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)(lk_ + i * 4096), 16, v, soff_k, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-      int v = vvo[i];
-      if (edge && j0 + vc[i] >= v_cols_left) v = INV;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(lv_ + i * 4096), 16, v, soff_v, 0, 0);
-    }
-  };
+  load_q_frags<1, D>(p, seq, head, qrow, qok, hi, qf);
+  const Stage kv(p, smem, tid, wid, head, kbase, vbase);
   f32x16_t o[DB];
 #pragma unroll
   for (int i = 0; i < DB; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
   float m_run = -1e30f, l_run = 0.f;
-  const int pi = 16 * ((l31 >> 2) & 1) + (l31 & 3) + 4 * (l31 >> 3);      // see attn_kernel: accumulator reg r <-> key 16 hi + r
+  const int pi = key_perm(l31);
   const unsigned lds_base = lds_addr(smem);
   unsigned kaddr[2][JJ], vaddr[DB][2];
 #pragma unroll
@@ -975,7 +915,7 @@ __global__ __launch_bounds__(256, 2) void attn8_kernel(const AttnP p) {
     constexpr int KOFF = BUF * STAGE, VOFF = BUF * STAGE + K_BYTES;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (t + 1 < ntiles) stage(BUF ^ 1, t + 1);
+    if (t + 1 < ntiles) kv.stage(BUF ^ 1, t + 1);
     raw_u32x4_t kf[2][JJ], vf[DB][2];
 #pragma unroll
     for (int jj = 0; jj < JJ; ++jj)
@@ -997,16 +937,7 @@ __global__ __launch_bounds__(256, 2) void attn8_kernel(const AttnP p) {
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int db = 0; db < DB; ++db) vf[db][kb] = lds_read16_raw_off<VOFF>(vaddr[db][kb]);      // land under the softmax
-    if constexpr (MASKED) {
-      const int j0 = t * KB;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = j0 + kb * 32 + hi * 16 + r;
-          if (j >= p.lk) s[kb][r] = -INFINITY;
-        }
-    }
+    if constexpr (MASKED) mask_ragged(s, t, hi, p.lk);
     // lazy reference point, optimistic evaluation as in attn_kernel, with e4m3's range in mind: P' = 8 * exp2(s c - m_run), and
     // the tile is accepted when every lane's partial row sum is <= 448 -- then no P' exceeds e4m3's largest value.  The slow path
     // (first tile, or scores that outgrew the reference by ~2^5) makes the tile's true maximum the reference, so a row maximum
@@ -1033,20 +964,7 @@ __global__ __launch_bounds__(256, 2) void attn8_kernel(const AttnP p) {
     };
     exponentiate(P_LOG2 - m_run);
     if (__any(!(psum <= PSUM_OK))) {                                       // (also catches inf / NaN: first tile, m_run = -1e30)
-      float mx = s[0][0];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float m_new = fmaxf(m_run, mx * p.scale_log2e);
-      const float alpha = fast_exp2(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < DB; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-      m_run = m_new;
+      softmax_rescale<DB>(s, p.scale_log2e, m_run, l_run, o);
       exponentiate(P_LOG2 - m_run);
     }
     l_run += psum;
@@ -1057,122 +975,19 @@ __global__ __launch_bounds__(256, 2) void attn8_kernel(const AttnP p) {
     for (int db = 0; db < DB; ++db) o[db] = mfma8(pack8(vf[db][0], vf[db][1]), pv, o[db]);
     __builtin_amdgcn_sched_barrier(0);
   };
-  stage(0, 0);
-  const bool ragged = (p.lk % KB) != 0;
-  const int full = ragged ? ntiles - 1 : ntiles;
-  int t = 0;
-  for (; t + 1 < full; t += 2) {
-    tile(t, std::integral_constant<int, 0>{}, std::false_type{});
-    tile(t + 1, std::integral_constant<int, 1>{}, std::false_type{});
-  }
-  if (t < full) {
-    tile(t, std::integral_constant<int, 0>{}, std::false_type{});
-    if (ragged) tile(t + 1, std::integral_constant<int, 1>{}, std::true_type{});
-  } else if (ragged) {
-    tile(t, std::integral_constant<int, 0>{}, std::true_type{});
-  }
-  // ---- finalize (as attn_kernel): rows leave through a wave-private LDS strip as full D*ES-byte rows
-  float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  __syncthreads();
-  constexpr int ROWB_O = D * ES, CPR_O = ROWB_O / 16;
-  char* strip = smem + wid * (32 * ROWB_O);
-#pragma unroll
-  for (int db = 0; db < DB; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int byte = (db * 32 + 8 * g + 4 * hi) * ES;
-      const float v4[4] = {o[db][g * 4] * inv, o[db][g * 4 + 1] * inv, o[db][g * 4 + 2] * inv, o[db][g * 4 + 3] * inv};
-      *(quad_t*)(strip + l31 * ROWB_O + (((byte >> 4) ^ (l31 & (CPR_O - 1))) << 4) + (byte & 15)) = f32_to_quad<Tag>(v4);
-    }
-  constexpr int RPP = 64 / CPR_O;
-  const int oc = lane % CPR_O, orow = lane / CPR_O;
-#pragma unroll
-  for (int pass = 0; pass < 32 / RPP; ++pass) {
-    const int r = pass * RPP + orow;
-    const uint4 v = *(const uint4*)(strip + r * ROWB_O + ((oc ^ (r & (CPR_O - 1))) << 4));
-    const int qr = qblk * QB + wid * 32 + r;
-    if (qr < p.lq) *(uint4*)(p.out + (((long)seq * p.lq + qr) * p.ldo + head * D) * ES + oc * 16) = v;
-  }
-}
-
-template <typename Tag, int D>
-void launch_attn8(const AttnP& p, hipStream_t st) {
-  // the K/V ring (2 x 2 x 64 x D bytes) doubles as the 4 x 32 x D*ES-byte output strips
-  constexpr size_t ring = 2 * (KB * D + D * KB), strips = 4 * 32 * D * Elem<Tag>::ES;
-  constexpr size_t lds = ring > strips ? ring : strips;
-  static unsigned long long attr_done = 0;
-  tt_lds_opt_in((const void*)attn8_kernel<Tag, D>, (int)lds, &attr_done);
-  const dim3 grid((p.lq + QB - 1) / QB, p.heads, p.nseq);
-  hipLaunchKernelGGL((attn8_kernel<Tag, D>), grid, dim3(256), lds, st, p);
-}
-
-template <typename Tag, int D, int MASK>
-void launch_attn_m(const AttnP& p, hipStream_t st) {
-  constexpr size_t lds = 2 * (KB * D * Elem<Tag>::ES + D * KB * Elem<Tag>::ES);
-  static_assert(lds <= 160 * 1024, "attention K/V ring exceeds the LDS");
-  // mask 2: one block per (query residue class, QB queries of that class)
-  const int cls = MASK == 2 ? p.ctx_batches : 1;
-  const dim3 grid(cls * ((((p.lq + cls - 1) / cls) + QB - 1) / QB), p.heads, p.nseq);
-  if constexpr (Elem<Tag>::ES == 4 && D == 64) {      // (head dimension 128 keeps the exact-fp32 MFMA: its split variant spills 1 KiB per lane)
-    if (tt_internal_f32_split()) {             // TT_F32 "split16": the split-product variant of the same kernel
-      static unsigned long long attr_done_sp = 0;
-      tt_lds_opt_in((const void*)attn_kernel<Tag, D, MASK, false, false, true>, (int)lds, &attr_done_sp);
-      hipLaunchKernelGGL((attn_kernel<Tag, D, MASK, false, false, true>), grid, dim3(256), lds, st, p);
-      return;
-    }
-  }
-  static unsigned long long attr_done = 0;
-  tt_lds_opt_in((const void*)attn_kernel<Tag, D, MASK>, (int)lds, &attr_done);
-  hipLaunchKernelGGL((attn_kernel<Tag, D, MASK>), grid, dim3(256), lds, st, p);
-}
-// cross-attention with the query projection fused in (D = 64, 16-bit): LDS = the 3 x 24 KiB projection ring (the K / V^T ring reuses it)
-template <typename Tag, int MASK>
-void launch_attn_qp(const AttnP& p, hipStream_t st) {
-  constexpr size_t lds = 3 * (QB * 128 + 64 * 128);
-  static unsigned long long attr_done = 0;
-  tt_lds_opt_in((const void*)attn_kernel<Tag, 64, MASK, true>, (int)lds, &attr_done);
-  const int cls = MASK == 2 ? p.ctx_batches : 1;
-  const dim3 grid(cls * ((((p.lq + cls - 1) / cls) + QB - 1) / QB), p.heads, p.nseq);
-  hipLaunchKernelGGL((attn_kernel<Tag, 64, MASK, true>), grid, dim3(256), lds, st, p);
-}
-template <typename Tag, int D>
-void launch_attn(const AttnP& p, hipStream_t st) {
-  if constexpr (D == 64 && Elem<Tag>::ES == 2) {
-    if (p.qx) { if (p.mask == 1) launch_attn_qp<Tag, 1>(p, st); else launch_attn_qp<Tag, 2>(p, st); return; }
-  }
-  if constexpr (D == 64 && Elem<Tag>::ES == 2) {
-    if (p.v_rows) {                                          // row-major V (mask 0, checked by tt_attention)
-      constexpr size_t lds = 2 * (KB * D * 2 + D * KB * 2);
-      static int pipe = -1;                                  // TT_ATTN_PIPE=0: attn_kernel for every key count (A/B)
-      if (pipe < 0) { const char* e = getenv("TT_ATTN_PIPE"); pipe = e ? atoi(e) : 1; }
-      if (pipe && p.lk >= 2 * KB && p.lk % KB == 0) {        // whole key tiles: the software-pipelined kernel
-        static unsigned long long attr_done_p = 0;
-        tt_lds_opt_in((const void*)attn_pipe_kernel<Tag>, (int)lds, &attr_done_p);
-        hipLaunchKernelGGL((attn_pipe_kernel<Tag>), dim3((p.lq + QB - 1) / QB, p.heads, p.nseq), dim3(256), lds, st, p);
-        return;
-      }
-      static unsigned long long attr_done = 0;
-      tt_lds_opt_in((const void*)attn_kernel<Tag, 64, 0, false, true>, (int)lds, &attr_done);
-      hipLaunchKernelGGL((attn_kernel<Tag, 64, 0, false, true>), dim3((p.lq + QB - 1) / QB, p.heads, p.nseq), dim3(256), lds, st, p);
-      return;
-    }
-  }
-  if (p.mask == 0) launch_attn_m<Tag, D, 0>(p, st);
-  else if (p.mask == 1) launch_attn_m<Tag, D, 1>(p, st);
-  else launch_attn_m<Tag, D, 2>(p, st);
+  kv.stage(0, 0);
+  for_each_tile(ntiles, p.lk, tile);
+  attn_store_rows<Tag, D>(p, smem, o, l_run, wid, lane, seq, head, qblk, 1, 0);
 }
 
 // two 16-bit products accumulated in fp32 in one instruction (v_dot2c_f32_bf16 / v_dot2c_f32_f16): the scores of the
 // temporal kernel need neither operand unpacked
-typedef __attribute__((ext_vector_type(2))) _Float16 tt_half2;
-typedef __attribute__((ext_vector_type(2))) __bf16 tt_bf162;
 template <typename Tag> __device__ __forceinline__ float dot2_acc(unsigned a, unsigned b, float acc) { return acc; }   // f32_tag never calls it
 template <> __device__ __forceinline__ float dot2_acc<bf16_tag>(unsigned a, unsigned b, float acc) {
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(tt_bf162, a), __builtin_bit_cast(tt_bf162, b), acc, false);
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), acc, false);
 }
 template <> __device__ __forceinline__ float dot2_acc<f16_tag>(unsigned a, unsigned b, float acc) {
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(tt_half2, a), __builtin_bit_cast(tt_half2, b), acc, false);
+  return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2_t, a), __builtin_bit_cast(f16x2_t, b), acc, false);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1407,6 +1222,101 @@ __global__ __launch_bounds__(256) void tattn_mfma_kernel(const char* qkv, long l
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side: which kernel a problem takes is decided ONCE (resolve_attention / resolve_temporal, from the validated arguments and the
+// knobs), one tag x head-dimension dispatch turns the runtime dtype / head_dim into template arguments, and every kernel leaves
+// through one launch helper.
+int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+// Both A/B switches, read from the environment together, once per process, by the first call that asks for one.
+struct AttnKnobs {
+  int pipe = env_int("TT_ATTN_PIPE", 1);          // 0: attn_kernel for every key count of the v_rows route
+  int tattn_mfma = env_int("TT_TATTN_MFMA", 1);   // 0: the per-lane temporal kernel
+};
+const AttnKnobs& attn_knobs() { static const AttnKnobs k; return k; }
+
+enum class AttnRoute { FP8, QPROJ, PIPE, VROWS, SPLIT16, PLAIN };
+// (asked of arguments tt_attention has validated: fp8 / qx / v_rows imply the dtype, head dimension and mask their kernels are built for)
+AttnRoute resolve_attention(const TtAttnArgs& a) {
+  if (a.fp8) return AttnRoute::FP8;                          // attn8_kernel
+  if (a.qx) return AttnRoute::QPROJ;                         // attn_kernel<.., QP>: cross-attention with the query projection fused in
+  if (a.v_rows)                                              // row-major V; whole key tiles, at least two: the software-pipelined kernel
+    return attn_knobs().pipe && a.lk >= 2 * KB && a.lk % KB == 0 ? AttnRoute::PIPE : AttnRoute::VROWS;
+  // TT_F32 "split16": the split-product variant of the same kernel (head dimension 128 keeps the exact-fp32 MFMA: its split variant spills 1 KiB per lane)
+  if (a.dtype == TT_F32 && a.head_dim == 64 && tt_internal_f32_split()) return AttnRoute::SPLIT16;
+  return AttnRoute::PLAIN;
+}
+struct TattnRoute { bool mfma; int lpu; };                   // tattn_mfma_kernel or tattn_kernel<.., LPU lanes per unit>
+TattnRoute resolve_temporal(int dtype, int head_dim, int frames) {
+  // (one 16 x 16 MFMA tile of keys x queries per unit: tattn_mfma_kernel's own precondition)
+  return TattnRoute{attn_knobs().tattn_mfma && dtype != TT_F32 && head_dim == 64 && frames <= 16, frames <= 16 ? 16 : 32};
+}
+
+// One launch.  Kernels that use dynamic LDS opt in to its size first, once per device: the mask is this instantiation's, i.e. per kernel instance.
+template <auto Kernel, typename... Args>
+void launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  static unsigned long long attr_done = 0;
+  if (lds) tt_lds_opt_in((const void*)Kernel, (int)lds, &attr_done);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+}
+// f(Tag{}, integral_constant<int, D>{}) for the runtime dtype / head_dim (both validated by the caller)
+template <typename F>
+void for_tag_dim(int dtype, int head_dim, F&& f) {
+  auto dim = [&](auto tag) {
+    if (head_dim == 64) f(tag, std::integral_constant<int, 64>{}); else f(tag, std::integral_constant<int, 128>{});
+  };
+  if (dtype == TT_BF16) dim(bf16_tag{}); else if (dtype == TT_F16) dim(f16_tag{}); else dim(f32_tag{});
+}
+template <typename F>
+void for_mask(int mask, F&& f) {
+  if (mask == 0) f(std::integral_constant<int, 0>{}); else if (mask == 1) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 2>{});
+}
+
+// false: the route has no instance for this tag / head dimension (validation keeps such problems out)
+template <typename Tag, int D>
+bool launch_attention(AttnRoute route, const AttnP& p, hipStream_t st) {
+  constexpr int ES = Elem<Tag>::ES;
+  constexpr bool H64 = D == 64 && ES == 2;                   // QPROJ, PIPE, VROWS: head dimension 64, 16-bit storage
+  constexpr size_t ring = 2 * (KB * D * ES + D * KB * ES);   // the K / V^T ring; it doubles as the output strips
+  static_assert(ring <= 160 * 1024, "attention K/V ring exceeds the LDS");
+  // mask 2: one block per (query residue class, QB queries of that class)
+  const int cls = p.mask == 2 ? p.ctx_batches : 1;
+  const dim3 grid(cls * ((((p.lq + cls - 1) / cls) + QB - 1) / QB), p.heads, p.nseq), block(256);
+  switch (route) {
+    case AttnRoute::FP8:
+      if constexpr (ES == 2) {
+        // the K/V ring (2 x 2 x 64 x D bytes) doubles as the 4 x 32 x D*ES-byte output strips
+        constexpr size_t ring8 = 2 * (KB * D + D * KB), strips = 4 * 32 * D * ES;
+        launch<attn8_kernel<Tag, D>>(grid, block, ring8 > strips ? ring8 : strips, st, p);
+        return true;
+      }
+      break;
+    case AttnRoute::QPROJ:
+      if constexpr (H64) {
+        constexpr size_t lds = 3 * (QB * 128 + 64 * 128);    // the 3 x 24 KiB projection ring (the K / V^T ring reuses it)
+        if (p.mask == 1) launch<attn_kernel<Tag, 64, 1, true>>(grid, block, lds, st, p);
+        else launch<attn_kernel<Tag, 64, 2, true>>(grid, block, lds, st, p);
+        return true;
+      }
+      break;
+    case AttnRoute::PIPE:
+      if constexpr (H64) { launch<attn_pipe_kernel<Tag>>(grid, block, ring, st, p); return true; }
+      break;
+    case AttnRoute::VROWS:
+      if constexpr (H64) { launch<attn_kernel<Tag, 64, 0, false, true>>(grid, block, ring, st, p); return true; }
+      break;
+    case AttnRoute::SPLIT16:
+      if constexpr (ES == 4 && D == 64) {
+        for_mask(p.mask, [&](auto m) { launch<attn_kernel<Tag, D, decltype(m)::value, false, false, true>>(grid, block, ring, st, p); });
+        return true;
+      }
+      break;
+    case AttnRoute::PLAIN:
+      for_mask(p.mask, [&](auto m) { launch<attn_kernel<Tag, D, decltype(m)::value>>(grid, block, ring, st, p); });
+      return true;
+  }
+  return false;
+}
+
 template <typename Tag, int D, int LPU>
 void launch_tattn(const void* qkv, long ldqkv, void* out, long ldo, int batch, int frames, int hw, int heads, hipStream_t st) {
   constexpr int UPB = 128 / LPU;
@@ -1417,23 +1327,17 @@ void launch_tattn(const void* qkv, long ldqkv, void* out, long ldo, int batch, i
 #endif
   constexpr size_t lds = (REUSE ? 1 : 2) * UPB * (LPU * (D * Elem<Tag>::ES + 16) + 64);
   static_assert(lds <= 160 * 1024, "temporal attention staging exceeds the LDS");
-  static unsigned long long attr_done = 0;
-  tt_lds_opt_in((const void*)tattn_kernel<Tag, D, LPU>, (int)lds, &attr_done);
   const long units = (long)batch * hw * heads;
-  const float sl2 = 1.4426950408889634f / sqrtf((float)D);
-  if constexpr (D == 64 && Elem<Tag>::ES == 2 && LPU == 16) {
-    static int mfma = -1;                                    // TT_TATTN_MFMA=0: the per-lane kernel (A/B)
-    if (mfma < 0) { const char* e = getenv("TT_TATTN_MFMA"); mfma = e ? atoi(e) : 1; }
-    if (mfma && frames <= 16) {                              // (one 16 x 16 MFMA tile of keys x queries per unit: the kernel's own precondition)
-      long blocks = (units + 3) / 4;
-      if (blocks > 256 * 8) blocks = 256 * 8;                // 8 blocks of 4 waves per CU, grid-stride over the units
-      hipLaunchKernelGGL((tattn_mfma_kernel<Tag>), dim3((unsigned)blocks), dim3(256), 0, st, (const char*)qkv, ldqkv, (char*)out, ldo, batch, frames, hw,
-                         heads, sl2, units);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((tattn_kernel<Tag, D, LPU>), dim3((unsigned)((units + UPB - 1) / UPB)), dim3(128), lds, st,
-                     (const char*)qkv, ldqkv, (char*)out, ldo, batch, frames, hw, heads, sl2);
+  launch<tattn_kernel<Tag, D, LPU>>(dim3((unsigned)((units + UPB - 1) / UPB)), dim3(128), lds, st, (const char*)qkv, ldqkv, (char*)out, ldo, batch,
+                                    frames, hw, heads, 1.4426950408889634f / sqrtf((float)D));
+}
+template <typename Tag>
+void launch_tattn_mfma(const void* qkv, long ldqkv, void* out, long ldo, int batch, int frames, int hw, int heads, hipStream_t st) {
+  const long units = (long)batch * hw * heads;
+  long blocks = (units + 3) / 4;
+  if (blocks > 256 * 8) blocks = 256 * 8;                    // 8 blocks of 4 waves per CU, grid-stride over the units
+  launch<tattn_mfma_kernel<Tag>>(dim3((unsigned)blocks), dim3(256), 0, st, (const char*)qkv, ldqkv, (char*)out, ldo, batch, frames, hw, heads,
+                                 1.4426950408889634f / sqrtf(64.0f), units);
 }
 
 }  // namespace
@@ -1494,16 +1398,10 @@ extern "C" int tt_attention(const TtAttnArgs* a, tt_stream_t stream) {
     if (xb >= (1L << 31) || wb >= (1L << 31)) TT_FAIL(TT_EUNSUPPORTED, "tt_attention: x or Wq larger than 2 GiB");
     p.qx_bytes = (unsigned)xb; p.wq_bytes = (unsigned)wb;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (a->fp8) {
-    if (a->dtype == TT_BF16) { if (a->head_dim == 64) launch_attn8<bf16_tag, 64>(p, st); else launch_attn8<bf16_tag, 128>(p, st); }
-    else { if (a->head_dim == 64) launch_attn8<f16_tag, 64>(p, st); else launch_attn8<f16_tag, 128>(p, st); }
-    TT_CHECK_LAUNCH("tt_attention");
-    return TT_OK;
-  }
-  if (a->dtype == TT_BF16) { if (a->head_dim == 64) launch_attn<bf16_tag, 64>(p, st); else launch_attn<bf16_tag, 128>(p, st); }
-  else if (a->dtype == TT_F16) { if (a->head_dim == 64) launch_attn<f16_tag, 64>(p, st); else launch_attn<f16_tag, 128>(p, st); }
-  else { if (a->head_dim == 64) launch_attn<f32_tag, 64>(p, st); else launch_attn<f32_tag, 128>(p, st); }
+  const AttnRoute route = resolve_attention(*a);
+  bool launched = false;
+  for_tag_dim(a->dtype, a->head_dim, [&](auto tag, auto dim) { launched = launch_attention<decltype(tag), decltype(dim)::value>(route, p, (hipStream_t)stream); });
+  if (!launched) TT_FAIL(TT_EUNSUPPORTED, "tt_attention: no kernel instance for this route, dtype and head_dim");
   TT_CHECK_LAUNCH("tt_attention");
   return TT_OK;
 }
@@ -1517,18 +1415,16 @@ extern "C" int tt_temporal_attention(const void* qkv, int64_t ldqkv, void* out, 
   if (((ldqkv * (dtype == TT_F32 ? 4 : 2)) & 15) || ((ldo * (dtype == TT_F32 ? 4 : 2)) & 15)) TT_FAIL(TT_EINVAL, "tt_temporal_attention: strides");
   if ((((size_t)qkv | (size_t)out) & 15)) TT_FAIL(TT_EINVAL, "tt_temporal_attention: qkv and out must start on 16-byte boundaries");
   hipStream_t st = (hipStream_t)stream;
-#define TT_TA(TAG, D, L) launch_tattn<TAG, D, L>(qkv, ldqkv, out, ldo, batch, frames, hw, heads, st)
-  if (dtype == TT_BF16) {
-    if (head_dim == 64) { if (frames <= 16) TT_TA(bf16_tag, 64, 16); else TT_TA(bf16_tag, 64, 32); }
-    else { if (frames <= 16) TT_TA(bf16_tag, 128, 16); else TT_TA(bf16_tag, 128, 32); }
-  } else if (dtype == TT_F16) {
-    if (head_dim == 64) { if (frames <= 16) TT_TA(f16_tag, 64, 16); else TT_TA(f16_tag, 64, 32); }
-    else { if (frames <= 16) TT_TA(f16_tag, 128, 16); else TT_TA(f16_tag, 128, 32); }
-  } else {
-    if (head_dim == 64) { if (frames <= 16) TT_TA(f32_tag, 64, 16); else TT_TA(f32_tag, 64, 32); }
-    else { if (frames <= 16) TT_TA(f32_tag, 128, 16); else TT_TA(f32_tag, 128, 32); }
-  }
-#undef TT_TA
+  const TattnRoute route = resolve_temporal(dtype, head_dim, frames);
+  for_tag_dim(dtype, head_dim, [&](auto tag, auto dim) {
+    typedef decltype(tag) Tag;
+    constexpr int D = decltype(dim)::value;
+    if constexpr (D == 64 && Elem<Tag>::ES == 2) {
+      if (route.mfma) { launch_tattn_mfma<Tag>(qkv, ldqkv, out, ldo, batch, frames, hw, heads, st); return; }
+    }
+    if (route.lpu == 16) launch_tattn<Tag, D, 16>(qkv, ldqkv, out, ldo, batch, frames, hw, heads, st);
+    else launch_tattn<Tag, D, 32>(qkv, ldqkv, out, ldo, batch, frames, hw, heads, st);
+  });
   TT_CHECK_LAUNCH("tt_temporal_attention");
   return TT_OK;
 }

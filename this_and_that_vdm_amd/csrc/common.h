@@ -287,6 +287,38 @@ template <int N> __device__ __forceinline__ void lds_wait() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// ---- running sum and sum of squares of one 16-byte MFMA operand chunk (fused LayerNorm statistics).  16-bit storage: two
+// packed dot products per dword (v_dot2_f32_*: x . (1,1) and x . x, accumulated in fp32) -- the operand stays packed.
+// (tt_gemm's ln_fold and the fused query projection of tt_attention.)
+template <typename Tag> __device__ __forceinline__ void ln_stat(const raw_u32x4_t& f, float& s, float& q);
+template <> __device__ __forceinline__ void ln_stat<bf16_tag>(const raw_u32x4_t& f, float& s, float& q) {
+  // (hipcc / ROCm 7.2 miscompiles __builtin_bit_cast(.., f[d]) on an ext-vector subscript inside a loop: every
+  // iteration reads element 0 -- tools/dot2_test.hip.  Copy the dwords to scalars first.)
+  const bf16x2_t one = __builtin_bit_cast(bf16x2_t, 0x3F803F80u);
+  const unsigned w[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const bf16x2_t x = __builtin_bit_cast(bf16x2_t, w[d]);
+    s = __builtin_amdgcn_fdot2_f32_bf16(x, one, s, false);
+    q = __builtin_amdgcn_fdot2_f32_bf16(x, x, q, false);
+  }
+}
+template <> __device__ __forceinline__ void ln_stat<f16_tag>(const raw_u32x4_t& f, float& s, float& q) {
+  const f16x2_t one = __builtin_bit_cast(f16x2_t, 0x3C003C00u);
+  const unsigned w[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const f16x2_t x = __builtin_bit_cast(f16x2_t, w[d]);
+    s = __builtin_amdgcn_fdot2(x, one, s, false);
+    q = __builtin_amdgcn_fdot2(x, x, q, false);
+  }
+}
+template <> __device__ __forceinline__ void ln_stat<f32_tag>(const raw_u32x4_t& f, float& s, float& q) {
+  const unsigned w[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+  for (int d = 0; d < 4; ++d) { const float x = __uint_as_float(w[d]); s += x; q = fmaf(x, x, q); }
+}
+
 // ---------------------------------------------------------------- kernel-argument warm-up
 // hipcc loads the kernel arguments where they are first needed: a kernel with a few hundred bytes of them meets 3-5 SERIALISED
 // scalar-cache misses (s_load ... s_waitcnt lgkmcnt(0), ~0.3-0.5 us each when the line comes from L2 / the fabric) before its first

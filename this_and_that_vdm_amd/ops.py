@@ -323,7 +323,7 @@ def attention(q, k, vt, out, *, nseq, lq, heads, head_dim, mask, lk, k_seq_strid
         tag = _TAG[a.dtype]
         if fp8:
             kname = f"attn8_kernel<{tag}, {head_dim}>"
-        elif v_rows and lk >= 128 and lk % 64 == 0 and os.environ.get("TT_ATTN_PIPE", "1") != "0":     # (launch_attn in attention.hip)
+        elif v_rows and lk >= 128 and lk % 64 == 0 and os.environ.get("TT_ATTN_PIPE", "1") != "0":     # (resolve_attention in attention.hip)
             kname = f"attn_pipe_kernel<{tag}>"
         else:
             kname = f"attn_kernel<{tag}, {head_dim}, {mask}{', true' if qx is not None else ''}{', false, true' if v_rows else ''}>"
