@@ -383,6 +383,65 @@ int tt_add_rowvec(const void* x, int64_t ldx, int32_t rows, int32_t c, const flo
 int tt_softmax_rows(const float* x, int64_t ldx, int32_t rows, int32_t cols, void* y, int64_t ldy, int32_t cols_pad,
                     int32_t dtype, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The CLIP encoders behind encode_clip (svd/pipeline_stable_video_diffusion_controlnet.py:130-185): the image encoder
+ * CLIPVisionModelWithProjection (loaded at test_code/inference.py:325; ViT-H/14: width 1280, 16 heads of 80, 257 tokens) and the
+ * text encoder CLIPTextModel (test_code/inference.py:348; SD-2.1: width 1024, 16 heads of 64, 77 tokens, causal), chosen per
+ * checkpoint by train_code/train_svd.py:214-231.  Their Linear layers and LayerNorms are tt_gemm / tt_layernorm; the entry points
+ * below are what those do not cover.  Additive: the ABI version is unchanged.
+ *
+ * tt_encoder_attention: self-attention  softmax(Q K^T / sqrt(d) [+ causal]) V  per (sequence, head) with lq == lk == l, any l >= 1,
+ * head_dim 64 or 80 (CLIPAttention; transformers modeling_clip.py, reached from encode_clip :130-185).
+ *   q   [nseq * l, ldq]  (+ head * d): query r of sequence s is row s * l + r
+ *   k   [rows, ldk]      (+ head * d): key j of sequence s is row s * k_seq_stride + j
+ *   v   TT_BF16 / TT_F16: V itself, [rows, ldv] (+ head * d), rows addressed like k with v_seq_stride -- q, k and v are then the three
+ *                         column slices of one fused [nseq * l, 3 C] projection output; the kernel transposes on the way out of LDS.
+ *       TT_F32:           V TRANSPOSED, [heads * d, ldv]: key j of sequence s is column s * v_seq_stride + j (written by tt_gemm with
+ *                         out_col_hw = l, out_col_hwp = v_seq_stride, a multiple of 4; fp32 storage has no transposing LDS read).
+ *   out [nseq * l, ldo]  (+ head * d)
+ * causal != 0: key j > query r scores -inf (CLIPTextModel's mask); key tiles wholly past a block's last query are skipped.
+ * Keys >= l of a sequence (a stride larger than l) never contribute: their probability is an exact zero (finite values assumed).
+ * head_dim 80 runs as a head padded to 128 columns in LDS: chunks beyond the head's 80 elements read as zeros through the buffer
+ * descriptor (never from the next head), the scale is 1/sqrt(80), 80 columns are stored.  TT_F32 always multiplies with the
+ * exact-fp32 MFMA (tt_gemm_set_f32_split does not change this kernel).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct TtEncAttnArgs {
+  const void* q; int64_t ldq;
+  const void* k; int64_t ldk;
+  const void* v; int64_t ldv;
+  void* out; int64_t ldo;
+  int32_t nseq, l, heads, head_dim;    /* head_dim 64 or 80 */
+  int32_t causal;                      /* 0 / 1 */
+  int32_t k_seq_stride, v_seq_stride;  /* rows of k (and of v, 16-bit) / columns of v (TT_F32) per sequence, >= l */
+  int32_t dtype;
+} TtEncAttnArgs;
+int tt_encoder_attention(const TtEncAttnArgs* args, tt_stream_t stream);
+
+/* y[r][0:c] = act(x[r][0:c]) over `dtype` rows with strides (c, ldx, ldy multiples of 8); y may be x (in place).
+ *   act 0  exact-erf GELU            (hidden_act "gelu": CLIP ViT-H and SD-2.1's text encoder; CLIPMLP between fc1 and fc2)
+ *   act 1  x * sigmoid(1.702 x)      ("quick_gelu": OpenAI CLIP checkpoints)
+ * encode_clip, svd/pipeline_stable_video_diffusion_controlnet.py:130-185. */
+int tt_act_rows(const void* x, int64_t ldx, int32_t rows, int32_t c, int32_t act, void* y, int64_t ldy, int32_t dtype,
+                tt_stream_t stream);
+
+/* NCHW image -> patch token rows for CLIPVisionEmbeddings.patch_embedding (Conv2d(3, C, p, stride p, bias=False); the
+ * CLIPVisionModelWithProjection of test_code/inference.py:325):  dst[(n, py, px)][k] = src[n][c][py*p + ky][px*p + kx],
+ * k = (c, ky, kx) as patch_embedding.weight.flatten(1) orders it, columns ch*p*p .. kpad zero-filled (kpad a multiple of 8,
+ * >= ch*p*p, <= ld_dst).  The conv is then one mode-0 tt_gemm against the weight packed to kpad columns.
+ * src fp32 (src_f32 != 0) or `dtype`, contiguous [nimg, ch, h, w], h and w multiples of p. */
+int tt_patch_tokens(const void* src, int32_t src_f32, int32_t nimg, int32_t ch, int32_t h, int32_t w, int32_t p, void* dst,
+                    int64_t ld_dst, int32_t kpad, int32_t dtype, tt_stream_t stream);
+
+/* The embedding rows of the two encoders (CLIPTextEmbeddings / CLIPVisionEmbeddings; encode_clip :130-185), `dtype` tables,
+ * c a multiple of 8, out [rows, ldo]:
+ *   mode 0 (text)    out[r] = table[ids[r]] + pos[r % l]                      ids int64 [rows], each in [0, table_rows)
+ *                    (an id outside the table leaves a row of zeros + pos: no out-of-range read)
+ *   mode 1 (vision)  out[r] = (r % l == 0 ? cls : patches[(r / l) * (l - 1) + r % l - 1]) + pos[r % l]
+ *                    table = patch rows [rows / l * (l - 1), ld_table], cls = the class embedding [c], ids unused. */
+int tt_embed_rows(int32_t mode, const int64_t* ids, const void* table, int64_t ld_table, int32_t table_rows, const void* cls,
+                  const void* pos, int64_t ld_pos, int32_t rows, int32_t l, int32_t c, void* out, int64_t ldo, int32_t dtype,
+                  tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,15 @@ class TtConvArgs(C.Structure):
     ]
 
 
+class TtEncAttnArgs(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("ldq", C.c_int64), ("k", C.c_void_p), ("ldk", C.c_int64),
+        ("v", C.c_void_p), ("ldv", C.c_int64), ("out", C.c_void_p), ("ldo", C.c_int64),
+        ("nseq", C.c_int32), ("l", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
+        ("causal", C.c_int32), ("k_seq_stride", C.c_int32), ("v_seq_stride", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
 _i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
 # name -> (restype, argtypes): every symbol include/ttvdm.h declares
@@ -104,6 +113,11 @@ SIGNATURES = {
     "tt_add_scaled": (C.c_int, [_vp, _vp, _f32, _vp, _i64, _i32, _vp]),
     "tt_add_rowvec": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _vp]),
     "tt_softmax_rows": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
+    # the CLIP encoders (additive; the ABI version is unchanged)
+    "tt_encoder_attention": (C.c_int, [C.POINTER(TtEncAttnArgs), _vp]),
+    "tt_act_rows": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
+    "tt_patch_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
+    "tt_embed_rows": (C.c_int, [_i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
 }
 
 _lib = None

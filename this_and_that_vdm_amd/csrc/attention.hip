@@ -103,12 +103,16 @@ __device__ __forceinline__ void vr_read_addrs(int lane, unsigned lds_base, unsig
 // position is a scalar offset, out-of-range rows/columns land beyond num_records and read as zeros (same scheme as gemm.hip).
 // A stage of the ring is the K tile ([64 keys][D], 16-byte chunks swizzled per row) followed by the V^T tile ([D][64 keys]; VR: V itself,
 // rows = keys like the K tile).
-template <int EB, int D, bool VR>
+// DH < D (tt_encoder_attention, head dimension 80 staged as 128 columns): the head holds DH elements in memory; the chunks / V^T rows of
+// the tile beyond them are requested past num_records, i.e. land as zeros -- never as the next head's data.
+template <int EB, int D, bool VR, int DH = D>
 struct KvStage {
   static constexpr int EPC = 16 / EB;                                   // elements per 16-byte chunk
-  static constexpr int KCPR = D / EPC, VCPR = KB / EPC;                 // 16-B chunks per K-tile row (row = key, D elements) / per V^T-tile row (row = d, 64 keys)
+  static constexpr int KCPR = D / EPC, VCPR = VR ? D / EPC : KB / EPC;  // 16-B chunks per K-tile row (row = key, D elements) / per V^T-tile row (row = d, 64 keys; VR: row = key)
+  static_assert(DH <= D && DH % EPC == 0, "whole chunks of the head");
   static constexpr int K_BYTES = KB * D * EB, V_BYTES = D * KB * EB, STAGE = K_BYTES + V_BYTES;
-  static constexpr int KPT = (KB * KCPR) / 256, VPT = (D * VCPR) / 256;  // chunks per thread
+  static constexpr int KPT = (KB * KCPR) / 256, VPT = ((VR ? KB : D) * VCPR) / 256;  // chunks per thread (both tiles hold KB * D elements)
+  static_assert(KPT * 4096 == K_BYTES && VPT * 4096 == V_BYTES, "the staged pieces cover each tile exactly");
   static constexpr int INV = (int)0x80000000;
   static_assert(KPT >= 1 && VPT >= 1, "tile smaller than the block");
   const AttnP& p;
@@ -127,7 +131,8 @@ struct KvStage {
       const int slot = i * 256 + tid;
       const int r = slot / KCPR, c = (slot % KCPR) ^ tile_swz<KCPR>(r);
       kr[i] = r;
-      kvo[i] = (int)((((long)kbase + r) * p.ldk + head * D + c * EPC) * EB);
+      kvo[i] = (int)((((long)kbase + r) * p.ldk + head * DH + c * EPC) * EB);
+      if (DH != D && c * EPC >= DH) kvo[i] = INV;
     }
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
@@ -135,10 +140,12 @@ struct KvStage {
       const int r = slot / VCPR, c = (slot % VCPR) ^ tile_swz<VCPR>(r);
       if constexpr (VR) {                                      // rows = keys, like the K tile
         vc[i] = r;
-        vvo[i] = (int)((((long)vbase + r) * p.ldvt + head * D + c * EPC) * EB);
+        vvo[i] = (int)((((long)vbase + r) * p.ldvt + head * DH + c * EPC) * EB);
+        if (DH != D && c * EPC >= DH) vvo[i] = INV;
       } else {
         vc[i] = c * EPC;
-        vvo[i] = (int)(((long)(head * D + r) * p.ldvt + vbase + c * EPC) * EB);
+        vvo[i] = (int)(((long)(head * DH + r) * p.ldvt + vbase + c * EPC) * EB);
+        if (DH != D && r >= DH) vvo[i] = INV;
       }
     }
   }
@@ -221,9 +228,11 @@ __device__ __forceinline__ void softmax_rescale(const f32x16_t (&s)[2], float sc
 // 32 rows; instead the wave's 32 x D outputs go through a private LDS strip (the K/V ring is free once every wave has passed the
 // barrier in here) and leave as full rows: 8 (D = 64, 16-bit) or more lanes cover one row's D*ES contiguous bytes.  Block qblk owns
 // query rows (qblk * QB + i) * qstride + qcls (mask 2: one residue class; everything else 1, 0).
-template <typename Tag, int D>
-__device__ __forceinline__ void attn_store_rows(const AttnP& p, char* smem, const f32x16_t (&o)[D / 32], float l_run, int wid, int lane,
+// DO < D (tt_encoder_attention's padded head): the strips are D wide, the NO accumulators cover the head's DO columns, DO columns are stored.
+template <typename Tag, int D, int DO = D, int NO = D / 32>
+__device__ __forceinline__ void attn_store_rows(const AttnP& p, char* smem, const f32x16_t (&o)[NO], float l_run, int wid, int lane,
                                                 int seq, int head, int qblk, int qstride, int qcls) {
+  static_assert(NO * 32 >= DO && NO * 32 <= D && (DO * Elem<Tag>::ES) % 16 == 0, "accumulators cover the stored columns");
   typedef typename Elem<Tag>::quad_t quad_t;
   constexpr int ES = Elem<Tag>::ES;
   const int l31 = lane & 31, hi = lane >> 5;
@@ -233,7 +242,7 @@ __device__ __forceinline__ void attn_store_rows(const AttnP& p, char* smem, cons
   constexpr int ROWB_O = D * ES, CPR_O = ROWB_O / 16;  // output row bytes per head, 16-byte chunks per row
   char* strip = smem + wid * (32 * ROWB_O);
 #pragma unroll
-  for (int db = 0; db < D / 32; ++db)
+  for (int db = 0; db < NO; ++db)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int byte = (db * 32 + 8 * g + 4 * hi) * ES;   // this lane's 4 consecutive d of query row l31
@@ -247,7 +256,7 @@ __device__ __forceinline__ void attn_store_rows(const AttnP& p, char* smem, cons
     const int r = pass * RPP + orow;
     const uint4 v = *(const uint4*)(strip + r * ROWB_O + ((oc ^ (r & (CPR_O - 1))) << 4));
     const int qr = (qblk * QB + wid * 32 + r) * qstride + qcls;
-    if (qr < p.lq) *(uint4*)(p.out + (((long)seq * p.lq + qr) * p.ldo + head * D) * ES + oc * 16) = v;
+    if (qr < p.lq && (DO == D || oc * 16 < DO * ES)) *(uint4*)(p.out + (((long)seq * p.lq + qr) * p.ldo + head * DO) * ES + oc * 16) = v;
   }
 }
 
@@ -980,6 +989,158 @@ __global__ __launch_bounds__(256, 2) void attn8_kernel(const AttnP p) {
   attn_store_rows<Tag, D>(p, smem, o, l_run, wid, lane, seq, head, qblk, 1, 0);
 }
 
+// ---------------------------------------------------------------------------------------------
+// tt_encoder_attention (the CLIP image / text encoders): self-attention over l = lq = lk tokens per sequence, head dimension DH = 64 or 80,
+// optionally causal.  Same lane layout and the same pieces as attn_kernel (load_q_frags, KvStage, for_each_tile / mask_ragged, the lazy softmax
+// reference with softmax_rescale, attn_store_rows, xcd_remap3); the tile is written plainly -- one batch of operand reads, one wait, its MFMAs --
+// because the problem is 16-48 workgroups of at most five key tiles per launch: launch-bound, nothing to pipeline.
+//   16-bit storage: V arrives row-major ([keys, ldv], a column slice of the fused Q | K | V projection) and is transposed on the way out of
+//                   LDS by ds_read_b64_tr_b16 (the VR layout of attn_kernel, addresses computed per read instead of folded into immediates);
+//   fp32 storage:   V arrives transposed ([heads * DH, ldv], tt_gemm out_col_hw) and both products run on the exact-fp32 MFMA.
+// DH = 80 is a head PADDED to D = 128 staged columns: a K-tile row is 128 elements of which chunks >= 80 / EPC are requested past the buffer
+// descriptor's num_records (zeros, never the next head) and are not even multiplied -- QK^T takes the DH * ES / 32 chunk pairs the head has
+// (5 K-steps of 32x32x16 in 16-bit); V^T rows >= 80 of the head are zeros the same way, O^T is three 32-row blocks (rows 80..95 of the third
+// are the waste: 1/6 of the PV MFMAs, and 3/8 of the ring's LDS), 80 columns are stored.  Scale 1/sqrt(80) (the host's scale_log2e).
+// CAUSAL: lane = one query, key j > query scores -inf; a block stops at the tile that holds its LAST query (block-uniform: the barriers are
+// per block), key 0 is visible to every query, so the first tile always gives every row a finite reference.
+template <typename Tag, int DH, bool CAUSAL>
+__global__ __launch_bounds__(256, 1) void enc_attn_kernel(const AttnP p) {
+  kernarg_touch<sizeof(AttnP)>();
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int ES = Elem<Tag>::ES, EPC = Elem<Tag>::EPC;
+  constexpr bool VR = ES == 2;
+  constexpr int D = DH == 64 ? 64 : 128;      // staged columns per head
+  static_assert(DH == 64 || DH == 80, "head dimension 64 or 80");
+  typedef KvStage<ES, D, VR, DH> Stage;
+  constexpr int KCPR = Stage::KCPR, VCPR = Stage::VCPR, K_BYTES = Stage::K_BYTES, STAGE = Stage::STAGE;
+  constexpr int DS = DH * ES / 32;            // chunk pairs (one chunk per lane half) of a K row that hold the head: the K-steps of QK^T
+  constexpr int NO = (DH + 31) / 32;          // 32-row blocks of O^T
+  constexpr int PH = 16 / EPC;                // P chunks per lane per 32-key block
+  constexpr int KBATCH = ES == 4 ? DS / 2 : DS;
+  static_assert(DS % KBATCH == 0, "whole batches of K fragments");
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, hi = lane >> 5;
+  const Bid3 blk = xcd_remap3();
+  const int head = blk.y, seq = blk.z, qblk = blk.x;
+  const int kbase = seq * p.k_seq_stride, vbase = seq * p.v_seq_stride;
+  const int qlast = min(qblk * QB + QB - 1, p.lq - 1);                         // the block's last query
+  const int ntiles = CAUSAL ? qlast / KB + 1 : (p.lk + KB - 1) / KB;           // causal: tiles wholly past it are skipped
+  const int lk_loop = min(p.lk, ntiles * KB);                                  // ragged only if the loop reaches the sequence's last tile
+
+  const int qrow = qblk * QB + wid * 32 + l31;
+  const bool qok = qrow < p.lq;
+  uint4 qf[DS];
+  load_q_frags<ES, DH>(p, seq, head, qrow, qok, hi, qf);
+  const Stage kv(p, smem, tid, wid, head, kbase, vbase);
+
+  f32x16_t o[NO];
+#pragma unroll
+  for (int i = 0; i < NO; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
+  float m_run = -1e30f, l_run = 0.f;
+  const int pi = key_perm(l31);
+  const unsigned lds_base = lds_addr(smem);
+  const int gi = lane & 15, gg = lane >> 4;   // VR: the 16-lane groups of the transposing read
+
+  auto tile = [&](int t, auto buf_tag, auto mask_tag) {
+    constexpr int BUF = decltype(buf_tag)::value;
+    constexpr bool MASKED = decltype(mask_tag)::value;
+    constexpr int KOFF = BUF * STAGE, VOFF = BUF * STAGE + K_BYTES;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's share of tile t has landed ...
+    __syncthreads();                                           // ... and everybody's; the other buffer is free
+    if (t + 1 < ntiles) kv.stage(BUF ^ 1, t + 1);
+    f32x16_t s[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
+    // ---- S^T = K Q^T over the head's DS chunk pairs
+#pragma unroll
+    for (int b = 0; b < DS / KBATCH; ++b) {
+      raw_u32x4_t kf[2][KBATCH];
+#pragma unroll
+      for (int i = 0; i < KBATCH; ++i)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) kf[kb][i] = lds_read16_raw_off<KOFF>(lds_base + tile_off<KCPR>(kb * 32 + pi, (b * KBATCH + i) * 2 + hi));
+      lds_wait<0>();
+#pragma unroll
+      for (int i = 0; i < KBATCH; ++i)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)                         // alternate the two accumulators
+          s[kb] = Cvt<Tag>::mfma32(make_uint4(kf[kb][i].x, kf[kb][i].y, kf[kb][i].z, kf[kb][i].w), qf[b * KBATCH + i], s[kb]);
+      __builtin_amdgcn_sched_barrier(0);                       // the MFMAs read the batch before it is re-filled
+    }
+    // ---- masks (lane: query qrow, keys t*KB + kb*32 + hi*16 + r) + online softmax, lazy reference as in attn_kernel
+    if constexpr (MASKED) mask_ragged(s, t, hi, p.lk);
+    if constexpr (CAUSAL) {
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (t * KB + kb * 32 + hi * 16 + r > qrow) s[kb][r] = -INFINITY;
+    }
+    constexpr float PSUM_OK = 16384.0f;
+    float psum = 0.f;
+    uint4 pf[2][PH];
+    auto exponentiate = [&](float m_ref) {
+      psum = 0.f;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int h = 0; h < PH; ++h) {
+          float e[EPC];
+#pragma unroll
+          for (int r = 0; r < EPC; ++r) { e[r] = fast_exp2(fmaf(s[kb][h * EPC + r], p.scale_log2e, -m_ref)); psum += e[r]; }
+          pf[kb][h] = pack_chunk<Tag>(e);
+        }
+    };
+    exponentiate(m_run);
+    if (__any(!(psum <= PSUM_OK))) {                            // first tile (m_run = -1e30 gives inf), or scores that outgrew the reference
+      softmax_rescale<NO>(s, p.scale_log2e, m_run, l_run, o);
+      exponentiate(m_run);
+    }
+    l_run += psum;
+    // ---- O^T += V^T P^T, one 32-row block of O^T at a time: k-slot (hi, e) of read k = kb*PH + h is key kb*32 + 16*hi + EPC*h + e
+#pragma unroll
+    for (int db = 0; db < NO; ++db) {
+      if constexpr (VR) {
+        // fragment k = two transposing reads of [4 keys][16 d]: lane gi of group gg supplies the 8-byte run (key + (gi >> 2), d 4 (gi & 3) ..)
+        // of d block (db, gg & 1) and receives d = 16 (gg & 1) + gi of the four keys
+        raw_u32x2_t g[2 * PH][2];
+#pragma unroll
+        for (int k = 0; k < 2 * PH; ++k)
+#pragma unroll
+          for (int half = 0; half < 2; ++half) {
+            const int row = (k / PH) * 32 + 16 * (gg >> 1) + 8 * (k % PH) + 4 * half + (gi >> 2);
+            g[k][half] = lds_read8_tr_off<VOFF>(lds_base + tile_off<VCPR>(row, db * 4 + (gg & 1) * 2 + ((gi & 3) >> 1)) + (gi & 1) * 8);
+          }
+        lds_wait<0>();
+#pragma unroll
+        for (int k = 0; k < 2 * PH; ++k)
+          o[db] = Cvt<Tag>::mfma32(make_uint4(g[k][0].x, g[k][0].y, g[k][1].x, g[k][1].y), pf[k / PH][k % PH], o[db]);
+      } else {
+        raw_u32x4_t f[2 * PH];
+#pragma unroll
+        for (int k = 0; k < 2 * PH; ++k)
+          f[k] = lds_read16_raw_off<VOFF>(lds_base + tile_off<VCPR>(db * 32 + l31, (k / PH) * (32 / EPC) + hi * PH + k % PH));
+        lds_wait<0>();
+#pragma unroll
+        for (int k = 0; k < 2 * PH; ++k)
+          o[db] = Cvt<Tag>::mfma32(make_uint4(f[k].x, f[k].y, f[k].z, f[k].w), pf[k / PH][k % PH], o[db]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  kv.stage(0, 0);
+  for_each_tile(ntiles, lk_loop, tile);
+  static_assert(4 * 32 * D * ES <= 2 * STAGE, "output strips do not fit the K/V ring");
+  attn_store_rows<Tag, D, DH, NO>(p, smem, o, l_run, wid, lane, seq, head, qblk, 1, 0);
+}
+
 // two 16-bit products accumulated in fp32 in one instruction (v_dot2c_f32_bf16 / v_dot2c_f32_f16): the scores of the
 // temporal kernel need neither operand unpacked
 template <typename Tag> __device__ __forceinline__ float dot2_acc(unsigned a, unsigned b, float acc) { return acc; }   // f32_tag never calls it
@@ -1426,5 +1587,55 @@ extern "C" int tt_temporal_attention(const void* qkv, int64_t ldqkv, void* out, 
     else launch_tattn<Tag, D, 32>(qkv, ldqkv, out, ldo, batch, frames, hw, heads, st);
   });
   TT_CHECK_LAUNCH("tt_temporal_attention");
+  return TT_OK;
+}
+
+// tt_encoder_attention: validation first (nothing is launched on a refused problem), then one kernel instance per (tag, head_dim, causal).
+extern "C" int tt_encoder_attention(const TtEncAttnArgs* a, tt_stream_t stream) {
+  if (!a || !a->q || !a->k || !a->v || !a->out) TT_FAIL(TT_EINVAL, "tt_encoder_attention: null operand");
+  if (a->nseq <= 0 || a->l <= 0 || a->heads <= 0) TT_FAIL(TT_EINVAL, "tt_encoder_attention: empty problem");
+  if (a->head_dim != 64 && a->head_dim != 80) TT_FAIL(TT_EUNSUPPORTED, "tt_encoder_attention: head_dim %d (64 or 80)", a->head_dim);
+  if (a->dtype != TT_BF16 && a->dtype != TT_F16 && a->dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_encoder_attention: bad dtype");
+  if (a->causal != 0 && a->causal != 1) TT_FAIL(TT_EINVAL, "tt_encoder_attention: causal %d (0 or 1)", a->causal);
+  const int es = a->dtype == TT_F32 ? 4 : 2;
+  const bool vrows = es == 2;                                  // 16-bit: v is V itself; fp32: v is V^T
+  if (((a->ldq * es) & 15) || ((a->ldk * es) & 15) || ((a->ldv * es) & 15) || ((a->ldo * es) & 15) || (!vrows && (((long)a->v_seq_stride * es) & 15)))
+    TT_FAIL(TT_EINVAL, "tt_encoder_attention: strides must keep 16-byte chunks aligned");
+  if ((((size_t)a->q | (size_t)a->k | (size_t)a->v | (size_t)a->out) & 15))
+    TT_FAIL(TT_EINVAL, "tt_encoder_attention: q, k, v and out must start on 16-byte boundaries");
+  if (a->l > a->k_seq_stride || a->l > a->v_seq_stride) TT_FAIL(TT_EINVAL, "tt_encoder_attention: l exceeds sequence stride");
+  const long c = (long)a->heads * a->head_dim;
+  AttnP p = {};
+  p.q = (const char*)a->q; p.ldq = a->ldq; p.k = (const char*)a->k; p.ldk = a->ldk;
+  p.vt = (const char*)a->v; p.ldvt = a->ldv; p.out = (char*)a->out; p.ldo = a->ldo;
+  p.nseq = a->nseq; p.lq = a->l; p.lk = a->l; p.heads = a->heads; p.mask = 0;
+  p.k_seq_stride = a->k_seq_stride; p.v_seq_stride = a->v_seq_stride; p.frames = 1; p.ctx_batches = 1; p.batch0 = 0;
+  p.v_rows = vrows ? 1 : 0;
+  // rows of k (and of a row-major v) / columns of v^T that exist: the last sequence ends with its l-th key (fp32: with the 16-byte chunk that holds it)
+  const long k_rows = (long)(a->nseq - 1) * a->k_seq_stride + a->l;
+  const long v_ext = (long)(a->nseq - 1) * a->v_seq_stride + (vrows ? a->l : (a->l + 3) / 4 * 4);
+  if (a->ldq < c || a->ldk < c || a->ldo < c || (vrows ? a->ldv < c : a->ldv < v_ext))
+    TT_FAIL(TT_EINVAL, "tt_encoder_attention: row stride smaller than the row (heads * head_dim; fp32 v^T: the key columns)");
+  const long kb = ((k_rows - 1) * a->ldk + c) * es;
+  const long vb = vrows ? ((v_ext - 1) * a->ldv + c) * es : ((c - 1) * a->ldv + v_ext) * es;
+  if (k_rows >= (1L << 31) || v_ext >= (1L << 31) || kb >= (1L << 31) || vb >= (1L << 31)) TT_FAIL(TT_EUNSUPPORTED, "tt_encoder_attention: K or V larger than 2 GiB");
+  p.k_rows_total = (int)k_rows; p.vt_cols_total = v_ext;
+  p.k_bytes = (unsigned)kb; p.vt_bytes = (unsigned)vb;
+  p.scale_log2e = 1.4426950408889634f / sqrtf((float)a->head_dim);
+  const dim3 grid((a->l + QB - 1) / QB, a->heads, a->nseq), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  auto go = [&](auto tag, auto dh) {
+    typedef decltype(tag) Tag;
+    constexpr int DH = decltype(dh)::value, D = DH == 64 ? 64 : 128;
+    constexpr size_t ring = 2 * (size_t)(2 * KB * D * Elem<Tag>::ES);    // two stages of K tile + V tile; doubles as the output strips
+    static_assert(ring <= 160 * 1024, "encoder attention K/V ring exceeds the LDS");
+    if (a->causal) launch<enc_attn_kernel<Tag, DH, true>>(grid, block, ring, st, p);
+    else launch<enc_attn_kernel<Tag, DH, false>>(grid, block, ring, st, p);
+  };
+  auto dim = [&](auto tag) {
+    if (a->head_dim == 64) go(tag, std::integral_constant<int, 64>{}); else go(tag, std::integral_constant<int, 80>{});
+  };
+  if (a->dtype == TT_BF16) dim(bf16_tag{}); else if (a->dtype == TT_F16) dim(f16_tag{}); else dim(f32_tag{});
+  TT_CHECK_LAUNCH("tt_encoder_attention");
   return TT_OK;
 }

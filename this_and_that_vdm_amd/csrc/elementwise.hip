@@ -323,6 +323,74 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* x, long 
   }
 }
 
+
+// ---- the CLIP encoders' small kernels (tt_act_rows, tt_patch_tokens, tt_embed_rows)
+// y = act(x) over row views, 8 elements per lane; ACT 0: exact-erf GELU (gelu_erf_f, |erf error| <= 1.5e-7), 1: x sigmoid(1.702 x)
+template <typename Tag, int ACT>
+__global__ void act_rows_kernel(const char* x, long ldx, int rows, int cv, char* y, long ldy) {
+  const long total = (long)rows * cv;
+  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < total; v += (long)gridDim.x * blockDim.x) {
+    const long row = v / cv;
+    const int ch = (int)(v - row * cv) * 8;
+    float f[8];
+    load8<Tag>(x + (row * ldx + ch) * Elem<Tag>::ES, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = ACT == 0 ? gelu_erf_f(f[e]) : f[e] / (1.0f + __expf(-1.702f * f[e]));
+    store8<Tag>(y + (row * ldy + ch) * Elem<Tag>::ES, f);
+  }
+}
+
+// NCHW image -> patch rows: one lane per 8 consecutive k = (c, ky, kx) of one patch; k >= ch p^2 (the tail up to kpad) is zero
+template <typename Tag, bool SRC_F32>
+__global__ void patch_tokens_kernel(const char* src, int ch, int h, int w, int p, long npatch, char* dst, long ld_dst, int kpad) {
+  const int kv = kpad >> 3, gw = w / p, gh = h / p, kk = ch * p * p;
+  const long total = npatch * kv;
+  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < total; v += (long)gridDim.x * blockDim.x) {
+    const long t = v / kv;
+    const int k0 = (int)(v - t * kv) * 8;
+    const int px = (int)(t % gw), py = (int)((t / gw) % gh);
+    const long n = t / ((long)gw * gh);
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int k = k0 + e;
+      f[e] = 0.f;
+      if (k < kk) {
+        const int c = k / (p * p), ky = (k / p) % p, kx = k % p;
+        const long idx = ((n * ch + c) * h + (py * p + ky)) * w + (px * p + kx);
+        f[e] = SRC_F32 ? ((const float*)src)[idx] : load1<Tag>(src + idx * Elem<Tag>::ES);
+      }
+    }
+    store8<Tag>(dst + (t * ld_dst + k0) * Elem<Tag>::ES, f);
+  }
+}
+
+// embedding rows + position rows.  VISION: row r of a sequence of l tokens is the class row (r % l == 0) or patch row (r / l) (l - 1) + r % l - 1;
+// text: table[ids[r]] (an id outside the table reads nothing: zeros).  Sums in fp32, one rounding.
+template <typename Tag, bool VISION>
+__global__ void embed_rows_kernel(const long long* ids, const char* table, long ld_table, int table_rows, const char* cls, const char* pos,
+                                  long ld_pos, int rows, int l, int cv, char* out, long ldo) {
+  constexpr int ES = Elem<Tag>::ES;
+  const long total = (long)rows * cv;
+  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < total; v += (long)gridDim.x * blockDim.x) {
+    const long row = v / cv;
+    const int ch = (int)(v - row * cv) * 8;
+    const int t = (int)(row % l);
+    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, b[8];
+    if constexpr (VISION) {
+      if (t == 0) load8<Tag>(cls + (long)ch * ES, a);
+      else load8<Tag>(table + (((row / l) * (l - 1) + t - 1) * ld_table + ch) * ES, a);
+    } else {
+      const long long id = ids[row];
+      if (id >= 0 && id < table_rows) load8<Tag>(table + ((long)id * ld_table + ch) * ES, a);
+    }
+    load8<Tag>(pos + ((long)t * ld_pos + ch) * ES, b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] += b[e];
+    store8<Tag>(out + (row * ldo + ch) * ES, a);
+  }
+}
+
 }  // namespace
 
 extern "C" int tt_add_rowvec(const void* x, int64_t ldx, int32_t rows, int32_t c, const float* rowvec, int64_t ld_rowvec,
@@ -493,5 +561,64 @@ extern "C" int tt_add_scaled(const void* a, const void* b, float scale, void* y,
   else if (dtype == TT_F16) hipLaunchKernelGGL(add_scaled_kernel<f16_tag>, dim3((unsigned)blocks), dim3(256), 0, st, (const char*)a, (const char*)b, scale, (char*)y, nvec);
   else hipLaunchKernelGGL(add_scaled_kernel<f32_tag>, dim3((unsigned)blocks), dim3(256), 0, st, (const char*)a, (const char*)b, scale, (char*)y, nvec);
   TT_CHECK_LAUNCH("tt_add_scaled");
+  return TT_OK;
+}
+
+extern "C" int tt_act_rows(const void* x, int64_t ldx, int32_t rows, int32_t c, int32_t act, void* y, int64_t ldy, int32_t dtype,
+                           tt_stream_t stream) {
+  if (!x || !y) TT_FAIL(TT_EINVAL, "tt_act_rows: null operand");
+  if (rows <= 0 || c <= 0 || (c & 7) || (ldx & 7) || (ldy & 7) || ldx < c || ldy < c) TT_FAIL(TT_EINVAL, "tt_act_rows: c and strides must be multiples of 8, strides >= c");
+  if (act != 0 && act != 1) TT_FAIL(TT_EINVAL, "tt_act_rows: act %d (0 gelu, 1 quick_gelu)", act);
+  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_act_rows: bad dtype");
+  if ((((size_t)x | (size_t)y) & 15)) TT_FAIL(TT_EINVAL, "tt_act_rows: x and y must start on 16-byte boundaries");
+  const long total = (long)rows * (c >> 3);
+  long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
+  hipStream_t st = (hipStream_t)stream;
+#define TT_ACT(TAG) do { if (act == 0) hipLaunchKernelGGL((act_rows_kernel<TAG, 0>), dim3((unsigned)blocks), dim3(256), 0, st, (const char*)x, (long)ldx, rows, c >> 3, (char*)y, (long)ldy); \
+                         else hipLaunchKernelGGL((act_rows_kernel<TAG, 1>), dim3((unsigned)blocks), dim3(256), 0, st, (const char*)x, (long)ldx, rows, c >> 3, (char*)y, (long)ldy); } while (0)
+  if (dtype == TT_BF16) TT_ACT(bf16_tag); else if (dtype == TT_F16) TT_ACT(f16_tag); else TT_ACT(f32_tag);
+#undef TT_ACT
+  TT_CHECK_LAUNCH("tt_act_rows");
+  return TT_OK;
+}
+
+extern "C" int tt_patch_tokens(const void* src, int32_t src_f32, int32_t nimg, int32_t ch, int32_t h, int32_t w, int32_t p, void* dst,
+                               int64_t ld_dst, int32_t kpad, int32_t dtype, tt_stream_t stream) {
+  if (!src || !dst) TT_FAIL(TT_EINVAL, "tt_patch_tokens: null operand");
+  if (nimg <= 0 || ch <= 0 || p <= 0 || h <= 0 || w <= 0 || h % p || w % p) TT_FAIL(TT_EINVAL, "tt_patch_tokens: image sides must be positive multiples of the patch");
+  if ((kpad & 7) || kpad < ch * p * p || ld_dst < kpad || (ld_dst & 7)) TT_FAIL(TT_EINVAL, "tt_patch_tokens: kpad a multiple of 8 with ch * p * p <= kpad <= ld_dst, ld_dst a multiple of 8");
+  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_patch_tokens: bad dtype");
+  if (dtype == TT_F32 && !src_f32) TT_FAIL(TT_EINVAL, "tt_patch_tokens: TT_F32 takes an fp32 source");
+  if (((size_t)dst & 15)) TT_FAIL(TT_EINVAL, "tt_patch_tokens: dst must start on a 16-byte boundary");
+  const long npatch = (long)nimg * (h / p) * (w / p), total = npatch * (kpad >> 3);
+  long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
+  hipStream_t st = (hipStream_t)stream;
+#define TT_PT(TAG, F) hipLaunchKernelGGL((patch_tokens_kernel<TAG, F>), dim3((unsigned)blocks), dim3(256), 0, st, (const char*)src, ch, h, w, p, npatch, (char*)dst, (long)ld_dst, kpad)
+  if (dtype == TT_BF16) { if (src_f32) TT_PT(bf16_tag, true); else TT_PT(bf16_tag, false); }
+  else if (dtype == TT_F16) { if (src_f32) TT_PT(f16_tag, true); else TT_PT(f16_tag, false); }
+  else TT_PT(f32_tag, true);
+#undef TT_PT
+  TT_CHECK_LAUNCH("tt_patch_tokens");
+  return TT_OK;
+}
+
+extern "C" int tt_embed_rows(int32_t mode, const int64_t* ids, const void* table, int64_t ld_table, int32_t table_rows, const void* cls,
+                             const void* pos, int64_t ld_pos, int32_t rows, int32_t l, int32_t c, void* out, int64_t ldo, int32_t dtype,
+                             tt_stream_t stream) {
+  if (mode != 0 && mode != 1) TT_FAIL(TT_EINVAL, "tt_embed_rows: mode %d (0 text, 1 vision)", mode);
+  if (!table || !pos || !out || (mode == 0 ? !ids : !cls)) TT_FAIL(TT_EINVAL, "tt_embed_rows: null operand");
+  if (rows <= 0 || l <= 0 || rows % l || c <= 0 || (c & 7) || (ld_table & 7) || (ld_pos & 7) || (ldo & 7) || ld_table < c || ld_pos < c || ldo < c)
+    TT_FAIL(TT_EINVAL, "tt_embed_rows: rows a multiple of l, c and strides multiples of 8, strides >= c");
+  if (mode == 0 ? table_rows <= 0 : (l < 2 || table_rows != rows / l * (l - 1))) TT_FAIL(TT_EINVAL, "tt_embed_rows: table_rows (vision: rows / l * (l - 1) patch rows)");
+  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_embed_rows: bad dtype");
+  if ((((size_t)table | (size_t)cls | (size_t)pos | (size_t)out) & 15) || ((size_t)ids & 7)) TT_FAIL(TT_EINVAL, "tt_embed_rows: operands must start on 16-byte boundaries");
+  const long total = (long)rows * (c >> 3);
+  long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
+  hipStream_t st = (hipStream_t)stream;
+#define TT_EMB(TAG) do { if (mode == 0) hipLaunchKernelGGL((embed_rows_kernel<TAG, false>), dim3((unsigned)blocks), dim3(256), 0, st, (const long long*)ids, (const char*)table, (long)ld_table, table_rows, (const char*)cls, (const char*)pos, (long)ld_pos, rows, l, c >> 3, (char*)out, (long)ldo); \
+                         else hipLaunchKernelGGL((embed_rows_kernel<TAG, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const long long*)ids, (const char*)table, (long)ld_table, table_rows, (const char*)cls, (const char*)pos, (long)ld_pos, rows, l, c >> 3, (char*)out, (long)ldo); } while (0)
+  if (dtype == TT_BF16) TT_EMB(bf16_tag); else if (dtype == TT_F16) TT_EMB(f16_tag); else TT_EMB(f32_tag);
+#undef TT_EMB
+  TT_CHECK_LAUNCH("tt_embed_rows");
   return TT_OK;
 }

@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import TT_BF16, TT_F16, TT_F32, TtAttnArgs, TtConvArgs, TtGemmArgs, check
+from ._lib import TT_BF16, TT_F16, TT_F32, TtAttnArgs, TtConvArgs, TtEncAttnArgs, TtGemmArgs, check
 from .packing import PreSplitF32
 
 
@@ -551,5 +551,94 @@ def add_scaled(a, b, scale=1.0, out=None):
     if out is None:
         out = torch.empty_like(a)
     check(lib.tt_add_scaled(_p(a), _p(b), scale, _p(out), a.numel(), _code(a.dtype), _stream()), "tt_add_scaled")
+    _wrote(out)
+    return out
+
+
+# ---- the CLIP encoders (this_and_that_vdm_amd/clip.py)
+def encoder_attention(q, k, v, out, *, nseq, l, heads, head_dim, causal=False, k_seq_stride=None, v_seq_stride=None):
+    """softmax(q k^T / sqrt(d) [+ causal]) v per (sequence, head), l queries = l keys, head_dim 64 or 80 (tt_encoder_attention).
+    q [nseq*l, heads*d]; k [rows, heads*d], key j of sequence s in row s*k_seq_stride + j (default l).  16-bit storage: v like k (V itself,
+    e.g. q / k / v = the three column slices of a fused projection); fp32 storage: v is V TRANSPOSED, [heads*d, columns], key j of
+    sequence s in column s*v_seq_stride + j (gemm(..., out_col_pad=(l, v_seq_stride)), v_seq_stride a multiple of 4)."""
+    lib = _lib.load()
+    if not (q.dtype == k.dtype == v.dtype == out.dtype):
+        raise RuntimeError("encoder_attention: q, k, v and out must share one dtype")
+    for t in (q, k, v, out):
+        assert t.dim() == 2 and t.stride(1) == 1, (t.shape, t.stride())
+    a = TtEncAttnArgs()
+    a.q, a.ldq, a.k, a.ldk = _p(q), q.stride(0), _p(k), k.stride(0)
+    a.v, a.ldv, a.out, a.ldo = _p(v), v.stride(0), _p(out), out.stride(0)
+    a.nseq, a.l, a.heads, a.head_dim, a.causal = nseq, l, heads, head_dim, int(bool(causal))
+    a.k_seq_stride = l if k_seq_stride is None else k_seq_stride
+    a.v_seq_stride = l if v_seq_stride is None else v_seq_stride
+    a.dtype = _code(q.dtype)
+    ev = _prof_begin()
+    check(lib.tt_encoder_attention(C.byref(a), _stream()), "tt_encoder_attention")
+    _wrote(out)
+    if ev is not None:
+        _prof_end(ev, f"enc_attn_kernel<{_TAG[a.dtype]}, {head_dim}, {'true' if causal else 'false'}>",
+                  4.0 * nseq * heads * l * l * head_dim * (0.5 if causal else 1.0), shape=("attn", nseq * heads, l, l, int(bool(causal)), 0))
+    return out
+
+
+ACTS = {"gelu": 0, "quick_gelu": 1}
+
+
+def act_rows(x, act: str = "gelu", out=None):
+    """y = act(x) over a [rows, c] row view (strides allowed; out=x: in place).  act: "gelu" (exact erf) or "quick_gelu"."""
+    lib = _lib.load()
+    if act not in ACTS:
+        raise RuntimeError(f"act_rows: unknown activation {act!r} (one of {sorted(ACTS)})")
+    assert x.dim() == 2 and x.stride(1) == 1, (x.shape, x.stride())
+    y = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device) if out is None else out
+    assert y.shape == x.shape and y.stride(1) == 1 and y.dtype == x.dtype
+    check(lib.tt_act_rows(_p(x), x.stride(0), x.shape[0], x.shape[1], ACTS[act], _p(y), y.stride(0), _code(x.dtype), _stream()), "tt_act_rows")
+    _wrote(y)
+    return y
+
+
+def patch_tokens(src, patch: int, dtype, kpad=None):
+    """[N, C, H, W] (fp32 or `dtype`) -> [N*(H/p)*(W/p), kpad] rows of `dtype`, k = (c, ky, kx), zero tail (kpad = C*p*p rounded up to 8)."""
+    lib = _lib.load()
+    n, c, h, w = src.shape
+    src = src.contiguous()
+    if src.dtype not in (torch.float32, dtype):
+        src = src.float()
+    kk = c * patch * patch
+    kpad = (kk + 7) // 8 * 8 if kpad is None else kpad
+    if h % patch or w % patch:
+        raise RuntimeError(f"patch_tokens: image {h}x{w} is not a whole number of {patch}x{patch} patches")
+    out = torch.empty((n * (h // patch) * (w // patch), kpad), dtype=dtype, device=src.device)
+    check(lib.tt_patch_tokens(_p(src), int(src.dtype == torch.float32), n, c, h, w, patch, _p(out), out.stride(0), kpad, _code(dtype),
+                              _stream()), "tt_patch_tokens")
+    _wrote(out)
+    return out
+
+
+def embed_rows(table, pos, *, ids=None, cls=None, l: int, out=None):
+    """Text (ids int64 [rows]): out[r] = table[ids[r]] + pos[r % l].  Vision (cls [c], table = patch rows [N*(l-1), c]):
+    out[r] = (class row | patch row) + pos[r % l], rows = N*l."""
+    lib = _lib.load()
+    assert table.dim() == 2 and table.stride(1) == 1 and pos.dim() == 2 and pos.stride(1) == 1 and pos.dtype == table.dtype
+    c = table.shape[1]
+    if pos.shape[0] < l or pos.shape[1] != c:
+        raise RuntimeError(f"embed_rows: position table {tuple(pos.shape)} does not cover {l} positions of width {c}")
+    if (ids is None) == (cls is None):
+        raise RuntimeError("embed_rows: pass ids (text) or cls (vision)")
+    if ids is not None:
+        if ids.dtype != torch.int64 or not ids.is_contiguous():
+            raise RuntimeError("embed_rows: ids must be a contiguous int64 tensor")
+        rows, mode = ids.numel(), 0
+    else:
+        assert cls.dtype == table.dtype and cls.is_contiguous() and cls.numel() == c
+        if l < 2 or table.shape[0] % (l - 1):
+            raise RuntimeError(f"embed_rows: {table.shape[0]} patch rows are not a whole number of images of {l - 1} patches")
+        rows, mode = table.shape[0] // (l - 1) * l, 1
+    if out is None:
+        out = torch.empty((rows, c), dtype=table.dtype, device=table.device)
+    assert out.shape == (rows, c) and out.stride(1) == 1 and out.dtype == table.dtype
+    check(lib.tt_embed_rows(mode, _p(ids), _p(table), table.stride(0), table.shape[0], _p(cls), _p(pos), pos.stride(0), rows, l, c,
+                            _p(out), out.stride(0), _code(table.dtype), _stream()), "tt_embed_rows")
     _wrote(out)
     return out

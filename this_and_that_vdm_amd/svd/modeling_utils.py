@@ -21,13 +21,14 @@ WEIGHTS_NAME = "diffusion_pytorch_model.safetensors"
 WEIGHTS_NAME_BIN = "diffusion_pytorch_model.bin"
 
 
-def _load_weights(path: str, variant: str = None) -> Dict[str, torch.Tensor]:
+def _load_weights(path: str, variant: str = None, name: str = "diffusion_pytorch_model") -> Dict[str, torch.Tensor]:
     """State dict of a diffusers model folder: a single ``diffusion_pytorch_model[.variant].safetensors`` / ``.bin``, or
     a sharded checkpoint described by ``diffusion_pytorch_model.safetensors.index[.variant].json`` (``weight_map``:
-    parameter name -> shard file), as diffusers' save_pretrained(max_shard_size=...) writes it."""
-    stem = "diffusion_pytorch_model" + (f".{variant}" if variant else "")
+    parameter name -> shard file), as diffusers' save_pretrained(max_shard_size=...) writes it.  ``name``: the file stem
+    (transformers folders -- the CLIP encoders -- use ``model``)."""
+    stem = name + (f".{variant}" if variant else "")
     st_file, bin_file = os.path.join(path, stem + ".safetensors"), os.path.join(path, stem + ".bin")
-    index = os.path.join(path, "diffusion_pytorch_model.safetensors.index" + (f".{variant}" if variant else "") + ".json")
+    index = os.path.join(path, name + ".safetensors.index" + (f".{variant}" if variant else "") + ".json")
     if os.path.isfile(st_file):
         from safetensors.torch import load_file
         return load_file(st_file)
