@@ -442,6 +442,52 @@ int tt_embed_rows(int32_t mode, const int64_t* ids, const void* table, int64_t l
                   const void* pos, int64_t ld_pos, int32_t rows, int32_t l, int32_t c, void* out, int64_t ldo, int32_t dtype,
                   tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The request path around the models: what encode_clip does to the image before the CLIP vision model and to the context after the
+ * text encoder, and what decode_latents / tensor2vid do to the decoder's output (svd/pipeline_stable_video_diffusion_controlnet.py).
+ * Additive: the ABI version is unchanged.
+ *
+ * tt_clip_image: the preprocessing in front of CLIPVisionModelWithProjection -- _resize_with_antialiasing (:741-767) as encode_clip
+ * calls it (:130-185: image * 2 - 1, resize to out_h x out_w, (image + 1) / 2) and the feature extractor's per-channel
+ * normalisation (:145-152).  All arithmetic fp32:
+ *   src      src_kind 0: uint8 [nimg, h, w, 3] (what np.asarray of a PIL RGB image holds), x = u / 255;
+ *            src_kind 1: fp32 [nimg, 3, h, w] in [0, 1]
+ *   v = 2 x - 1
+ *   per axis: f = in / out, sigma = max((f - 1) / 2, 1e-3), k = int(max(4 sigma, 3)) made odd; taps exp(-t^2 / (2 sigma^2)) for
+ *            t = -(k / 2) .. k / 2, normalised to sum 1 (formed on the host in fp64, rounded to fp32)
+ *   blur     along x, then along y, each with reflect padding (no edge repeat)
+ *   resample bicubic, align_corners = True (source position o (in - 1) / (out - 1)), A = -0.75, the four tap indices clamped to the image
+ *   dst[n][c] = ((v + 1) / 2 - mean_c) / std_c   in `dtype` (TT_BF16 / TT_F16 / TT_F32), contiguous [nimg, 3, out_h, out_w]
+ * THREE launches (blur x: src -> ws, blur y: ws -> ws, resample + normalise: ws -> dst); ws holds two fp32 copies of the image planes,
+ * tt_clip_image_ws_bytes(nimg, h, w) bytes, 16-byte aligned.  Refused: TT_EINVAL for a null operand, a bad src_kind / dtype, an empty
+ * image, out_h or out_w < 2 (align_corners divides by out - 1), a std <= 0, a reflect pad k / 2 that reaches the image size (h or
+ * w <= k / 2: torch refuses it too), a workspace that is too small or misaligned; TT_EUNSUPPORTED for more than 63 taps on an axis (63
+ * covers in / out <= 32.5, e.g. a 3500-pixel side -> 224). */
+size_t tt_clip_image_ws_bytes(int32_t nimg, int32_t h, int32_t w);
+int tt_clip_image(const void* src, int32_t src_kind, int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w,
+                  float mean0, float mean1, float mean2, float std0, float std1, float std2, void* dst, int32_t dtype,
+                  void* ws, size_t ws_bytes, tt_stream_t stream);
+
+/* LayerNorm without affine parameters over a whole [rows, c] block per batch element: the nn.LayerNorm((78, 1024)) that encode_clip
+ * constructs afresh (weight 1, bias 0) for the text + image context of use_text requests (:172):
+ *   y[b] = (x[b] - mean_b) * rsqrt(var_b + eps),  mean_b / var_b (biased) over all rows * c elements of batch element b.
+ * x and y are [nb * rows, ldx] in `dtype` with the same row stride (c, ldx multiples of 8, ldx >= c; columns c .. ldx are neither
+ * read nor written); y may be x.  Statistics: the mean first (fp32 sums of x - x[b][0][0] per thread, fp64 across threads), then the sum
+ * of squares centred on it -- never E[x^2] - E[x]^2.  One 256-thread block per batch element, one launch. */
+int tt_layernorm_block(const void* x, int64_t ldx, int32_t nb, int32_t rows, int32_t c, float eps, void* y, int32_t dtype,
+                       tt_stream_t stream);
+
+/* Decoder output -> what the caller receives: decode_latents' permute + float (:257-283) and tensor2vid / VaeImageProcessor.postprocess
+ * (image / 2 + 0.5, clamp to [0, 1], NCHW -> NHWC; for "pil" numpy_to_pil's (image * 255).round().astype(uint8)).
+ *   src  [n, ch, h, w] in src_dtype (TT_BF16 / TT_F16 / TT_F32), 1 <= ch <= 4 (TT_EUNSUPPORTED beyond)
+ *   dst  [n, h, w, ch]:  kind 0  fp32   f = clamp(x * 0.5 + 0.5, 0, 1)
+ *                        kind 1  uint8  rint(f * 255), round-half-to-even
+ * Bit-exact with the torch / numpy statements on the fp32 value of x: x * 0.5 is exact, so the addition is the only rounding, and
+ * f * 255 is one fp32 product.  A NaN is not part of the contract: the kernel writes 0 (kind 0: +0.0f) where torch writes NaN.
+ * One launch. */
+int tt_frames_out(const void* src, int32_t src_dtype, int32_t n, int32_t ch, int32_t h, int32_t w, int32_t kind, void* dst,
+                  tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

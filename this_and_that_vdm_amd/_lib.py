@@ -118,6 +118,11 @@ SIGNATURES = {
     "tt_act_rows": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
     "tt_patch_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
     "tt_embed_rows": (C.c_int, [_i32, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
+    # the request path around the models: CLIP preprocessing, context LayerNorm, frame export (additive as well)
+    "tt_clip_image_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "tt_clip_image": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _sz, _vp]),
+    "tt_layernorm_block": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _f32, _vp, _i32, _vp]),
+    "tt_frames_out": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -642,3 +642,69 @@ def embed_rows(table, pos, *, ids=None, cls=None, l: int, out=None):
                             _p(out), out.stride(0), _code(table.dtype), _stream()), "tt_embed_rows")
     _wrote(out)
     return out
+
+
+# ---- the request path around the models (svd/pipeline_stable_video_diffusion_controlnet.py: encode_clip, decode_latents + tensor2vid)
+def clip_image(src, size, mean, std, dtype):
+    """CLIP image preprocessing on the device (tt_clip_image): ``pipeline_utils.resize_with_antialiasing(x * 2 - 1, size)`` -> ``(. + 1) / 2``
+    -> ``(. - mean) / std`` in fp32.  src: uint8 [N, H, W, 3] (or [H, W, 3]; x = u / 255) or float32 [N, 3, H, W] in [0, 1].
+    -> [N, 3, size[0], size[1]] in `dtype`."""
+    lib = _lib.load()
+    _p(src)
+    if src.dtype == torch.uint8:
+        src = src[None] if src.dim() == 3 else src
+        if src.dim() != 4 or src.shape[-1] != 3:
+            raise RuntimeError(f"clip_image: a uint8 source is [N, H, W, 3], got {tuple(src.shape)}")
+        kind, (n, h, w) = 0, src.shape[:3]
+    elif src.dtype == torch.float32:
+        if src.dim() != 4 or src.shape[1] != 3:
+            raise RuntimeError(f"clip_image: a float32 source is [N, 3, H, W], got {tuple(src.shape)}")
+        kind, n, (h, w) = 1, src.shape[0], src.shape[2:]
+    else:
+        raise RuntimeError(f"clip_image: the source must be uint8 (NHWC) or float32 (NCHW), got {src.dtype}")
+    if len(mean) != 3 or len(std) != 3:
+        raise RuntimeError("clip_image: mean and std hold one value per RGB channel")
+    src = src.contiguous()
+    oh, ow = int(size[0]), int(size[1])
+    out = torch.empty((n, 3, oh, ow), dtype=dtype, device=src.device)
+    need = lib.tt_clip_image_ws_bytes(n, h, w)
+    ws = _workspace(need, src.device)
+    check(lib.tt_clip_image(_p(src), kind, n, h, w, oh, ow, *[float(v) for v in mean], *[float(v) for v in std], _p(out), _code(dtype),
+                            _p(ws), need, _stream()), "tt_clip_image")
+    _wrote(out)
+    return out
+
+
+def layernorm_block(x, rows: int, eps: float = 1e-5, out=None):
+    """LayerNorm without affine parameters over each [rows, c] block of the row view x [nb * rows, c] (tt_layernorm_block): the
+    ``nn.LayerNorm((rows, c))`` encode_clip builds afresh for the use_text context.  ``out`` may be ``x`` (in place) or a row view with
+    x's row stride."""
+    lib = _lib.load()
+    _p(x)
+    assert x.dim() == 2 and x.stride(1) == 1, (x.shape, x.stride())
+    if rows <= 0 or x.shape[0] % rows:
+        raise RuntimeError(f"layernorm_block: {x.shape[0]} rows are not a whole number of blocks of {rows}")
+    y = torch.empty_strided(tuple(x.shape), tuple(x.stride()), dtype=x.dtype, device=x.device) if out is None else out
+    if y.shape != x.shape or y.stride() != x.stride() or y.dtype != x.dtype:
+        raise RuntimeError("layernorm_block: out must have x's shape, strides and dtype")
+    check(lib.tt_layernorm_block(_p(x), x.stride(0), x.shape[0] // rows, rows, x.shape[1], float(eps), _p(y), _code(x.dtype), _stream()),
+          "tt_layernorm_block")
+    _wrote(y)
+    return y
+
+
+def frames_out(x, kind: int):
+    """Decoder output [N, C, H, W] (C <= 4, bf16 / fp16 / fp32) -> NHWC frames as the caller receives them (tt_frames_out):
+    kind 0 float32 ``clamp(x / 2 + 0.5, 0, 1)`` (output_type "np"), kind 1 uint8 ``rint(that * 255)`` ("pil") -- bit for bit what
+    ``VaeImageProcessor.postprocess`` / ``numpy_to_pil`` compute."""
+    lib = _lib.load()
+    _p(x)
+    if kind not in (0, 1):
+        raise RuntimeError(f"frames_out: kind {kind!r} (0 float32, 1 uint8)")
+    assert x.dim() == 4, x.shape
+    x = x.contiguous()
+    n, ch, h, w = x.shape
+    out = torch.empty((n, h, w, ch), dtype=torch.float32 if kind == 0 else torch.uint8, device=x.device)
+    check(lib.tt_frames_out(_p(x), _code(x.dtype), n, ch, h, w, kind, _p(out), _stream()), "tt_frames_out")
+    _wrote(out)
+    return out

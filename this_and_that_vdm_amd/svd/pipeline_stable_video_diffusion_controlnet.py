@@ -6,6 +6,8 @@ Kept: the ``__call__`` surface and argument meaning, CLIP(+text) context with th
 LayerNorm((78,1024)) (reference :165-173), un-scaled VAE ``.mode()`` latents (:200), CFG order [uncond, cond]
 (:177-185,203-211), fps-1 / motion bucket / noise-aug time ids, per-frame guidance ramp, ``output_type="latent"``,
 ``latents=``, ``generator=``, ``callback_on_step_end``.
+Opt-in (``native_image_io=True``, default off): the CLIP image preprocessing, the use_text context LayerNorm and the export of decoded
+frames run on the library's kernels (ops.clip_image / layernorm_block / frames_out) instead of stock torch ops.
 ``use_instructpix2pix`` (CFG batch of 3, reference :182-184,208-210,698-702) and ``guess_mode`` without CFG are built;
 ``guess_mode`` with CFG raises, as the reference's branch (:676-681) cannot run either.
 Changed on purpose: the gesture map is VAE-encoded ONCE per request instead of inside every step (reference :652 --
@@ -19,19 +21,30 @@ import PIL.Image
 import torch
 import torch.nn as nn
 
+from .. import ops
 from .denoise import DenoiseLoop
 from .pipeline_utils import (CLIPFeatureExtractor, PipelineBase, StableVideoDiffusionPipelineOutput, VaeImageProcessor,
                              append_dims, randn_tensor, resize_with_antialiasing, tensor2vid)
 from .temporal_controlnet import ControlNetModel
 
 
+_NO_FEATURE_EXTRACTOR = ("encode_clip: the pipeline has no feature_extractor, so the CLIP mean/std normalisation the "
+                         "reference always applies (:145-152) cannot be done; build the pipeline with from_pretrained() "
+                         "or pass feature_extractor=CLIPFeatureExtractor()")
+
+
 class _SVDPipelineCore(PipelineBase):
     model_cpu_offload_seq = "image_encoder->unet->vae"
     _callback_tensor_inputs = ["latents"]
+    native_image_io = False            # class default: also what an instance built without __init__ sees
 
-    def __init__(self, vae, image_encoder, unet, scheduler, feature_extractor):
+    def __init__(self, vae, image_encoder, unet, scheduler, feature_extractor, native_image_io: bool = False):
         self.register_modules(vae=vae, image_encoder=image_encoder, unet=unet, scheduler=scheduler,
                               feature_extractor=feature_extractor)
+        # True: PIL / numpy images reach CLIP through ops.clip_image, the use_text context LayerNorm is ops.layernorm_block and
+        # "np" / "pil" frames leave through ops.frames_out (one uint8 / fp32 NHWC copy per decoded chunk).  A plain attribute:
+        # it may be switched between calls.
+        self.native_image_io = bool(native_image_io)
         self.vae_scale_factor = 2 ** (len(self.vae.config.block_out_channels) - 1)
         self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, do_convert_rgb=True)
         self.control_image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, do_convert_rgb=True,
@@ -40,7 +53,7 @@ class _SVDPipelineCore(PipelineBase):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, *, vae=None, image_encoder=None, unet=None, scheduler=None,
-                        feature_extractor=None, torch_dtype=None, **kwargs):
+                        feature_extractor=None, torch_dtype=None, native_image_io: bool = False, **kwargs):
         """The reference passes vae / image_encoder / unet explicitly (test_code/inference.py:171-178) and lets diffusers
         load the remaining components from the hub folder.  Same here, from a LOCAL diffusers-format folder (no network):
           feature_extractor/preprocessor_config.json -> CLIP image processor (mean/std used by ``encode_clip``, reference :145-152)
@@ -48,7 +61,8 @@ class _SVDPipelineCore(PipelineBase):
           unet/                                      -> UNetSpatioTemporalConditionModel (only if ``unet`` is not passed)
         vae and image_encoder are third-party models (AutoencoderKLTemporalDecoder / CLIPVisionModelWithProjection) and must be
         passed in.  Without a folder the scheduler defaults to SVD's shipped EulerDiscrete configuration and the feature
-        extractor to CLIP's published preprocessing constants; nothing is ever silently skipped."""
+        extractor to CLIP's published preprocessing constants; nothing is ever silently skipped.
+        ``native_image_io=True`` sets the pipeline attribute of that name (default False: the torch request path)."""
         import os
         path = pretrained_model_name_or_path
         have_dir = isinstance(path, str) and os.path.isdir(path)
@@ -65,33 +79,56 @@ class _SVDPipelineCore(PipelineBase):
         if feature_extractor is None:
             cfg = os.path.join(path, "feature_extractor", "preprocessor_config.json") if have_dir else None
             feature_extractor = CLIPFeatureExtractor.from_json_file(cfg) if cfg and os.path.isfile(cfg) else CLIPFeatureExtractor()
-        return cls(vae=vae, image_encoder=image_encoder, unet=unet, scheduler=scheduler, feature_extractor=feature_extractor)
+        return cls(vae=vae, image_encoder=image_encoder, unet=unet, scheduler=scheduler, feature_extractor=feature_extractor,
+                   native_image_io=native_image_io)
 
     # ---- constants of a request (reference :130-254,305-337)
     def encode_clip(self, image, prompt, use_text, text_encoder, device, num_videos_per_prompt, do_classifier_free_guidance,
                     use_instructpix2pix=False):
         dtype = next(self.image_encoder.parameters()).dtype
+        # encode_clip needs only the encoder, the two processors and, optionally, this switch of whatever object it is called on
+        # (callers run it unbound on stand-ins that predate the option): absent means off
+        native = getattr(self, "native_image_io", False)
         if not isinstance(image, torch.Tensor):
-            image = self.image_processor.numpy_to_pt(self.image_processor.pil_to_numpy(image))
-            image = (resize_with_antialiasing(image * 2.0 - 1.0, (224, 224)) + 1.0) / 2.0
-            if self.feature_extractor is None:
-                raise RuntimeError("encode_clip: the pipeline has no feature_extractor, so the CLIP mean/std normalisation the "
-                                   "reference always applies (:145-152) cannot be done; build the pipeline with from_pretrained() "
-                                   "or pass feature_extractor=CLIPFeatureExtractor()")
-            image = self.feature_extractor(images=image, do_normalize=True, do_center_crop=False, do_resize=False,
-                                           do_rescale=False, return_tensors="pt").pixel_values
+            if native:
+                image = self._clip_image_native(image, device, dtype)
+            else:
+                image = self.image_processor.numpy_to_pt(self.image_processor.pil_to_numpy(image))
+                image = (resize_with_antialiasing(image * 2.0 - 1.0, (224, 224)) + 1.0) / 2.0
+                if self.feature_extractor is None:
+                    raise RuntimeError(_NO_FEATURE_EXTRACTOR)
+                image = self.feature_extractor(images=image, do_normalize=True, do_center_crop=False, do_resize=False,
+                                               do_rescale=False, return_tensors="pt").pixel_values
         emb = self.image_encoder(image.to(device=device, dtype=dtype)).image_embeds.unsqueeze(1)
         bs, seq, _ = emb.shape
         ehs = emb.repeat(1, num_videos_per_prompt, 1).view(bs * num_videos_per_prompt, seq, -1)
         if use_text:
             text = text_encoder(prompt)[0]
             ehs = torch.cat((text, ehs), dim=1)
-            ln = nn.LayerNorm(tuple(ehs.shape[1:])).to(device=device, dtype=dtype)      # fresh, gamma=1 beta=0 (:172)
-            ehs = ln(ehs)
+            if native:
+                ehs = ops.layernorm_block(ehs.reshape(-1, ehs.shape[-1]), ehs.shape[1], eps=1e-5).view(ehs.shape)
+            else:
+                ln = nn.LayerNorm(tuple(ehs.shape[1:])).to(device=device, dtype=dtype)      # fresh, gamma=1 beta=0 (:172)
+                ehs = ln(ehs)
         if do_classifier_free_guidance:
             neg = torch.zeros_like(ehs)
             ehs = torch.cat([ehs, neg, neg]) if use_instructpix2pix else torch.cat([neg, ehs])        # :182-185
         return ehs
+
+    def _clip_image_native(self, image, device, dtype):
+        """PIL / list of PIL / numpy image(s) -> the CLIP vision model's input on the device: the uint8 HWC pixels are uploaded once
+        and ops.clip_image does the reference's resize + normalisation (:145-152, 741-767) there.  A numpy image that is not uint8
+        takes the values pil_to_numpy would give it (x / 255), as float32 NCHW.  The images must be RGB (three channels): the kernel
+        refuses anything else, where the torch path would hand a grayscale / RGBA array on to the encoder."""
+        if self.feature_extractor is None:
+            raise RuntimeError(_NO_FEATURE_EXTRACTOR)
+        ims = [np.asarray(im) for im in (image if isinstance(image, (list, tuple)) else [image])]
+        arr = np.stack([im[..., None] if im.ndim == 2 else im for im in ims], 0)
+        if arr.dtype == np.uint8:
+            src = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+        else:
+            src = self.image_processor.numpy_to_pt(arr.astype(np.float32) / 255.0).contiguous().to(device)
+        return ops.clip_image(src, (224, 224), self.feature_extractor.image_mean, self.feature_extractor.image_std, dtype)
 
     def _encode_vae_image(self, image, device, num_videos_per_prompt, do_classifier_free_guidance, use_instructpix2pix=False):
         lat = self.vae.encode(image.to(device=device)).latent_dist.mode()
@@ -113,17 +150,30 @@ class _SVDPipelineCore(PipelineBase):
             return t
         return torch.cat([t, t, t]) if use_instructpix2pix else torch.cat([t, t])
 
-    def decode_latents(self, latents, num_frames, decode_chunk_size=14):
+    def _decode_chunks(self, latents, decode_chunk_size):
+        """the decoder's ``.sample`` [f, 3, H, W] for every chunk of at most decode_chunk_size frames (reference :257-283)"""
         import inspect
         lat = latents.flatten(0, 1) / self.vae.config.scaling_factor
         takes_frames = "num_frames" in inspect.signature(self.vae.forward).parameters
-        out = []
         for i in range(0, lat.shape[0], decode_chunk_size):
             chunk = lat[i:i + decode_chunk_size]
             kw = {"num_frames": chunk.shape[0]} if takes_frames else {}
-            out.append(self.vae.decode(chunk, **kw).sample)
-        frames = torch.cat(out, 0)
+            yield self.vae.decode(chunk, **kw).sample
+
+    def decode_latents(self, latents, num_frames, decode_chunk_size=14):
+        frames = torch.cat(list(self._decode_chunks(latents, decode_chunk_size)), 0)
         return frames.reshape(-1, num_frames, *frames.shape[1:]).permute(0, 2, 1, 3, 4).float()
+
+    def _frames_native(self, latents, num_frames, decode_chunk_size, output_type):
+        """decode_latents + tensor2vid for "np" / "pil" through ops.frames_out: every decoded chunk leaves the device once, as the
+        NHWC float32 ("np") or uint8 ("pil") array the caller receives."""
+        kind = 0 if output_type == "np" else 1
+        host = [ops.frames_out(sample, kind).cpu().numpy() for sample in self._decode_chunks(latents, decode_chunk_size)]
+        arr = np.concatenate(host, 0)
+        arr = arr.reshape(-1, num_frames, *arr.shape[1:])                                # [B, F, H, W, C]
+        if output_type == "np":
+            return arr
+        return [[PIL.Image.fromarray(im.squeeze(-1) if im.shape[-1] == 1 else im) for im in video] for video in arr]
 
     def check_inputs(self, image, height, width):
         if not isinstance(image, (torch.Tensor, PIL.Image.Image, list)):
@@ -227,7 +277,9 @@ class _SVDPipelineCore(PipelineBase):
                         loop.latents.copy_(new.reshape(loop.latents.shape))
                 bar.update()
         latents = loop.result().to(ehs.dtype)
-        if output_type != "latent":
+        if self.native_image_io and output_type in ("np", "pil"):
+            frames = self._frames_native(latents.to(self.vae.dtype), num_frames, decode_chunk_size, output_type)
+        elif output_type != "latent":
             frames = tensor2vid(self.decode_latents(latents.to(self.vae.dtype), num_frames, decode_chunk_size),
                                 self.image_processor, output_type=output_type)
         else:
