@@ -361,6 +361,27 @@ int tt_cfg_euler_step(const float* eps, int32_t ld_eps, float* latents, const fl
 int tt_cfg3_euler_step(const float* eps, int32_t ld_eps, float* latents, const float* guidance, float image_guidance_scale,
                        const float* sigmas, int32_t step, int32_t frames, int32_t h, int32_t w, tt_stream_t stream);
 
+/* The same glue for R independent requests in one launch (additive: the ABI version is unchanged).  The reference's __call__ takes a
+ * list of images and num_videos_per_prompt > 1 (pipeline_stable_video_diffusion_controlnet.py:392, :520-605) and runs the loop body
+ * (:630-635 prep, :698-709 CFG + scheduler.step) on the joint batch; here every request is computed as a call of its own would.
+ * Batch order is CFG-major, b = c * requests + r, c in [0, cfg): what torch.cat([neg, cond]) (:185, :211)
+ * gives for batched tensors, so image_latents [R*C,F,4,h,w] is taken as the reference holds it.
+ * tt_prep_model_input_requests: x[b,f,p,0:4] = latents[r,f,:,p] * c_in, x[...,4:8] = image_latents[b,f,:,p],
+ *   x[...,8:12] = cond[f,:,p] (cond_per_request 0: one [F,4,h,w] for all requests, reference :660) or cond[r,f,:,p]
+ *   (cond_per_request 1: [R,F,4,h,w]); cond NULL: 8 channels.  x [R*C*F*h*w, cpad] token rows in `dtype`.
+ * tt_cfg_euler_step_requests: eps [R*C*F*h*w, ld_eps] fp32 token rows in the same order; cfg 1 (no CFG; guidance may be NULL),
+ *   2 (uncond, cond) or 3 (first-frame, cond, uncond + image_guidance_scale, :698-702); guidance fp32 [F] for all requests
+ *   (guidance_per_request 0) or [R,F] (1); latents fp32 [R,F,4,h,w] updated in place by the v-prediction Euler step.  All requests
+ *   share sigmas[step], sigmas[step+1].
+ * Element indices are 64-bit throughout.  TT_EINVAL: a null operand, requests / frames / h / w <= 0, cfg outside 1..3, cpad < 8 (12
+ * with cond) or not a multiple of 8, a flag that is not 0 / 1, ld_eps < 4, cfg 3 without guidance, a bad dtype. */
+int tt_prep_model_input_requests(const float* latents, const float* image_latents, const float* cond, int32_t cond_per_request,
+                                 const float* sigmas, int32_t step, int32_t requests, int32_t cfg, int32_t frames, int32_t h,
+                                 int32_t w, int32_t cpad, void* x, int32_t dtype, tt_stream_t stream);
+int tt_cfg_euler_step_requests(const float* eps, int64_t ld_eps, float* latents, const float* guidance, int32_t guidance_per_request,
+                               float image_guidance_scale, const float* sigmas, int32_t step, int32_t requests, int32_t cfg,
+                               int32_t frames, int32_t h, int32_t w, tt_stream_t stream);
+
 /* layout plumbing at the drop-in boundary: NCHW (any float dtype code below) <-> token-major.
  * src_kind/dst_kind: 0 = dtype (bf16/f16), 1 = fp32. */
 int tt_nchw_to_tokens(const void* src, int32_t src_f32, int32_t nimg, int32_t c, int32_t hw, void* dst, int64_t ld_dst,

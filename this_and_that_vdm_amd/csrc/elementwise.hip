@@ -208,6 +208,80 @@ __global__ void cfg_euler_kernel(const float* eps, int ld_eps, float* lat, const
   }
 }
 
+// R-request forms of the two loop-glue kernels (tt_prep_model_input_requests / tt_cfg_euler_step_requests).  Internal batch order is
+// CFG-major, b = c * requests + r -- the order torch.cat([neg, cond]) gives the reference's batched tensors -- so image_latents
+// [R*C,F,4,h,w] is read as it is and request r's latents are duplicated into its C batch elements.  All indices are 64-bit: R*C*F*hw*cpad
+// passes 2^31 at 64x112 latents for a few requests.  The arithmetic is the single-request kernels' statement by statement.
+template <typename Tag>
+__global__ void prep_input_requests_kernel(const float* lat, const float* img, const float* cond, int cond_per_request,
+                                           const float* sigmas, int step, int requests, int cfg, int frames, long hw, int cpad, char* x) {
+#pragma clang fp contract(off)      // every product and sum rounds on its own: the result is the plain fp32 statement, bit for bit
+  const long total = (long)cfg * requests * frames * hw;
+  const float sg = sigmas[step];
+  const float c_in = 1.0f / sqrtf(sg * sg + 1.0f);
+  constexpr int ES = Elem<Tag>::ES;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long p = i % hw;
+    const long bf = i / hw;
+    const long f = bf % frames;
+    const long b = bf / frames;                 // c * requests + r
+    const long r = b % requests;
+    const float* lp = lat + ((r * frames + f) * 4) * hw + p;
+    const float* ip = img + ((b * frames + f) * 4) * hw + p;
+    char* o = x + i * cpad * ES;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      store1<Tag>(o + c * ES, lp[c * hw] * c_in);
+      store1<Tag>(o + (4 + c) * ES, ip[c * hw]);
+    }
+    int c0 = 8;
+    if (cond) {
+      const float* cp = cond + (((cond_per_request ? r : 0) * frames + f) * 4) * hw + p;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) store1<Tag>(o + (8 + c) * ES, cp[c * hw]);
+      c0 = 12;
+    }
+    for (int c = c0; c < cpad; ++c) store1<Tag>(o + c * ES, 0.f);
+  }
+}
+
+__global__ void cfg_euler_requests_kernel(const float* eps, long ld_eps, float* lat, const float* guidance, int guidance_per_request,
+                                          const float* sigmas, int step, int requests, int cfg, int frames, long hw, float image_guidance) {
+#pragma clang fp contract(off)
+  const long total = (long)requests * frames * hw;
+  const float sg = sigmas[step], sn = sigmas[step + 1];
+  const float c_out = -sg / sqrtf(sg * sg + 1.0f), c_skip = 1.0f / (sg * sg + 1.0f);
+  const long cls = (long)requests * frames * hw;            // token rows between two CFG classes of one request
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long p = i % hw;
+    const long rf = i / hw;                     // r * frames + f
+    const long f = rf % frames;
+    const long r = rf / frames;
+    const float g = guidance ? guidance[(guidance_per_request ? r * frames : 0) + f] : 1.0f;
+    const float* e = eps + (rf * hw + p) * ld_eps;          // class 0 of request r
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float v;
+      if (cfg == 3) {             // InstructPix2Pix order (reference :698-702): first-frame, cond, uncond
+        const float e1 = e[c];
+        const float cd = e[cls * ld_eps + c];
+        const float u = e[2 * cls * ld_eps + c];
+        v = u + g * (cd - u) + image_guidance * (cd - e1);
+      } else if (cfg == 2) {
+        const float u = e[c];
+        const float cd = e[cls * ld_eps + c];
+        v = u + g * (cd - u);
+      } else {
+        v = e[c];
+      }
+      float* xp = lat + (rf * 4 + c) * hw + p;
+      const float xv = *xp;
+      const float x0 = v * c_out + xv * c_skip;
+      *xp = xv + (xv - x0) / sg * (sn - sg);
+    }
+  }
+}
+
 // NCHW -> tokens through a 32x32 LDS transpose (coalesced both sides)
 template <typename Tag, bool SRC_F32>
 __global__ void nchw_to_tokens_kernel(const char* src, int c, int hw, char* dst, long ld_dst) {
@@ -512,6 +586,43 @@ extern "C" int tt_cfg3_euler_step(const float* eps, int32_t ld_eps, float* laten
   long blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, eps, ld_eps, latents, guidance, sigmas, step, 3, frames, h * w, image_guidance_scale);
   TT_CHECK_LAUNCH("tt_cfg3_euler_step");
+  return TT_OK;
+}
+
+extern "C" int tt_prep_model_input_requests(const float* latents, const float* image_latents, const float* cond, int32_t cond_per_request,
+                                            const float* sigmas, int32_t step, int32_t requests, int32_t cfg, int32_t frames, int32_t h,
+                                            int32_t w, int32_t cpad, void* x, int32_t dtype, tt_stream_t stream) {
+  if (!latents || !image_latents || !sigmas || !x) TT_FAIL(TT_EINVAL, "tt_prep_model_input_requests: null operand");
+  if (requests <= 0 || cfg < 1 || cfg > 3 || frames <= 0 || h <= 0 || w <= 0 || step < 0)
+    TT_FAIL(TT_EINVAL, "tt_prep_model_input_requests: requests/cfg/frames/h/w (cfg is 1, 2 or 3)");
+  if (cpad < (cond ? 12 : 8) || (cpad & 7)) TT_FAIL(TT_EINVAL, "tt_prep_model_input_requests: cpad");
+  if (cond_per_request != 0 && cond_per_request != 1) TT_FAIL(TT_EINVAL, "tt_prep_model_input_requests: cond_per_request is 0 or 1");
+  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_prep_model_input_requests: bad dtype");
+  const long hw = (long)h * w;
+  const long total = (long)cfg * requests * frames * hw;
+  long blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == TT_BF16) hipLaunchKernelGGL(prep_input_requests_kernel<bf16_tag>, dim3((unsigned)blocks), dim3(256), 0, st, latents, image_latents, cond, cond_per_request, sigmas, step, requests, cfg, frames, hw, cpad, (char*)x);
+  else if (dtype == TT_F16) hipLaunchKernelGGL(prep_input_requests_kernel<f16_tag>, dim3((unsigned)blocks), dim3(256), 0, st, latents, image_latents, cond, cond_per_request, sigmas, step, requests, cfg, frames, hw, cpad, (char*)x);
+  else hipLaunchKernelGGL(prep_input_requests_kernel<f32_tag>, dim3((unsigned)blocks), dim3(256), 0, st, latents, image_latents, cond, cond_per_request, sigmas, step, requests, cfg, frames, hw, cpad, (char*)x);
+  TT_CHECK_LAUNCH("tt_prep_model_input_requests");
+  return TT_OK;
+}
+
+extern "C" int tt_cfg_euler_step_requests(const float* eps, int64_t ld_eps, float* latents, const float* guidance, int32_t guidance_per_request,
+                                          float image_guidance_scale, const float* sigmas, int32_t step, int32_t requests, int32_t cfg,
+                                          int32_t frames, int32_t h, int32_t w, tt_stream_t stream) {
+  if (!eps || !latents || !sigmas) TT_FAIL(TT_EINVAL, "tt_cfg_euler_step_requests: null operand");
+  if (requests <= 0 || cfg < 1 || cfg > 3 || frames <= 0 || h <= 0 || w <= 0 || ld_eps < 4 || step < 0)
+    TT_FAIL(TT_EINVAL, "tt_cfg_euler_step_requests: requests/cfg/frames/h/w/ld_eps (cfg is 1, 2 or 3)");
+  if (cfg == 3 && !guidance) TT_FAIL(TT_EINVAL, "tt_cfg_euler_step_requests: cfg 3 (use_instructpix2pix) needs guidance");
+  if (guidance_per_request != 0 && guidance_per_request != 1) TT_FAIL(TT_EINVAL, "tt_cfg_euler_step_requests: guidance_per_request is 0 or 1");
+  const long hw = (long)h * w;
+  const long total = (long)requests * frames * hw;
+  long blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(cfg_euler_requests_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, eps, (long)ld_eps, latents, guidance,
+                     guidance_per_request, sigmas, step, requests, cfg, frames, hw, image_guidance_scale);
+  TT_CHECK_LAUNCH("tt_cfg_euler_step_requests");
   return TT_OK;
 }
 

@@ -513,6 +513,40 @@ def cfg_euler_step(eps, latents, guidance, sigmas, step, batch, frames, h, w, im
     return latents
 
 
+def prep_model_input_requests(latents, image_latents, cond, sigmas, step, requests, cfg, frames, h, w, cpad, dtype):
+    """R requests in one launch: latents fp32 [R,F,4,h,w], image_latents fp32 [R*C,F,4,h,w] in the reference's (CFG-major) order,
+    cond None, fp32 [F,4,h,w] (shared by all requests) or [R,F,4,h,w] -> token rows [R*C*F*h*w, cpad], batch element c * R + r."""
+    lib = _lib.load()
+    per_request = 0
+    if cond is not None:
+        if cond.numel() not in (frames * 4 * h * w, requests * frames * 4 * h * w):
+            raise ValueError(f"prep_model_input_requests: cond holds {cond.numel()} elements, expected [F,4,h,w] or [R,F,4,h,w] "
+                             f"with R = {requests}, F = {frames}, h = {h}, w = {w}")
+        per_request = int(requests > 1 and cond.numel() == requests * frames * 4 * h * w)
+    x = torch.empty((requests * cfg * frames * h * w, cpad), dtype=dtype, device=latents.device)
+    check(lib.tt_prep_model_input_requests(_p(latents), _p(image_latents), _p(cond), per_request, _p(sigmas), step, requests, cfg,
+                                           frames, h, w, cpad, _p(x), _code(dtype), _stream()), "tt_prep_model_input_requests")
+    return x
+
+
+def cfg_euler_step_requests(eps, latents, guidance, sigmas, step, requests, cfg, frames, h, w, image_guidance_scale=None):
+    """R requests in one launch: eps fp32 token rows of batch element c * R + r, latents fp32 [R,F,4,h,w] (updated in place),
+    guidance None (cfg 1), fp32 [F] / [1,F] for all requests or [R,F]; cfg 3 is use_instructpix2pix and needs image_guidance_scale."""
+    lib = _lib.load()
+    if cfg == 3 and (image_guidance_scale is None or guidance is None):
+        raise ValueError("a CFG batch of 3 needs guidance and image_guidance_scale")
+    per_request = 0
+    if guidance is not None:
+        if guidance.numel() not in (frames, requests * frames):
+            raise ValueError(f"cfg_euler_step_requests: guidance holds {guidance.numel()} values, expected [1,F] or [R,F] with "
+                             f"R = {requests}, F = {frames}")
+        per_request = int(requests > 1 and guidance.numel() == requests * frames)
+    check(lib.tt_cfg_euler_step_requests(_p(eps), eps.stride(0), _p(latents), _p(guidance), per_request,
+                                         float(image_guidance_scale) if cfg == 3 else 0.0, _p(sigmas), step, requests, cfg, frames, h, w,
+                                         _stream()), "tt_cfg_euler_step_requests")
+    return latents
+
+
 def nchw_to_tokens(src, dtype, ld=None, out=None):
     """[N,C,H,W] contiguous (fp32 or `dtype`) -> token-major `dtype` [N*H*W, ld>=C] (extra columns zero), or into
     ``out`` (a [N*H*W, C] column window of a wider token buffer)."""

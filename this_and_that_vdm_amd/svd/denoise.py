@@ -27,6 +27,11 @@ from .layers import Geom
 
 FILM_TABLE = os.environ.get("TT_FILM_TABLE", "1") != "0"
 
+# Most batch elements (requests x CFG batch) one loop can carry.  The time / FiLM rows of a step are one tt_small_linear launch of one row
+# per batch element, and that kernel takes at most 32 rows; nothing else in the step is bounded by the batch before this is (the GEMM,
+# GroupNorm and attention launches index rows in 64 bits or refuse sizes beyond 2 GiB themselves).  32 allows 16 requests with CFG 2.
+MAX_BATCH = 32
+
 
 class DenoiseLoop:
     def __init__(self, unet, controlnet=None, use_graph: bool = True, split_cfg: bool = False):
@@ -47,39 +52,59 @@ class DenoiseLoop:
               timesteps: torch.Tensor, controlnet_cond: Optional[torch.Tensor] = None, conditioning_scale: float = 1.0,
               controlnet_keep: Optional[Sequence[float]] = None, image_guidance_scale: Optional[float] = None,
               guess_mode: bool = False):
-        """latents [1,F,4,h,w] (already scaled by init_noise_sigma); image_latents [B,F,4,h,w]; encoder_hidden_states
-        [B,S,D]; added_time_ids [B,3]; guidance_scale [1,F,1,1,1] or None (no CFG: B == 1); sigmas [steps+1],
-        timesteps [steps]; controlnet_cond [F,4,h,w] gesture latents (same for both CFG halves, reference :660); controlnet_keep: one 0.0/1.0 per step
-        (reference :611-617), None = keep everywhere.  B == 3 is the use_instructpix2pix batch (first-frame, cond, uncond; reference
-        :182-184,208-210,698-702) and needs image_guidance_scale.  guess_mode: the 13 residual scales become
+        """latents [R,F,4,h,w] (already scaled by init_noise_sigma), R independent requests; image_latents [B,F,4,h,w], B = R*C;
+        encoder_hidden_states [B,S,D]; added_time_ids [B,3]; guidance_scale [R,F,1,1,1] or [1,F,1,1,1] (all requests), None = no
+        CFG (C == 1); sigmas [steps+1], timesteps [steps] (shared by the requests); controlnet_cond gesture latents [F,4,h,w] (all
+        requests; the same for every CFG class, reference :660) or [R,F,4,h,w]; controlnet_keep: one 0.0/1.0 per step
+        (reference :611-617), None = keep everywhere.  C == 3 is the use_instructpix2pix batch (first-frame, cond, uncond; reference
+        :182-184,208-210,698-702) and needs image_guidance_scale.  The batched tensors are in the reference's order, the one
+        torch.cat([neg, cond]) gives a batch: CFG class by CFG class, element c * R + r -- which is the loop's internal order too.
+        Every request is computed as a begin() of its own would (never the reference's cross-request context pairing).
+        guess_mode: the 13 residual scales become
         logspace(-1, 0, 13) * conditioning_scale (temporal_controlnet.py:626-630); only without CFG -- the reference's
         guess-mode + CFG branch (:676-681) concatenates zeros onto an already CFG-sized residual batch and cannot run."""
         dev = self.unet.device
-        self.unet.prepare()
         b = image_latents.shape[0]
-        _, f, _, h, w = latents.shape
-        if b not in (1, 2, 3):
-            raise ValueError("CFG batch must be 1 (no CFG), 2 (uncond, cond) or 3 (use_instructpix2pix)")
-        if b == 3 and (image_guidance_scale is None or guidance_scale is None):
+        nr, f, _, h, w = latents.shape
+        if b > MAX_BATCH:
+            raise ValueError(f"{b} batch elements (requests x CFG batch) in one call; the cap is {MAX_BATCH} "
+                             "(the step's time / FiLM rows are one tt_small_linear launch of at most 32 rows)")
+        if nr < 1 or b % nr or b // nr not in (1, 2, 3):
+            raise ValueError(f"CFG batch must be 1 (no CFG), 2 (uncond, cond) or 3 (use_instructpix2pix): got {b} image-latent "
+                             f"batch elements for {nr} request(s)")
+        c = b // nr
+        if encoder_hidden_states.shape[0] != b or added_time_ids.shape[0] != b:
+            raise ValueError(f"encoder_hidden_states ({encoder_hidden_states.shape[0]}) and added_time_ids ({added_time_ids.shape[0]}) "
+                             f"need one row block per batch element ({b} = {nr} request(s) x CFG batch {c})")
+        if c == 3 and (image_guidance_scale is None or guidance_scale is None):
             raise ValueError("a CFG batch of 3 (use_instructpix2pix) needs guidance_scale and image_guidance_scale")
-        self.image_guidance_scale = float(image_guidance_scale) if b == 3 else None
+        if guidance_scale is not None and guidance_scale.numel() not in (f, nr * f):
+            raise ValueError(f"guidance_scale holds {guidance_scale.numel()} values: expected [1,F,1,1,1] or [R,F,1,1,1] with "
+                             f"R = {nr}, F = {f}")
+        if controlnet_cond is not None and controlnet_cond.numel() not in (f * 4 * h * w, nr * f * 4 * h * w):
+            raise ValueError(f"controlnet_cond {tuple(controlnet_cond.shape)}: expected [F,4,h,w] or [R,F,4,h,w] with R = {nr}, "
+                             f"F = {f}, h = {h}, w = {w}")
+        if nr > 1 and self.split_cfg:
+            raise NotImplementedError("split_cfg with several requests per call (the option was measured slower; use split_cfg=False)")
+        self.unet.prepare()
+        self.image_guidance_scale = float(image_guidance_scale) if c == 3 else None
         dtype = self.unet._run_dtype()
         if self.controlnet is not None:
             self.controlnet.prepare()
         # a captured graph holds raw pointers into the models' packed weights: the pack generation of both models is part
         # of the key, so load_state_dict / .to() / in-place updates between requests drop the stale graphs
         packs = self._pack_state()
-        key = (b, f, h, w, dtype, self.controlnet is not None, tuple(encoder_hidden_states.shape), len(timesteps),
+        key = (nr, b, f, h, w, dtype, self.controlnet is not None, tuple(encoder_hidden_states.shape), len(timesteps),
                guidance_scale is not None, self.image_guidance_scale, packs,   # the image scale is baked into the graph
                ops.f32_split())                                                # ... and so is the TT_F32 product mode (kernel variants)
         if key != self._key:                    # new shapes or new weights: new static buffers, new graph
             self._graph, self._graph_off, self._key, self._static = None, None, key, {}
         self._packs = packs                     # what the FiLM table, the context projections and the graphs below were built from
-        self.geom, self.dtype = Geom(b, f, h, w), dtype
+        self.geom, self.dtype = Geom(b, f, h, w, requests=nr), dtype
         f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
         sig = f32(sigmas)
         # static buffers: a captured graph keeps raw pointers, so later requests are COPIED into the same storage
-        self.latents = self._static_set("latents", f32(latents).reshape(f, 4, h, w))
+        self.latents = self._static_set("latents", f32(latents).reshape(f, 4, h, w) if nr == 1 else f32(latents))
         self.image_latents = self._static_set("image_latents", f32(image_latents))
         self.added_time_ids = self._static_set("added_time_ids", f32(added_time_ids))
         self.guidance = self._static_set("guidance", f32(guidance_scale).reshape(-1)) if guidance_scale is not None else None
@@ -96,16 +121,17 @@ class DenoiseLoop:
             self._graph = self._graph_off = None        # which rows skip cross-attention is part of the launch structure
             self._static["zero_ctx_mask"] = zmask
         self.ctx_unet = (self._static_set("k_unet", k), self._static_set("vt_unet", vt), s, sp, zmask)
-        self.cond = None
+        self.req_unet = self._request_major("unet", self.ctx_unet, nr, c)
+        self.cond = self.req_cn = None
         if self.controlnet is not None:
-            if guess_mode and b > 1:
+            if guess_mode and c > 1:
                 raise NotImplementedError("guess_mode with CFG (the reference's branch :676-681 cannot run either)")
             if controlnet_cond is None:
                 raise ValueError("controlnet_cond (VAE-encoded gesture latents) is required with a ControlNet")
             self.controlnet.prepare()
             if self.controlnet._run_dtype() != self.dtype:
                 raise RuntimeError("UNet and ControlNet must run in the same 16-bit dtype inside the fused loop")
-            self.cond = self._static_set("cond", f32(controlnet_cond).reshape(f, 4, h, w))
+            self.cond = self._static_set("cond", f32(controlnet_cond).reshape(-1, 4, h, w))
             if FILM_TABLE:
                 self.film_tab_c = self._static_set("film_tab_c", self.controlnet.film_table(self.table[:, 2], self.added_time_ids, b))
                 self.film_cur_c = self._static_set("film_cur_c", self.film_tab_c[0])
@@ -114,6 +140,7 @@ class DenoiseLoop:
                 self._graph = self._graph_off = None
                 self._static["zero_ctx_mask_cn"] = zmask_cn
             self.ctx_cn = (self._static_set("k_cn", k), self._static_set("vt_cn", vt), s, sp, zmask_cn)
+            self.req_cn = self._request_major("cn", self.ctx_cn, nr, c)
             self.cn_scales = self.controlnet._scales(float(conditioning_scale), bool(guess_mode), len(self.controlnet.controlnet_down_blocks))
             if self._static.setdefault("cn_scales", self.cn_scales) != self.cn_scales:
                 self._graph = None              # the scale is a launch argument baked into the graph
@@ -139,6 +166,16 @@ class DenoiseLoop:
             st += (id(m), m._pack_gen if fresh else -1, bool(m.attention_fp8))
         return st
 
+    def _request_major(self, name: str, ctx, nr: int, c: int):
+        """(K, V^T) with the contexts re-ordered request by request (r * C + c) for the temporal cross-attention's per-request
+        launches; None where the loop's own order serves (one request, or no CFG)."""
+        if nr == 1 or c == 1:
+            return None
+        k, vt, _, sp, _ = ctx
+        k_req = k.view(c, nr, sp, -1).transpose(0, 1).reshape(k.shape)
+        vt_req = vt.view(-1, c, nr, sp).transpose(1, 2).reshape(vt.shape)
+        return (self._static_set("k_req_" + name, k_req), self._static_set("vt_req_" + name, vt_req))
+
     def _static_set(self, name: str, value: torch.Tensor) -> torch.Tensor:
         cur = self._static.get(name)
         if cur is not None and cur.shape == value.shape and cur.dtype == value.dtype:
@@ -160,20 +197,25 @@ class DenoiseLoop:
         from . import layers as _layers
         _layers._Side.origin = torch.cuda.current_stream().cuda_stream     # the only stream that may fork side launches under capture
         cpad = cn._cin_pad if cn is not None else self.unet._cin_pad
-        x_tok = ops.prep_model_input(self.latents, self.image_latents, self.cond if use_cn else None, self.cur, 0, g.batch, g.frames, g.h, g.w,
-                                     cpad, self.dtype)
+        if g.requests == 1:
+            x_tok = ops.prep_model_input(self.latents, self.image_latents, self.cond if use_cn else None, self.cur, 0, g.batch, g.frames, g.h, g.w,
+                                         cpad, self.dtype)
+        else:
+            x_tok = ops.prep_model_input_requests(self.latents, self.image_latents, self.cond if use_cn else None, self.cur, 0, g.requests,
+                                                  g.cfg, g.frames, g.h, g.w, cpad, self.dtype)
         t = self.cur[2:3]
         x_unet = x_tok if cpad == self.unet._cin_pad else x_tok[:, :self.unet._cin_pad]
         if self.film_cur_u is not None:         # this step's rows of the per-request FiLM table (copied in by step())
-            ctx_u = self.unet._step_context(None, self.ctx_unet, film=self.film_cur_u)
+            ctx_u = self.unet._step_context(None, self.ctx_unet, film=self.film_cur_u, request_ctx=self.req_unet)
         else:
-            ctx_u = self.unet._step_context(self.unet._embed(t, self.added_time_ids, g.batch, x_tok.device), self.ctx_unet)
+            ctx_u = self.unet._step_context(self.unet._embed(t, self.added_time_ids, g.batch, x_tok.device), self.ctx_unet,
+                                            request_ctx=self.req_unet)
         ctx_c = None
         if cn is not None:
             if self.film_cur_c is not None:
-                ctx_c = cn._step_context(None, self.ctx_cn, film=self.film_cur_c)
+                ctx_c = cn._step_context(None, self.ctx_cn, film=self.film_cur_c, request_ctx=self.req_cn)
             else:
-                ctx_c = cn._step_context(cn._embed(t, self.added_time_ids, g.batch, x_tok.device), self.ctx_cn)
+                ctx_c = cn._step_context(cn._embed(t, self.added_time_ids, g.batch, x_tok.device), self.ctx_cn, request_ctx=self.req_cn)
         eps = torch.empty((g.m, self.unet.conv_out.out_channels), dtype=torch.float32, device=x_tok.device)
         halves = [Geom(1, g.frames, g.h, g.w, b, g.batch) for b in range(g.batch)] if self.split_cfg and g.batch > 1 else [g]
         rows = halves[0].m
@@ -206,8 +248,12 @@ class DenoiseLoop:
                     tails.append(done)
         for ev in tails:
             main.wait_event(ev)
-        ops.cfg_euler_step(eps, self.latents, self.guidance, self.cur, 0, g.batch, g.frames, g.h, g.w,
-                           self.image_guidance_scale)
+        if g.requests == 1:
+            ops.cfg_euler_step(eps, self.latents, self.guidance, self.cur, 0, g.batch, g.frames, g.h, g.w,
+                               self.image_guidance_scale)
+        else:
+            ops.cfg_euler_step_requests(eps, self.latents, self.guidance, self.cur, 0, g.requests, g.cfg, g.frames, g.h, g.w,
+                                        self.image_guidance_scale)
 
     def _stream(self, name):
         if not self.overlap_branches:
@@ -266,4 +312,4 @@ class DenoiseLoop:
 
     def result(self) -> torch.Tensor:
         g = self.geom
-        return self.latents.view(1, g.frames, 4, g.h, g.w)
+        return self.latents.view(g.requests, g.frames, 4, g.h, g.w)

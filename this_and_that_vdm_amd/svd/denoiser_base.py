@@ -194,12 +194,16 @@ class DenoiserBase(ModelMixin):
             zero_mask = sum(1 << i for i, z in enumerate(flags) if z)
         return (k_all, vt_all, s, sp, zero_mask)
 
-    def _step_context(self, emb: Optional[torch.Tensor], context, film: Optional[torch.Tensor] = None) -> StepContext:
-        """``film``: this step's FiLM rows when the caller holds them already (DenoiseLoop: one row block of film_table)."""
+    def _step_context(self, emb: Optional[torch.Tensor], context, film: Optional[torch.Tensor] = None, request_ctx=None) -> StepContext:
+        """``film``: this step's FiLM rows when the caller holds them already (DenoiseLoop: one row block of film_table).
+        ``request_ctx``: (K, V^T) with the contexts in request-major order, for a launch that holds several requests with CFG."""
         if film is None:
             film = ops.small_linear(emb, self._film_w, self._film_b, act_in=True)     # every ResBlock's FiLM row at once
         k_all, vt_all, s, sp, zero_mask = context
-        return StepContext(film, k_all, vt_all, s, sp, attn_fp8=bool(self.attention_fp8), zero_mask=zero_mask)
+        sc = StepContext(film, k_all, vt_all, s, sp, attn_fp8=bool(self.attention_fp8), zero_mask=zero_mask)
+        if request_ctx is not None:
+            sc.k_req, sc.vt_req = request_ctx
+        return sc
 
     # ---- encoder walk shared by both models
     def _encode(self, x, g: Geom, ctx: StepContext):
@@ -208,6 +212,37 @@ class DenoiserBase(ModelMixin):
             x, g, outs = blk(x, g, ctx)
             skips.extend(outs)
         return x, g, skips
+
+    # ---- the reference models' off-path methods (unet_spatio_temporal_condition.py:254-361): this is an inference-only build whose
+    # attention is the library's kernels, so there are no processor objects to hand out or swap.  A method is a no-op where a
+    # no-op is exact, an explicit NotImplementedError otherwise -- never an AttributeError in the middle of a caller's set-up.
+    _INFERENCE_ONLY = ("{}: inference-only build -- attention runs on the library's HIP kernels (tt_attention), there are no "
+                       "AttentionProcessor objects to read or replace")
+
+    @property
+    def attn_processors(self):
+        raise NotImplementedError(self._INFERENCE_ONLY.format(f"{type(self).__name__}.attn_processors"))
+
+    def set_attn_processor(self, processor):
+        raise NotImplementedError(self._INFERENCE_ONLY.format(f"{type(self).__name__}.set_attn_processor"))
+
+    def set_default_attn_processor(self):
+        """No-op: the default processor (plain softmax attention) is what the kernels compute; no other one can have been set."""
+
+    def _set_gradient_checkpointing(self, module, value=False):
+        """As the reference (:329-331): sets ``module.gradient_checkpointing`` where a module has it.  No module of this build does
+        and nothing reads the flag -- checkpointing changes what a backward pass stores, never a forward result."""
+        if hasattr(module, "gradient_checkpointing"):
+            module.gradient_checkpointing = value
+
+    def enable_forward_chunking(self, chunk_size: Optional[int] = None, dim: int = 0) -> None:
+        """No-op after the reference's argument check (:347-348): feed-forward chunking splits a row-wise computation to save memory
+        and does not change its result; the feed-forwards here are two GEMM launches whose 8C intermediate never exists."""
+        if dim not in [0, 1]:
+            raise ValueError(f"Make sure to set `dim` to either 0 or 1, not {dim}")
+
+    def disable_forward_chunking(self) -> None:
+        """No-op (see enable_forward_chunking)."""
 
     def _apply(self, fn, *a, **k):
         self._packed_key = None

@@ -35,6 +35,7 @@ class Geom:
     w: int
     batch0: int = 0          # index of its first batch element inside the request ...
     batch_total: int = 0     # ... and the request's full batch (0 = same as `batch`): the fused loop runs CFG halves apart
+    requests: int = 1        # independent requests sharing the launches: batch element c * requests + r
 
     @property
     def n(self):
@@ -52,6 +53,11 @@ class Geom:
     def ctx_batches(self):
         return self.batch_total or self.batch
 
+    @property
+    def cfg(self):
+        """CFG batch of ONE request: the modulus of the temporal cross-attention's context pairing (quirk Q3)."""
+        return self.ctx_batches // self.requests
+
     def film(self, film: torch.Tensor, off: int, c: int) -> torch.Tensor:
         """FiLM rows of this launch's batch elements, columns [off, off+c)."""
         return film[self.batch0:self.batch0 + self.batch, off:off + c]
@@ -66,6 +72,9 @@ class StepContext:
         self.film, self.k_all, self.vt_all, self.s_ctx, self.s_pad = film, k_all, vt_all, s_ctx, s_pad
         self.attn_fp8 = attn_fp8            # spatial self-attention on e4m3 operands (BASELINE config 5)
         self.zero_mask = zero_mask          # bit b: the context of batch element b is all zeros (denoiser_base.project_context)
+        # several requests with CFG (DenoiseLoop): the same K / V^T with every request's contexts side by side (request-major), for
+        # the per-request launches of the temporal cross-attention's general path (_temporal_cross_requests)
+        self.k_req = self.vt_req = None
 
     def live_batches(self, g: "Geom"):
         """Which batch elements of launch `g` need real cross-attention.  None: all of them (general path).  Otherwise
@@ -86,11 +95,13 @@ class StepContext:
         context (b*hw + p) % CB.  When hw is a multiple of CB that is p % CB = (token row) % CB for every row of the launch: the
         rows of residue class c all use context c.  Returns None when every context is live (or the classes do not align with
         the rows): general path.  Otherwise the list of classes whose context is NOT all-zero; the rows of the other classes
-        get exactly 0 from the attention (K = V = 0) and therefore only to_out's bias."""
-        cb = g.ctx_batches
+        get exactly 0 from the attention (K = V = 0) and therefore only to_out's bias.
+        With several requests in the launch (batch element c * R + r) the pairing holds per request: class c is skipped only when
+        the class-c context of EVERY request is all-zero (a live class computes a zero context like any other: exact as well)."""
+        cb, nr = g.cfg, g.requests
         if not self.zero_mask or cb < 2 or g.hw % cb or not ZERO_CTX_TEMPORAL:
             return None
-        live = [c for c in range(cb) if not (self.zero_mask >> c) & 1]
+        live = [c for c in range(cb) if not all((self.zero_mask >> (c * nr + r)) & 1 for r in range(nr))]
         return None if len(live) == cb else live
 
     _VT_CACHE: Dict[tuple, torch.Tensor] = {}
@@ -401,7 +412,7 @@ class Downsample2D(_Packable):
     def forward(self, x, g: Geom):
         ho, wo = (g.h + 2 - 3) // 2 + 1, (g.w + 2 - 3) // 2 + 1
         out = ops.gemm(x, self.w, mode=1, conv=(g.n, g.h, g.w, ho, wo, 2, 0), bias=self.b, stats=ho * wo)
-        return out, Geom(g.batch, g.frames, ho, wo, g.batch0, g.batch_total)
+        return out, Geom(g.batch, g.frames, ho, wo, g.batch0, g.batch_total, g.requests)
 
 
 class Upsample2D(_Packable):
@@ -418,7 +429,7 @@ class Upsample2D(_Packable):
     def forward(self, x, g: Geom):
         # nearest x2 is an index map inside the conv gather: never materialised
         out = ops.gemm(x, self.w, mode=1, conv=(g.n, g.h, g.w, 2 * g.h, 2 * g.w, 1, 1), bias=self.b, stats=4 * g.hw)
-        return out, Geom(g.batch, g.frames, 2 * g.h, 2 * g.w, g.batch0, g.batch_total)
+        return out, Geom(g.batch, g.frames, 2 * g.h, 2 * g.w, g.batch0, g.batch_total, g.requests)
 
 
 # --------------------------------------------------------------------------- attention / feed-forward
@@ -540,6 +551,31 @@ def _cross_attention(x, attn: Attention, qp: _QProj, eps, kv, g: Geom, ctx: Step
     return ops.attention(q, ctx.k_all[:, off:off + c], ctx.vt_all[off:off + c], out, **kw)
 
 
+def _temporal_cross_requests(x, attn: Attention, qp: _QProj, eps, kv, g: Geom, ctx: StepContext):
+    """Temporal cross-attention (mask 2, quirk Q3) of a launch that holds R > 1 requests with a CFG batch C > 1, general path: the
+    pairing (c * hw + p) % C must pick among the contexts of the query's OWN request, so every batch element b = c * R + r gets a
+    launch of its own (batch0 = c, ctx_batches = C) on request r's C contexts, which lie side by side in ctx.k_req / ctx.vt_req."""
+    off, c = kv
+    nr, cb, rows, csp = g.requests, g.cfg, g.frames * g.hw, g.cfg * ctx.s_pad
+    out = torch.empty((g.m, c), dtype=x.dtype, device=x.device)
+    kw = dict(nseq=g.frames, lq=g.hw, heads=attn.heads, head_dim=attn.dim_head, mask=2, lk=ctx.s_ctx, k_seq_stride=ctx.s_pad,
+              v_seq_stride=ctx.s_pad, frames=g.frames, ctx_batches=cb)
+    fused = qp.fused()
+    if fused is None or not ops.attention_qproj_supported(x, attn.dim_head, 2):
+        fused = None
+        wq, bq = qp.plain()
+        q = ops.gemm(x, wq, bias=bq, ln_fold=1, ln_eps=eps)
+    for b in range(g.batch):
+        cls, r = divmod(b, nr)
+        k, vt = ctx.k_req[r * csp:(r + 1) * csp, off:off + c], ctx.vt_req[off:off + c, r * csp:(r + 1) * csp]
+        sl = slice(b * rows, (b + 1) * rows)
+        if fused is not None:
+            ops.attention(None, k, vt, out[sl], qx=x[sl], wq=fused[0], bq=fused[1], ln_eps=eps, batch0=cls, **kw)
+        else:
+            ops.attention(q[sl], k, vt, out[sl], batch0=cls, **kw)
+    return out
+
+
 class BasicTransformerBlock(_Packable):
     """LN -> self-attn -> LN -> cross-attn -> LN -> GEGLU FF, residual after each (Appendix A.8)."""
 
@@ -610,7 +646,7 @@ class BasicTransformerBlock(_Packable):
         if count:
             rows = g.frames * g.hw
             xs = x[first * rows:(first + count) * rows]
-            gl = Geom(count, g.frames, g.h, g.w, g.batch0 + first, g.ctx_batches)
+            gl = Geom(count, g.frames, g.h, g.w, g.batch0 + first, g.ctx_batches, g.requests)
             a = _cross_attention(xs, self.attn2, self.q2, self.norm2.eps, self.kv, gl, ctx, temporal=False)
             ops.gemm(a, self.wo2, bias=self.bo2, residual=xs, out=xs)
         return self.ff(x, residual=x, **ff_rv)
@@ -681,7 +717,14 @@ class TemporalBasicTransformerBlock(_Packable):
         live = ctx.live_classes(g)
         if live is None:
             t = ops.gemm(a, self.wo1, bias=self.bo1, residual=t)
-            a = _cross_attention(t, self.attn2, self.q2, self.norm2.eps, self.kv, g, ctx, temporal=True)
+            if g.requests == 1:
+                a = _cross_attention(t, self.attn2, self.q2, self.norm2.eps, self.kv, g, ctx, temporal=True)
+            elif g.cfg == 1:
+                # several requests without CFG: (b * hw + p) % 1 = 0, every query sees its own request's one context -- which is what the
+                # spatial pairing (context of batch element seq / frames) selects
+                a = _cross_attention(t, self.attn2, self.q2, self.norm2.eps, self.kv, g, ctx, temporal=False)
+            else:
+                a = _temporal_cross_requests(t, self.attn2, self.q2, self.norm2.eps, self.kv, g, ctx)
             t = ops.gemm(a, self.wo2, bias=self.bo2, residual=t)
         else:
             # Rows of a residue class whose context is all zeros (the CFG uncond context: every other pixel, quirk Q3) get
@@ -689,7 +732,7 @@ class TemporalBasicTransformerBlock(_Packable):
             # run on the live classes alone, as strided row views t[c::CB] (row stride CB*C; the GEMM and the attention take
             # row strides, the output projection writes in place over its residual).  Exact.  The dead classes' "+ bias" rides
             # on the self-attention output projection as a per-class (periodic) row vector: no separate pass over half of the rows.
-            cb, off, cc = g.ctx_batches, self.kv[0], self.kv[1]
+            cb, off, cc = g.cfg, self.kv[0], self.kv[1]
             # the self-attention's output projection for ALL classes in one launch: the dead classes' extra bias (the cross-attention's
             # to_out bias bo2) is a periodic row vector -- row r takes class_rows[r % cb] (tt_gemm rowvec_mod; cb = 2: even / odd rows)
             t = ops.gemm(a, self.wo1, bias=self.bo1, residual=t, rowvec=self._class_rows(live, cb), rowvec_rows=1, rowvec_mod=cb)
@@ -702,14 +745,26 @@ class TemporalBasicTransformerBlock(_Packable):
                     if MERGE_FRAMES:                         # ... i.e. ONE sequence of all the class's rows: full 128-query blocks (an image has
                         akw.update(nseq=1, lq=g.n * (g.hw // cb), frames=1)      # 56 / 14 rows of a class at the two coarsest levels)
                     a = torch.empty((tv.shape[0], c), dtype=tv.dtype, device=tv.device)
+                    parts = [slice(None)]
+                    if g.requests > 1:
+                        # R requests: the class's rows come CFG class by CFG class (batch element c * R + r), and every one of them uses
+                        # context `cls` of its OWN request, element cls * R + r of the context batch: one launch per CFG class, R
+                        # sequences each (mask 1: context batch0 + sequence)
+                        nr, per = g.requests, g.requests * g.frames * (g.hw // cb)
+                        akw.update(nseq=nr * g.frames, lq=g.hw // cb, frames=g.frames, ctx_batches=nr * cb, batch0=cls * nr)
+                        if MERGE_FRAMES:
+                            akw.update(nseq=nr, lq=g.frames * (g.hw // cb), frames=1)
+                        parts = [slice(i * per, (i + 1) * per) for i in range(cb)]
                     fused = self.q2.fused()
                     if fused is not None and ops.attention_qproj_supported(tv, self.attn2.dim_head, 1):
-                        ops.attention(None, ctx.k_all[:, off:off + cc], ctx.vt_all[off:off + cc], a, qx=tv, wq=fused[0],
-                                      bq=fused[1], ln_eps=self.norm2.eps, **akw)
+                        for sl in parts:
+                            ops.attention(None, ctx.k_all[:, off:off + cc], ctx.vt_all[off:off + cc], a[sl], qx=tv[sl], wq=fused[0],
+                                          bq=fused[1], ln_eps=self.norm2.eps, **akw)
                     else:
                         wq2, bq2 = self.q2.plain()
                         q = ops.gemm(tv, wq2, bias=bq2, ln_fold=1, ln_eps=self.norm2.eps)
-                        ops.attention(q, ctx.k_all[:, off:off + cc], ctx.vt_all[off:off + cc], a, **akw)
+                        for sl in parts:
+                            ops.attention(q[sl], ctx.k_all[:, off:off + cc], ctx.vt_all[off:off + cc], a[sl], **akw)
                     ops.gemm(a, self.wo2, bias=self.bo2, residual=tv, out=tv)
         if blend_fix is not None:
             return self.ff(t, residual=t, blend=xs, alpha=alpha, rowvec=blend_fix, rowvec_rows=g.hw)

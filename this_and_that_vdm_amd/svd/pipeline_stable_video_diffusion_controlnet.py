@@ -5,7 +5,8 @@ hipGraph-replayed DenoiseLoop (svd/denoise.py).
 Kept: the ``__call__`` surface and argument meaning, CLIP(+text) context with the freshly constructed
 LayerNorm((78,1024)) (reference :165-173), un-scaled VAE ``.mode()`` latents (:200), CFG order [uncond, cond]
 (:177-185,203-211), fps-1 / motion bucket / noise-aug time ids, per-frame guidance ramp, ``output_type="latent"``,
-``latents=``, ``generator=``, ``callback_on_step_end``.
+``latents=``, ``generator=``, ``callback_on_step_end``, a list of images and ``num_videos_per_prompt`` (one call carries
+R = images x videos-per-image independent requests, image-major; every video is what a call of its own would give -- DESIGN.md section 8).
 Opt-in (``native_image_io=True``, default off): the CLIP image preprocessing, the use_text context LayerNorm and the export of decoded
 frames run on the library's kernels (ops.clip_image / layernorm_block / frames_out) instead of stock torch ops.
 ``use_instructpix2pix`` (CFG batch of 3, reference :182-184,208-210,698-702) and ``guess_mode`` without CFG are built;
@@ -104,6 +105,15 @@ class _SVDPipelineCore(PipelineBase):
         ehs = emb.repeat(1, num_videos_per_prompt, 1).view(bs * num_videos_per_prompt, seq, -1)
         if use_text:
             text = text_encoder(prompt)[0]
+            if bs * num_videos_per_prompt != 1:
+                # one row of ids per image (repeated for its videos, like the image embedding above), or one row for all requests
+                if text.shape[0] == bs:
+                    text = text.repeat_interleave(num_videos_per_prompt, 0)
+                elif text.shape[0] == 1:
+                    text = text.expand(bs * num_videos_per_prompt, -1, -1)
+                else:
+                    raise ValueError(f"prompt: {text.shape[0]} rows of token ids for {bs} image(s); pass one row per image or one row "
+                                     "for all")
             ehs = torch.cat((text, ehs), dim=1)
             if native:
                 ehs = ops.layernorm_block(ehs.reshape(-1, ehs.shape[-1]), ehs.shape[1], eps=1e-5).view(ehs.shape)
@@ -151,14 +161,17 @@ class _SVDPipelineCore(PipelineBase):
         return torch.cat([t, t, t]) if use_instructpix2pix else torch.cat([t, t])
 
     def _decode_chunks(self, latents, decode_chunk_size):
-        """the decoder's ``.sample`` [f, 3, H, W] for every chunk of at most decode_chunk_size frames (reference :257-283)"""
+        """the decoder's ``.sample`` [f, 3, H, W] for every chunk of at most decode_chunk_size frames (reference :257-283), video by
+        video: a chunk never spans two videos (the reference chunks flatten(0, 1); the temporal decoder mixes the frames of a
+        chunk, so a video of a batched call would otherwise depend on its neighbour)"""
         import inspect
-        lat = latents.flatten(0, 1) / self.vae.config.scaling_factor
         takes_frames = "num_frames" in inspect.signature(self.vae.forward).parameters
-        for i in range(0, lat.shape[0], decode_chunk_size):
-            chunk = lat[i:i + decode_chunk_size]
-            kw = {"num_frames": chunk.shape[0]} if takes_frames else {}
-            yield self.vae.decode(chunk, **kw).sample
+        for video in latents:
+            lat = video / self.vae.config.scaling_factor
+            for i in range(0, lat.shape[0], decode_chunk_size):
+                chunk = lat[i:i + decode_chunk_size]
+                kw = {"num_frames": chunk.shape[0]} if takes_frames else {}
+                yield self.vae.decode(chunk, **kw).sample
 
     def decode_latents(self, latents, num_frames, decode_chunk_size=14):
         frames = torch.cat(list(self._decode_chunks(latents, decode_chunk_size)), 0)
@@ -191,9 +204,20 @@ class _SVDPipelineCore(PipelineBase):
         return latents * self.scheduler.init_noise_sigma
 
     def prepare_condition_image(self, condition_img, device):
-        """[0,1] float gesture frames [F,3,H,W] -> fp16 on device (reference :363-364, quirk Q7)."""
+        """[0,1] float gesture frames [F,3,H,W] -> fp16 on device (reference :363-364, quirk Q7).  A list of such arrays, or one
+        [N,F,3,H,W] array, holds one gesture map per image."""
+        if isinstance(condition_img, (list, tuple)):
+            return torch.stack([self.prepare_condition_image(c, device) for c in condition_img], 0)
         t = torch.from_numpy(condition_img) if isinstance(condition_img, np.ndarray) else condition_img
         return t.to(torch.float16).to(device)
+
+    def _encode_gesture_maps(self, cond, num_videos_per_prompt):
+        """prepared gesture frames -> VAE latents: [F,3,H,W] -> [F,4,h,w] (shared by every request); one map per image
+        [N,F,3,H,W] -> [N * num_videos_per_prompt,F,4,h,w], each image's latents repeated for its videos.  ONE encode per call."""
+        lat = self.vae.encode(cond.reshape(-1, *cond.shape[-3:]).to(self.vae.dtype)).latent_dist.mode()
+        if cond.ndim == 5:
+            lat = lat.reshape(cond.shape[0], cond.shape[1], *lat.shape[1:]).repeat_interleave(num_videos_per_prompt, 0)
+        return lat
 
     @property
     def guidance_scale(self):
@@ -217,37 +241,59 @@ class _SVDPipelineCore(PipelineBase):
         decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else num_frames
         self.check_inputs(image, height, width)
         batch_size = 1 if isinstance(image, PIL.Image.Image) else (len(image) if isinstance(image, list) else image.shape[0])
-        if batch_size * num_videos_per_prompt != 1:
-            raise NotImplementedError("the fused loop serves one request per call (shard requests across GPUs/processes)")
+        nvid = 1 if num_videos_per_prompt is None else int(num_videos_per_prompt)
+        if batch_size < 1 or nvid < 1:
+            raise ValueError(f"need at least one image and one video per image, got {batch_size} image(s) x {nvid} video(s)")
+        nreq = batch_size * nvid             # independent requests of this call, image-major: request i * nvid + j = video j of image i
         device = self._execution_device
         do_cfg = max_guidance_scale > 1.0
 
         ip2p = bool(use_instructpix2pix) and do_cfg
-        ehs = self.encode_clip(image, prompt, use_text, text_encoder, device, num_videos_per_prompt, do_cfg, ip2p)
+        if isinstance(generator, (list, tuple)) and len(generator) != nreq:
+            raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective "
+                             f"batch size of {nreq} ({batch_size} image(s) x {nvid} video(s) per image). Make sure the batch size "
+                             "matches the length of the generators.")
+        lat_shape = (nreq, num_frames, self.unet.config.in_channels // 2, height // self.vae_scale_factor, width // self.vae_scale_factor)
+        if latents is not None and tuple(latents.shape) != lat_shape:
+            raise ValueError(f"latents {tuple(latents.shape)}: expected {lat_shape} = [{batch_size} image(s) x {nvid} video(s) per image, "
+                             "F, 4, h, w]")
+        cond = None
+        if controlnet is not None:
+            cond = self.prepare_condition_image(condition_img, device)
+            if cond.ndim not in (4, 5) or cond.shape[-4] != num_frames or (cond.ndim == 5 and cond.shape[0] != batch_size):
+                raise ValueError(f"condition_img {tuple(cond.shape)}: expected [F,3,H,W] (shared by every request) or one [F,3,H,W] map per "
+                                 f"image, [{batch_size},F,3,H,W], with F = {num_frames}")
+        ehs = self.encode_clip(image, prompt, use_text, text_encoder, device, nvid, do_cfg, ip2p)
+        if ehs.shape[0] != nreq * (1 if not do_cfg else 3 if ip2p else 2):
+            raise ValueError(f"encode_clip returned {ehs.shape[0]} contexts for {nreq} request(s)")
         fps = fps - 1                                                            # SVD was conditioned on fps-1 (:527)
         img = self.image_processor.preprocess(image, height=height, width=width)
+        if nvid > 1:
+            # every request noises its own copy of its image, as a call of its own would: generator r draws for request r.  (The reference
+            # noises once per image and then tiles cat([neg, lat]) with repeat (:211-214), which pairs videos with the wrong class.)
+            img = img.repeat_interleave(nvid, 0)
         img = img + noise_aug_strength * randn_tensor(img.shape, generator=generator, device=img.device, dtype=img.dtype)
         upcast = self.vae.dtype == torch.float16 and getattr(self.vae.config, "force_upcast", False)
         if upcast:
             self.vae.to(dtype=torch.float32)
-        image_latents = self._encode_vae_image(img.to(self.vae.dtype), device, num_videos_per_prompt, do_cfg, ip2p).to(ehs.dtype)
+        # one image per request already: the CFG classes are concatenated around the R latents (class by class, the loop's order)
+        image_latents = self._encode_vae_image(img.to(self.vae.dtype), device, 1, do_cfg, ip2p).to(ehs.dtype)
         image_latents = image_latents.unsqueeze(1).repeat(1, num_frames, 1, 1, 1)
         if upcast:
             self.vae.to(dtype=torch.float16)
         gesture_latents = None
         if controlnet is not None:
             # after the cast-back, in the VAE's own dtype: where (and in which precision) the reference encodes it (:652),
-            # but once per request instead of once per step (loop-invariant, quirk Q6)
-            cond = self.prepare_condition_image(condition_img, device)
-            gesture_latents = self.vae.encode(cond.to(self.vae.dtype)).latent_dist.mode()
+            # but once per request instead of once per step (loop-invariant, quirk Q6); one map per image: once per call
+            gesture_latents = self._encode_gesture_maps(cond, nvid)
         added_time_ids = self._get_add_time_ids(fps, motion_bucket_id, noise_aug_strength, ehs.dtype, batch_size,
-                                                num_videos_per_prompt, do_cfg, use_instructpix2pix=ip2p).to(device)
+                                                nvid, do_cfg, use_instructpix2pix=ip2p).to(device)
         self.scheduler.set_timesteps(num_inference_steps, device=device)
         timesteps = self.scheduler.timesteps
-        latents = self.prepare_latents(batch_size * num_videos_per_prompt, num_frames, self.unet.config.in_channels, height,
+        latents = self.prepare_latents(nreq, num_frames, self.unet.config.in_channels, height,
                                        width, ehs.dtype, device, generator, latents)
         guidance = torch.linspace(min_guidance_scale, max_guidance_scale, num_frames).unsqueeze(0).to(device, latents.dtype)
-        guidance = append_dims(guidance.repeat(batch_size * num_videos_per_prompt, 1), latents.ndim)
+        guidance = append_dims(guidance.repeat(nreq, 1), latents.ndim)
         self._guidance_scale = guidance
         self._num_timesteps = len(timesteps)
         scale = controlnet_conditioning_scale[0] if isinstance(controlnet_conditioning_scale, list) else controlnet_conditioning_scale
