@@ -30,10 +30,7 @@ void launch_sq320_bf16(const GemmP& p, hipStream_t st);
 void launch_sq320_f16(const GemmP& p, hipStream_t st);
 void launch_pp_bf16(GemmP& p, hipStream_t st);         // gemm_pp.hip: persistent 256 x 256 x 64 ping-pong kernel
 void launch_pp_f16(GemmP& p, hipStream_t st);
-void launch_w320_bf16(GemmP& p, hipStream_t st);       // gemm_w320.hip: 256 x 320 x 64 tiles for N = 320 t at the finest UNet level
-void launch_w320_f16(GemmP& p, hipStream_t st);
-void launch_w320h_bf16(GemmP& p, hipStream_t st);      // ... its 128-row variant (two K halves per slab) for problems with fewer rows
-void launch_w320h_f16(GemmP& p, hipStream_t st);
+void launch_w320(GemmP& p, hipStream_t st, int bm, bool bf16);      // gemm_w320.hip: 256 x 320 x 64 tiles for N = 320 t at the finest UNet level; bm = 128: the variant (two K halves per slab) for problems with fewer rows
 }
 using namespace ttg;
 
@@ -557,8 +554,8 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
   switch (r.kind) {
     case Kind::PP: if (bf16) launch_pp_bf16(p, st); else launch_pp_f16(p, st); break;
     case Kind::SQ320: if (bf16) launch_sq320_bf16(p, st); else launch_sq320_f16(p, st); break;
-    case Kind::W320: if (bf16) launch_w320_bf16(p, st); else launch_w320_f16(p, st); break;
-    case Kind::W320H: case Kind::W320H_SPLIT: if (bf16) launch_w320h_bf16(p, st); else launch_w320h_f16(p, st); break;
+    case Kind::W320: launch_w320(p, st, 256, bf16); break;
+    case Kind::W320H: case Kind::W320H_SPLIT: launch_w320(p, st, 128, bf16); break;
     case Kind::TILED:
       if (bf16) launch_bf16(p, r.cfg, st);
       else if (a->dtype == TT_F16) launch_f16(p, r.cfg, st);

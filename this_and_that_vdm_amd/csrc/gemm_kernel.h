@@ -230,6 +230,12 @@ __device__ __forceinline__ void epilogue_quad(const GemmP& p, int gm, int gn, fl
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// XCD-aware launch order: the dispatcher places block b on XCD b % 8; position `bid` of `n` is mapped so that every XCD gets a
+// contiguous run of the n tiles (same A rows, neighbouring W columns: its private L2 sees the reuse; guide T1, bijective form).
+__device__ __forceinline__ int xcd_remap(int bid, int n) {
+  const int q = n >> 3, r = n & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 // wait until at most `tiles` of the G-load groups issued last are still in flight (tiles <= 3)
 template <int G> __device__ __forceinline__ void wait_tiles(int tiles) {
   static_assert(3 * G <= 63, "vmcnt field is 6 bits");
@@ -293,14 +299,8 @@ void gemm_kernel(const GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // XCD-aware tile order: the dispatcher places block b on XCD b%8; give each XCD a contiguous run of
-  // tiles (same A rows, neighbouring W columns) so its private L2 sees the reuse (guide T1, bijective form).
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int split = 0;                                            // slices of one tile sit next to each other
+  int bid = xcd_remap(blockIdx.x, gridDim.x);
+  int split = 0;                                           // slices of one tile sit next to each other
   if (p.splitk > 1) { const int t = fdiv(bid, p.fd_splitk); split = bid - t * p.splitk; bid = t; }
   // Within an XCD's run the tiles go in groups of `group_m` tile rows, column by column inside a group: the ~64 workgroups
   // that are resident on an XCD at a time then cover group_m rows x 64/group_m columns, i.e. every K slice they fetch is

@@ -33,7 +33,6 @@
 
 namespace ttg {
 
-template <int N> __device__ __forceinline__ void pp_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void lds_write8_raw(unsigned addr, unsigned a, unsigned b) {
   const raw_u32x2_t v = {a, b};
   asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
@@ -65,9 +64,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmP p) {
   const int my_tiles = (int)blockIdx.x < ntiles ? (ntiles - 1 - (int)blockIdx.x) / nwg + 1 : 0;
   const int S = my_tiles * KS;
   auto tile_of = [&](int it, int& m0, int& n0) {
-    int bid = it * nwg + (int)blockIdx.x;
-    const int q = ntiles >> 3, r = ntiles & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int bid = xcd_remap(it * nwg + (int)blockIdx.x, ntiles);
     const int gm = p.group_m, per_group = gm * p.tiles_n;
     const int g = bid / per_group, first = g * gm, rows = min(gm, p.tiles_m - first), rem = bid - g * per_group;
     const int tn = rem / rows, tm = first + (rem - tn * rows);
@@ -212,11 +209,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmP p) {
   if constexpr (HALF) {
     stage(0, R0{}); stage(0, R2{}); stage(0, R3{});
     stage(1, R0{}); stage(1, R2{});
-    pp_wait_vm<4>();
+    wait_vmcnt<4>();
   } else {
   stage(0, R0{}); stage(0, R3{}); stage(0, R1{}); stage(0, R2{});
   stage(1, R0{}); stage(1, R3{}); stage(1, R1{});
-  pp_wait_vm<6>();
+  wait_vmcnt<6>();
   }
   bar();
   if (grp == 1) bar();                                       // group 1 runs one barrier behind group 0
@@ -392,7 +389,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmP p) {
       read_b(sb, 1);
       stage(slot, R0{}); stage(slot, R2{});
       stats(I0{});
-      pp_wait_vm<4>();
+      wait_vmcnt<4>();
       lds_wait<0>();
       bar();
       mma(I0{}, I1{});
@@ -434,7 +431,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmP p) {
     read_b(sb, 0);
     stage(slot, R1{});
     stats(I1{});
-    pp_wait_vm<6>();
+    wait_vmcnt<6>();
     lds_wait<0>();
     bar();
     mma(I1{}, I0{});
