@@ -509,6 +509,45 @@ int tt_layernorm_block(const void* x, int64_t ldx, int32_t nb, int32_t rows, int
 int tt_frames_out(const void* src, int32_t src_dtype, int32_t n, int32_t ch, int32_t h, int32_t w, int32_t kind, void* dst,
                   tt_stream_t stream);
 
+/* tt_gesture_maps: the "this"/"that" conditioning frames of a request, rasterised from the annotated points themselves -- the
+ * reference's get_thisthat_sam (data_loader/video_this_that_dataset.py:28-130, blur kernel utils/optical_flow_utils.py:197-219) as
+ * this_and_that_vdm_amd/gesture_map.py restates it.  The reference draws a 21 x 21 square on a white canvas of the ORIGINAL image
+ * size, blurs it (filter2D, 99 Gaussian taps, BORDER_REFLECT_101), resizes it (INTER_CUBIC) and divides by 255.  The canvas is
+ * 255 - (255 - colour) box with box an outer product of two 1-D indicators, and blur and resize are separable with rows that sum
+ * to 1, so every frame is rank 1:  1 - d_c ry[y] rx[x]  with two short profiles per point.
+ *
+ *   points   HOST pointer: npoints <= 64 records, copied into kernel arguments before the call returns (no device copy of them)
+ *            {map, frame, x, y, first}: the point (x horizontal, y vertical, original-image pixels, may lie outside the image)
+ *            decides frame `frame` of map `map`; first != 0 marks the "this" point (red), the others are green.
+ *            The LAST record of the list with a given (map, frame) wins; a frame no record names is all zeros.
+ *   per axis of original length n, centre c, output length n_out:
+ *     box      b[i] = 1 for max(0, c - 10) <= i < min(n, c + 11), else 0 (may be empty: the frame is then all ones)
+ *     blur     g[i] = sum_{t < T} k[t] b[r101(i + t - T / 2)];  r101(j): 0 if n == 1, else p = 2 (n - 1), j = |j| mod p, p - j if j >= n
+ *              dilate = 1: T = 99, k[t] ~ exp(-x^2 / 200), x = -49 .. 49, normalised to sum 1 (host, fp64); dilate = 0: T = 1, k = [1]
+ *     resize   s = (o + 0.5) (n / n_out) - 0.5, base = floor(s), t = s - base; Keys weights (A = -0.75) far(t + 1), near(t),
+ *              near(1 - t), far(2 - t) on g[clamp(base - 1 + tap, 0, n - 1)]; no antialiasing, no clamping of the result
+ *     flip = 1 mirrors the horizontal profile: rx[o] <- rx[out_w - 1 - o]
+ *   dst[m][f][c][y][x] = 1 - d_c ry[y] rx[x], planes in the reference's B, G, R order: d = (1, 1, 0) for a first record, (1, 0, 1)
+ *            otherwise.  Contiguous [nmaps, frames, 3, out_h, out_w] in `dtype` (TT_F32 / TT_F16 / TT_BF16); EVERY element is
+ *            written by the call, the exact zeros of unnamed frames included.
+ * The profiles are accumulated in fp64; ry[y] rx[x] is the fp64 product rounded once to fp32, the subtraction is fp32, and a 16-bit
+ * dtype stores the round-to-nearest-even of that fp32 value.  Stores are 16-byte vectors over the flat output whatever out_w is;
+ * only the last total % (16 / element size) elements leave one by one.
+ * TWO launches (profiles -> ws, store stream ws -> dst), no host array, no copy, no synchronisation: the call can be captured.
+ * ws: tt_gesture_maps_ws_bytes(npoints, out_h, out_w) bytes on a 16-byte boundary (0 bytes, and ws may be NULL, for npoints == 0).
+ * Refused before the first HIP call.  TT_EINVAL: null dst; null points with npoints > 0; nmaps / frames / out_h / out_w / org_h /
+ * org_w <= 0; npoints < 0; a record's map or frame out of range; first, dilate or flip other than 0 / 1; a bad dtype; dst off a
+ * 16-byte boundary; a workspace that is missing, too small or misaligned.  TT_EUNSUPPORTED: more than 64 points; an original axis
+ * longer than TT_GESTURE_MAX_AXIS; an output beyond the kernel's 32-bit per-frame indices (3 out_h out_w > 2^31 - 4096,
+ * nmaps frames >= 2^31, or more than 2^31 - 1 blocks of 256 16-byte stores). */
+#define TT_GESTURE_MAX_POINTS 64
+#define TT_GESTURE_MAX_AXIS (1 << 24)      /* original height / width: 2 (n - 1) and i + 98 stay far inside int32 */
+typedef struct TtGesturePoint { int32_t map, frame, x, y, first; } TtGesturePoint;
+size_t tt_gesture_maps_ws_bytes(int32_t npoints, int32_t out_h, int32_t out_w);
+int tt_gesture_maps(const TtGesturePoint* points /* host */, int32_t npoints, int32_t nmaps, int32_t frames, int32_t org_h,
+                    int32_t org_w, int32_t out_h, int32_t out_w, int32_t dilate, int32_t flip, void* dst, int32_t dtype, void* ws,
+                    size_t ws_bytes, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,10 @@ class TtConvArgs(C.Structure):
     ]
 
 
+class TtGesturePoint(C.Structure):
+    _fields_ = [("map", C.c_int32), ("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("first", C.c_int32)]
+
+
 class TtEncAttnArgs(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("ldq", C.c_int64), ("k", C.c_void_p), ("ldk", C.c_int64),
@@ -126,6 +130,9 @@ SIGNATURES = {
     "tt_clip_image": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _i32, _vp, _sz, _vp]),
     "tt_layernorm_block": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _f32, _vp, _i32, _vp]),
     "tt_frames_out": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # gesture maps rasterised from the annotated points (additive as well)
+    "tt_gesture_maps_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "tt_gesture_maps": (C.c_int, [C.POINTER(TtGesturePoint), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
 }
 
 _lib = None

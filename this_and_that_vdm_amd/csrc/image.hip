@@ -203,6 +203,120 @@ __global__ __launch_bounds__(256) void frames_out4_kernel(const char* src, int h
   }
 }
 
+// ------------------------------------------------------------------------------------------------ tt_gesture_maps
+// The gesture frames of get_thisthat_sam (data_loader/video_this_that_dataset.py:28-130; the blur kernel is
+// utils/optical_flow_utils.py:197-219) without the canvas: every frame is 1 - d_c ry[y] rx[x] (include/ttvdm.h).
+constexpr int GESTURE_TAPS = 99, GESTURE_DOT = 10;
+// Kernel ARGUMENTS, like ClipTaps: the fp64 Gaussian taps (792 bytes), the clipped box of every live point (1 KiB) and which frame
+// each live point decides (772 bytes).  "Live": no later record names the same (map, frame) -- the host drops the others, so a
+// frame has at most one live point and the kernels never see the order of the list.
+struct GestureTaps { double k[GESTURE_TAPS]; };
+struct GestureBoxes { int lo[TT_GESTURE_MAX_POINTS][2], hi[TT_GESTURE_MAX_POINTS][2]; };      // [point][axis: 0 vertical, 1 horizontal]
+struct GestureLive { int n, slab[TT_GESTURE_MAX_POINTS], first[TT_GESTURE_MAX_POINTS]; };   // slab = map * frames + frame
+
+// BORDER_REFLECT_101 as index arithmetic: any number of bounces (the blur radius 49 may exceed the axis)
+__device__ __forceinline__ int reflect101(int j, int n) {
+  if (n == 1) return 0;
+  const int p = 2 * (n - 1);
+  j = (j < 0 ? -j : j) % p;
+  return j >= n ? p - j : j;
+}
+
+// Keys cubic weights (A = -0.75) exactly as gesture_map._cubic_weights writes them, in fp64
+__device__ __forceinline__ double keys_near(double x) { return ((-0.75 + 2.0) * x - (-0.75 + 3.0)) * x * x + 1.0; }
+__device__ __forceinline__ double keys_far(double x) { return ((-0.75 * x - 5.0 * -0.75) * x + 8.0 * -0.75) * x - 4.0 * -0.75; }
+
+// Launch 1: the resized profile of one axis of one point, one lane per output position: prof[point][0 .. out_h) = ry,
+// prof[point][out_h .. out_h + out_w) = rx (mirrored when `flip`).  The blurred box is evaluated only at the four source positions the
+// resize reads -- 4 x 99 indicator tests per lane, nothing as long as the original axis is ever stored, so its length costs nothing.
+__global__ __launch_bounds__(256) void gesture_profile_kernel(GestureTaps taps, GestureBoxes boxes, int ntaps, int org_h, int org_w,
+                                                              int out_h, int out_w, int flip, double* prof) {
+  const int axis = blockIdx.y, pt = blockIdx.z;
+  const int n = axis ? org_w : org_h, n_out = axis ? out_w : out_h;
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= n_out) return;
+  const int lo = boxes.lo[pt][axis], hi = boxes.hi[pt][axis];
+  const double scale = (double)n / (double)n_out;
+  const double s = ((double)o + 0.5) * scale - 0.5, fl = floor(s), t = s - fl;
+  const int base = (int)fl;                                                     // in [-1, n - 1]
+  const double w[4] = {keys_far(t + 1.0), keys_near(t), keys_near(1.0 - t), keys_far(2.0 - t)};
+  double r = 0.0;
+#pragma unroll
+  for (int tap = 0; tap < 4; ++tap) {
+    const int i = min(max(base - 1 + tap, 0), n - 1);
+    double g = 0.0;
+    for (int k = 0; k < ntaps; ++k) {
+      const int j = reflect101(i + k - ntaps / 2, n);
+      if (j >= lo && j < hi) g += taps.k[k];
+    }
+    r += w[tap] * g;
+  }
+  const int at = axis ? out_h + (flip ? out_w - 1 - o : o) : o;
+  prof[(long)pt * (out_h + out_w) + at] = r;
+}
+
+// the value of one output element: plane c of a frame decided by live point `rec` (-1: no point names the frame)
+__device__ __forceinline__ bool gesture_plane_on(int first, int c) { return c == 0 || (c == 1) == (first != 0); }   // d = (1,1,0) / (1,0,1)
+__device__ __forceinline__ float gesture_value(double ry, double rx) { return 1.0f - (float)(ry * rx); }
+
+// Launch 2: the store stream.  The output is one flat array of 16-byte chunks, one chunk per lane; a chunk that lies inside one row
+// (every chunk when out_w is a multiple of the chunk) takes one frame lookup and one ry, the others walk their elements across the
+// row / plane / frame boundary.  The block's first element is split into (frame slab, offset) once, on the scalar unit.
+template <typename Tag>
+__global__ __launch_bounds__(256) void gesture_store_kernel(const double* __restrict__ prof, GestureLive live, int out_h, int out_w,
+                                                            long total, char* __restrict__ dst) {
+  constexpr int EPC = Elem<Tag>::EPC, ES = Elem<Tag>::ES;
+  const unsigned hw = (unsigned)out_h * out_w, slab = 3u * hw, np = out_h + out_w;
+  const long e_blk = (long)blockIdx.x * (256 * EPC);
+  const long slab_blk = e_blk / slab;
+  const long e0 = e_blk + threadIdx.x * EPC;
+  if (e0 >= total) return;
+  unsigned rem = (unsigned)(e_blk - slab_blk * slab) + threadIdx.x * EPC;       // < slab + 256 EPC: the entry point keeps it in 32 bits
+  const unsigned q = rem / slab;
+  rem -= q * slab;
+  int mf = (int)(slab_blk + q), c = rem / hw;
+  rem -= c * hw;
+  int y = rem / out_w, x = rem - y * out_w;
+  // the live point of a frame slab (-1: none) and its colour; the loop bound and the argument reads are wave-uniform
+  const auto lookup = [&](int frame, int& first) {
+    int rec = -1;
+    for (int i = 0; i < live.n; ++i)
+      if (live.slab[i] == frame) { rec = i; first = live.first[i]; }
+    return rec;
+  };
+  int first = 0;
+  float f[EPC];
+  if (x + EPC <= out_w) {                                                       // (then e0 + EPC <= total as well)
+    const int rec = lookup(mf, first);
+    if (rec < 0 || !gesture_plane_on(first, c)) {
+      const float v = rec < 0 ? 0.f : 1.f;
+#pragma unroll
+      for (int i = 0; i < EPC; ++i) f[i] = v;
+    } else {
+      const double* p = prof + (long)rec * np;
+      const double ry = p[y];
+#pragma unroll
+      for (int i = 0; i < EPC; ++i) f[i] = gesture_value(ry, p[out_h + x + i]);
+    }
+    *(uint4*)(dst + e0 * ES) = pack_chunk<Tag>(f);
+    return;
+  }
+  const int valid = (int)min((long)EPC, total - e0);
+#pragma unroll
+  for (int i = 0; i < EPC; ++i) {
+    f[i] = 0.f;
+    if (i < valid) {
+      const int rec = lookup(mf, first);
+      if (rec >= 0) f[i] = gesture_plane_on(first, c) ? gesture_value(prof[(long)rec * np + y], prof[(long)rec * np + out_h + x]) : 1.f;
+      if (++x == out_w) { x = 0; if (++y == out_h) { y = 0; if (++c == 3) { c = 0; ++mf; } } }
+    }
+  }
+  if (valid == EPC) { *(uint4*)(dst + e0 * ES) = pack_chunk<Tag>(f); return; }
+#pragma unroll
+  for (int i = 0; i < EPC; ++i)                                                 // the last, partial chunk of the whole output
+    if (i < valid) store1<Tag>(dst + (e0 + i) * ES, f[i]);
+}
+
 bool dtype_ok(int32_t d) { return d == TT_BF16 || d == TT_F16 || d == TT_F32; }
 
 }  // namespace
@@ -290,5 +404,79 @@ extern "C" int tt_frames_out(const void* src, int32_t src_dtype, int32_t n, int3
 #undef TT_FO
 #undef TT_FO4
   TT_CHECK_LAUNCH("tt_frames_out");
+  return TT_OK;
+}
+
+extern "C" size_t tt_gesture_maps_ws_bytes(int32_t npoints, int32_t out_h, int32_t out_w) {
+  if (npoints <= 0 || out_h <= 0 || out_w <= 0) return 0;
+  return (size_t)npoints * ((size_t)out_h + (size_t)out_w) * sizeof(double);      // ry and rx of every point
+}
+
+extern "C" int tt_gesture_maps(const TtGesturePoint* points, int32_t npoints, int32_t nmaps, int32_t frames, int32_t org_h,
+                               int32_t org_w, int32_t out_h, int32_t out_w, int32_t dilate, int32_t flip, void* dst, int32_t dtype,
+                               void* ws, size_t ws_bytes, tt_stream_t stream) {
+  if (!dst) TT_FAIL(TT_EINVAL, "tt_gesture_maps: null dst");
+  if (npoints < 0) TT_FAIL(TT_EINVAL, "tt_gesture_maps: npoints %d", npoints);
+  if (npoints > 0 && !points) TT_FAIL(TT_EINVAL, "tt_gesture_maps: null points with npoints %d", npoints);
+  if (nmaps <= 0 || frames <= 0) TT_FAIL(TT_EINVAL, "tt_gesture_maps: %d map(s) of %d frame(s)", nmaps, frames);
+  if (out_h <= 0 || out_w <= 0) TT_FAIL(TT_EINVAL, "tt_gesture_maps: output size %d x %d", out_h, out_w);
+  if (org_h <= 0 || org_w <= 0) TT_FAIL(TT_EINVAL, "tt_gesture_maps: original size %d x %d", org_h, org_w);
+  if ((dilate != 0 && dilate != 1) || (flip != 0 && flip != 1)) TT_FAIL(TT_EINVAL, "tt_gesture_maps: dilate %d, flip %d (0 or 1)", dilate, flip);
+  if (!dtype_ok(dtype)) TT_FAIL(TT_EINVAL, "tt_gesture_maps: bad dtype");
+  if ((size_t)dst & 15) TT_FAIL(TT_EINVAL, "tt_gesture_maps: dst must start on a 16-byte boundary");
+  if (npoints > TT_GESTURE_MAX_POINTS) TT_FAIL(TT_EUNSUPPORTED, "tt_gesture_maps: %d points, built for at most %d", npoints, TT_GESTURE_MAX_POINTS);
+  for (int i = 0; i < npoints; ++i) {
+    const TtGesturePoint& p = points[i];
+    if (p.map < 0 || p.map >= nmaps || p.frame < 0 || p.frame >= frames)
+      TT_FAIL(TT_EINVAL, "tt_gesture_maps: point %d names map %d, frame %d of %d map(s) x %d frame(s)", i, p.map, p.frame, nmaps, frames);
+    if (p.first != 0 && p.first != 1) TT_FAIL(TT_EINVAL, "tt_gesture_maps: point %d has first %d (0 or 1)", i, p.first);
+  }
+  if (org_h > TT_GESTURE_MAX_AXIS || org_w > TT_GESTURE_MAX_AXIS)
+    TT_FAIL(TT_EUNSUPPORTED, "tt_gesture_maps: original size %d x %d, an axis may be at most %d", org_h, org_w, TT_GESTURE_MAX_AXIS);
+  const int epc = dtype == TT_F32 ? 4 : 8;
+  const long slab = 3L * out_h * out_w, nslab = (long)nmaps * frames, total = slab * nslab;
+  const long blocks = (total + 256L * epc - 1) / (256L * epc);
+  if (slab > 0x7fffffffL - 4096 || nslab > 0x7fffffffL || blocks > 0x7fffffffL)
+    TT_FAIL(TT_EUNSUPPORTED, "tt_gesture_maps: %d x %d frames of 3 x %d x %d are beyond the kernel's 32-bit frame indices", nmaps, frames, out_h, out_w);
+  if (npoints > 0 && (!ws || ((size_t)ws & 15) || ws_bytes < tt_gesture_maps_ws_bytes(npoints, out_h, out_w)))
+    TT_FAIL(TT_EINVAL, "tt_gesture_maps: the workspace must hold tt_gesture_maps_ws_bytes() = %zu bytes on a 16-byte boundary",
+            tt_gesture_maps_ws_bytes(npoints, out_h, out_w));
+  // live points: the last record of every (map, frame), in list order
+  GestureBoxes boxes;
+  GestureLive live;
+  live.n = 0;
+  for (int i = 0; i < npoints; ++i) {
+    bool later = false;
+    for (int j = i + 1; j < npoints && !later; ++j) later = points[j].map == points[i].map && points[j].frame == points[i].frame;
+    if (later) continue;
+    const int r = live.n++;
+    live.slab[r] = points[i].map * frames + points[i].frame;
+    live.first[r] = points[i].first;
+    const long c[2] = {points[i].y, points[i].x}, n[2] = {org_h, org_w};
+    for (int a = 0; a < 2; ++a) {                                             // 64-bit: a centre may be anywhere in int32
+      boxes.lo[r][a] = (int)(c[a] - GESTURE_DOT > 0 ? (c[a] - GESTURE_DOT < n[a] ? c[a] - GESTURE_DOT : n[a]) : 0);
+      boxes.hi[r][a] = (int)(c[a] + GESTURE_DOT + 1 < n[a] ? (c[a] + GESTURE_DOT + 1 > 0 ? c[a] + GESTURE_DOT + 1 : 0) : n[a]);
+    }
+  }
+  for (int r = live.n; r < TT_GESTURE_MAX_POINTS; ++r) {
+    live.slab[r] = -1; live.first[r] = 0;
+    boxes.lo[r][0] = boxes.lo[r][1] = boxes.hi[r][0] = boxes.hi[r][1] = 0;
+  }
+  // gesture_map.gaussian_taps: exp(-x^2 / (2 sigma^2)), sigma = 10, on x = -49 .. 49, normalised to sum 1; T = 1 without dilate
+  GestureTaps taps;
+  const int ntaps = dilate ? GESTURE_TAPS : 1;
+  double sum = 0.0;
+  for (int t = 0; t < GESTURE_TAPS; ++t) { const double x = (t - GESTURE_TAPS / 2) / 10.0; taps.k[t] = exp(-0.5 * x * x); sum += taps.k[t]; }
+  for (int t = 0; t < GESTURE_TAPS; ++t) taps.k[t] = dilate ? taps.k[t] / sum : (t == 0 ? 1.0 : 0.0);
+  hipStream_t st = (hipStream_t)stream;
+  if (live.n > 0) {
+    const int longest = out_h > out_w ? out_h : out_w;
+    hipLaunchKernelGGL(gesture_profile_kernel, dim3((unsigned)((longest + 255) / 256), 2, (unsigned)live.n), dim3(256), 0, st, taps, boxes, ntaps,
+                       (int)org_h, (int)org_w, (int)out_h, (int)out_w, (int)flip, (double*)ws);
+  }
+#define TT_GS(TAG) hipLaunchKernelGGL(gesture_store_kernel<TAG>, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)ws, live, (int)out_h, (int)out_w, total, (char*)dst)
+  if (dtype == TT_BF16) TT_GS(bf16_tag); else if (dtype == TT_F16) TT_GS(f16_tag); else TT_GS(f32_tag);
+#undef TT_GS
+  TT_CHECK_LAUNCH("tt_gesture_maps");
   return TT_OK;
 }

@@ -16,10 +16,14 @@ cv2 is not available in this image, so its two operators are restated from their
 `tests/test_gesture_map_cpu.py` checks the two against independent implementations (scipy.ndimage.correlate mode="mirror",
 torch bicubic interpolation, which uses the same A and alignment).  This is host-side request preparation, like the
 reference's; it feeds the VAE encode that produces `controlnet_cond` for the denoise loop.
+
+The same frames without the host: `GesturePoints`, `rasterise_points_device` and `get_thisthat_sam(..., device=)` at the end of this
+module hand the points to tt_gesture_maps (csrc/image.hip), which writes the frames on the device from two 1-D profiles per point.
 """
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -147,10 +151,78 @@ def read_points_file(path: str) -> List[Tuple[int, float, float]]:
     return pts
 
 
-def get_thisthat_sam(config, intput_dir: str, store_dir: Optional[str] = None, flip: bool = False, verbose: bool = False):
+# ---- the same frames on the device, from the points themselves (tt_gesture_maps, include/ttvdm.h) ----------------
+# The canvas above is 255 - (255 - colour) * box with box an outer product of two 1-D indicators, and both the blur and the resize are
+# separable with rows that sum to 1, so a frame is 1 - d_c * ry[y] * rx[x]: two short profiles per point instead of a canvas of the
+# original size.  The host functions above stay as they are (tests/golden/gesture_bridge.json pins their bytes); these stand beside them.
+MAX_DEVICE_POINTS = 64              # TT_GESTURE_MAX_POINTS: the records of one call travel as kernel arguments
+
+
+def point_records(points: Sequence[Tuple[int, float, float]], num_frames: int, map_index: int = 0) -> List[Tuple[int, int, int, int, int]]:
+    """(frame_idx, horizontal, vertical) annotations -> the (map, frame, x, y, first) integer records of ops.gesture_maps, with what
+    rasterise_points does to them: coordinates truncated by int(float(.)), the first point of the list marked, and the frame index
+    resolved as `cond[frame_idx] = ...` resolves it -- a negative index counts from the end, one outside [-F, F) is an IndexError."""
+    recs = []
+    for i, (frame_idx, horizontal, vertical) in enumerate(points):
+        frame = int(frame_idx)
+        if not -num_frames <= frame < num_frames:
+            raise IndexError(f"index {frame} is out of bounds for axis 0 with size {num_frames}")
+        recs.append((int(map_index), frame % num_frames, int(float(horizontal)), int(float(vertical)), int(i == 0)))
+    return recs
+
+
+@dataclass(frozen=True)
+class GesturePoints:
+    """The annotated points of one request, as a pipeline's `condition_img`: rasterised on the device at the call's height, width and
+    num_frames.  points: (frame_idx, horizontal, vertical) in pixels of the original image of size org_hw = (height, width)."""
+    points: Tuple[Tuple[int, float, float], ...]
+    org_hw: Tuple[int, int]
+    dilate: bool = True
+    flip: bool = False
+
+    def __post_init__(self):
+        object.__setattr__(self, "points", tuple((int(f), float(h), float(v)) for f, h, v in self.points))
+        object.__setattr__(self, "org_hw", (int(self.org_hw[0]), int(self.org_hw[1])))
+
+    @classmethod
+    def from_dir(cls, path: str, dilate: bool = True, flip: bool = False) -> "GesturePoints":
+        """`<path>/data.txt` and the size of `<path>/im_0.jpg`: what get_thisthat_sam reads."""
+        import PIL.Image
+
+        with PIL.Image.open(os.path.join(path, "im_0.jpg")) as im:
+            org_width, org_height = im.size
+        return cls(tuple(read_points_file(os.path.join(path, "data.txt"))), (org_height, org_width), dilate, flip)
+
+
+def rasterise_points_device(gp, height: int, width: int, num_frames: int, device, dtype=None):
+    """GesturePoints -> [F, 3, H, W], a list of them -> [N, F, 3, H, W], on `device` in `dtype` (default float32): the frames of
+    rasterise_points without a canvas, a host array or a copy to the device.  Maps that share original size, dilate and flip -- one
+    GesturePoints, or the images of one dataset -- are written by ONE call of tt_gesture_maps; a list that mixes them takes one call
+    per map (the entry point has one original size per call)."""
+    import torch
+
+    from . import ops
+
+    dtype = torch.float32 if dtype is None else dtype
+    if isinstance(gp, GesturePoints):
+        return rasterise_points_device([gp], height, width, num_frames, device, dtype)[0]
+    maps = list(gp)
+    if not maps or not all(isinstance(g, GesturePoints) for g in maps):
+        raise TypeError("rasterise_points_device: a GesturePoints or a non-empty list of them")
+    if all((g.org_hw, g.dilate, g.flip) == (maps[0].org_hw, maps[0].dilate, maps[0].flip) for g in maps):
+        recs = [r for m, g in enumerate(maps) for r in point_records(g.points, num_frames, m)]
+        if len(recs) <= MAX_DEVICE_POINTS:
+            return ops.gesture_maps(recs, len(maps), num_frames, maps[0].org_hw, (height, width), maps[0].dilate, maps[0].flip, dtype, device)
+    return torch.cat([ops.gesture_maps(point_records(g.points, num_frames), 1, num_frames, g.org_hw, (height, width), g.dilate, g.flip,
+                                       dtype, device) for g in maps], 0)
+
+
+def get_thisthat_sam(config, intput_dir: str, store_dir: Optional[str] = None, flip: bool = False, verbose: bool = False, device=None):
     """Drop-in for the reference function of the same name and (mis-spelt) argument: reads `<dir>/data.txt` and the size of
     `<dir>/im_0.jpg`, returns (condition [F, 3, H, W] float32, motion_bucket_id, frame indices, coordinates).
-    `config` needs: video_seq_length, conditioning_channels (3), height, width, dilate, motion_bucket_id."""
+    `config` needs: video_seq_length, conditioning_channels (3), height, width, dilate, motion_bucket_id.
+    `device` (default None: the host rasteriser, a numpy array): rasterise there with rasterise_points_device and return the device
+    tensor in the array's place."""
     import PIL.Image
 
     if config["conditioning_channels"] != 3:
@@ -158,11 +230,19 @@ def get_thisthat_sam(config, intput_dir: str, store_dir: Optional[str] = None, f
     with PIL.Image.open(os.path.join(intput_dir, "im_0.jpg")) as im:
         org_width, org_height = im.size
     pts = read_points_file(os.path.join(intput_dir, "data.txt"))
-    cond, frames, coords = rasterise_points(pts, (org_height, org_width), config["height"], config["width"],
-                                            config["video_seq_length"], dilate=bool(config["dilate"]), flip=flip)
+    if device is not None:
+        gp = GesturePoints(tuple(pts), (org_height, org_width), bool(config["dilate"]), bool(flip))
+        cond_dev = rasterise_points_device(gp, config["height"], config["width"], config["video_seq_length"], device)
+        frames = [int(p[0]) for p in pts]
+        coords = [(int(float(p[2])), int(float(p[1]))) for p in pts]
+        cond = cond_dev.cpu().numpy() if store_dir is not None and verbose else None
+    else:
+        cond_dev = None
+        cond, frames, coords = rasterise_points(pts, (org_height, org_width), config["height"], config["width"],
+                                                config["video_seq_length"], dilate=bool(config["dilate"]), flip=flip)
     if store_dir is not None and verbose:      # the reference dumps the resized BGR canvases for inspection
         for i, f in enumerate(frames):
             bgr = np.clip(cond[f].transpose(1, 2, 0) * 255.0, 0, 255).round().astype(np.uint8)
             PIL.Image.fromarray(bgr[..., ::-1].copy()).save(os.path.join(store_dir, f"condition_TT{i}.png"))
     bucket = 200 if config["motion_bucket_id"] is None else config["motion_bucket_id"]
-    return cond, bucket, frames, coords
+    return cond if cond_dev is None else cond_dev, bucket, frames, coords

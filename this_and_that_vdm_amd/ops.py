@@ -742,3 +742,34 @@ def frames_out(x, kind: int):
     check(lib.tt_frames_out(_p(x), _code(x.dtype), n, ch, h, w, kind, _p(out), _stream()), "tt_frames_out")
     _wrote(out)
     return out
+
+
+def gesture_maps(records, nmaps: int, frames: int, org_hw, out_hw, dilate: bool, flip: bool, dtype, device, out=None):
+    """Gesture frames rasterised on the device from the annotated points (tt_gesture_maps): `records` is a sequence of up to 64
+    ``(map, frame, x, y, first)`` integer tuples as ``gesture_map.point_records`` builds them -- the point (x horizontal, y vertical, in
+    pixels of the ``org_hw`` image) decides frame `frame` of map `map`, the last record of a (map, frame) wins, unnamed frames are zeros.
+    -> [nmaps, frames, 3, out_hw[0], out_hw[1]] in `dtype`, every element written by the call.  No host array is built and nothing is
+    copied to the device: the records travel as kernel arguments.  ``out``: a contiguous tensor of that shape and dtype to write instead of a new one."""
+    lib = _lib.load()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("libttvdm ops need tensors on the HIP device (no CPU fallback)")
+    lim = 1 << 31
+    recs = (_lib.TtGesturePoint * max(len(records), 1))()
+    for i, rec in enumerate(records):
+        m, f, x, y, first = (int(v) for v in rec)
+        # a centre beyond int32 is outside every image the library serves: clamping it keeps the (empty) box empty
+        recs[i] = _lib.TtGesturePoint(m, f, max(-lim, min(lim - 1, x)), max(-lim, min(lim - 1, y)), first)
+    n, (oh, ow) = len(records), (int(out_hw[0]), int(out_hw[1]))
+    with torch.cuda.device(device):
+        shape = (int(nmaps), int(frames), 3, oh, ow)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=device)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+            raise RuntimeError(f"gesture_maps: out must be a contiguous {dtype} tensor of shape {shape}")
+        need = lib.tt_gesture_maps_ws_bytes(n, oh, ow)
+        ws = _workspace(need, out.device) if need else None
+        check(lib.tt_gesture_maps(recs if n else None, n, int(nmaps), int(frames), int(org_hw[0]), int(org_hw[1]), oh, ow, int(dilate), int(flip),
+                                  _p(out), _code(dtype), _p(ws), need, _stream()), "tt_gesture_maps")
+    _wrote(out)
+    return out

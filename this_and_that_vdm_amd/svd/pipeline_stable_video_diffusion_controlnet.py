@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..gesture_map import GesturePoints, rasterise_points_device
 from .denoise import DenoiseLoop
 from .pipeline_utils import (CLIPFeatureExtractor, PipelineBase, StableVideoDiffusionPipelineOutput, VaeImageProcessor,
                              append_dims, randn_tensor, resize_with_antialiasing, tensor2vid)
@@ -259,7 +260,13 @@ class _SVDPipelineCore(PipelineBase):
                              "F, 4, h, w]")
         cond = None
         if controlnet is not None:
-            cond = self.prepare_condition_image(condition_img, device)
+            if isinstance(condition_img, GesturePoints) or (isinstance(condition_img, (list, tuple)) and len(condition_img) > 0
+                                                            and all(isinstance(c, GesturePoints) for c in condition_img)):
+                # the annotated points themselves: rasterised on the device straight to the fp16 that prepare_condition_image casts to
+                # (quirk Q7) -- no host canvas and no copy of a map to the device
+                cond = rasterise_points_device(condition_img, height, width, num_frames, device, torch.float16)
+            else:
+                cond = self.prepare_condition_image(condition_img, device)
             if cond.ndim not in (4, 5) or cond.shape[-4] != num_frames or (cond.ndim == 5 and cond.shape[0] != batch_size):
                 raise ValueError(f"condition_img {tuple(cond.shape)}: expected [F,3,H,W] (shared by every request) or one [F,3,H,W] map per "
                                  f"image, [{batch_size},F,3,H,W], with F = {num_frames}")
