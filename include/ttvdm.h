@@ -548,6 +548,60 @@ int tt_gesture_maps(const TtGesturePoint* points /* host */, int32_t npoints, in
                     int32_t org_w, int32_t out_h, int32_t out_w, int32_t dilate, int32_t flip, void* dst, int32_t dtype, void* ws,
                     size_t ws_bytes, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The request image itself: PIL's 8-bit resize (Image.resize on an RGB image; what VaeImageProcessor.preprocess does with LANCZOS,
+ * svd/pipeline_stable_video_diffusion_controlnet.py:530, and what the reference's callers do with BICUBIC before the pipeline,
+ * test_code/inference.py:83,198, app.py:278) and the VAE input that follows it (:530-532).  The resampler is integer arithmetic on
+ * tables the host forms in fp64, so the result equals Pillow's byte for byte.  Additive: the ABI version is unchanged.
+ *
+ * tt_resample_coeffs (HOST only, no HIP call): the tables of one axis, Pillow's precompute_coeffs + normalize_coeffs_8bpc, in fp64
+ * with libm, in this order:
+ *   scale = in / out, fs = max(scale, 1), ss = 1 / fs, support = S fs, ksize = 2 ceil(support) + 1
+ *   per output o:  c = (o + 0.5) scale,  xmin = max((int)(c - support + 0.5), 0),  n = min((int)(c + support + 0.5), in) - xmin
+ *                  w[x] = f((x + xmin - c + 0.5) ss) for x < n, ww their sum in index order, w[x] /= ww when ww != 0
+ *                  kk[o][x] = (int)(w[x] 2^22 + 0.5) for w[x] >= 0, (int)(w[x] 2^22 - 0.5) otherwise (truncating); 0 for n <= x < ksize
+ *                  bounds[o] = (xmin, n)
+ *   filter (PIL's codes)  TT_RESAMPLE_BOX 4       S = 0.5  1 on (-0.5, 0.5]
+ *                         TT_RESAMPLE_BILINEAR 2  S = 1    1 - |x|
+ *                         TT_RESAMPLE_HAMMING 5   S = 1    sinc(x) (0.54f + 0.46f cos(pi x)), 1 at 0: the two constants are fp32 values
+ *                         TT_RESAMPLE_BICUBIC 3   S = 2    Keys, a = -0.5
+ *                         TT_RESAMPLE_LANCZOS 1   S = 3    sinc(x) sinc(x / 3) on [-3, 3)
+ * *ksize is always written; bounds [2 out] and kk [out ksize] are written when both are non-null (both null: ksize only).
+ * Refused: TT_EINVAL for a null ksize, one null buffer of the two, in_size or out_size <= 0, an unknown filter; TT_EUNSUPPORTED for
+ * a size above TT_RESAMPLE_MAX_AXIS.
+ *
+ * DEVICE table of one axis, int32 [(2 + ksize) out], tap-major so that neighbouring outputs read neighbouring words:
+ *   tab[o] = xmin, tab[out + o] = n, tab[(2 + t) out + o] = kk[o][t].  NULL for an axis whose size does not change.
+ *
+ * The two passes (Pillow's ImagingResampleHorizontal_8bpc, then ImagingResampleVertical_8bpc), each skipped when its size is
+ * unchanged:  acc = 1 << 21 (int32);  acc += pixel kk[t] for t < n;  byte = clamp(acc >> 22 (arithmetic), 0, 255).
+ * The intermediate [nimg, h, out_w, 3] is uint8, as in PIL.  The kernels clamp xmin to [0, in - 1] and n to [0, min(ksize, in - xmin)],
+ * so no table makes them read outside the source or the table.
+ *
+ * tt_resize_u8:  src uint8 [nimg, h, w, 3] -> dst uint8 [nimg, out_h, out_w, 3].  Both sizes unchanged: one device-to-device copy on the stream.
+ * tt_vae_image:  the same pixels through the epilogue of the LAST pass (the only launch when neither size changes), for request r of
+ *   image r / nvid, r < nimg nvid:   x = u / 255.0f;  v = 2 x - 1;  y = v + na noise[r]   (noise NULL: y = v, na ignored)
+ *   every operation rounded to fp32 on its own (no contraction), then ONE round-to-nearest-even to `dtype`;
+ *   dst contiguous [nimg nvid, 3, out_h, out_w] in `dtype`, noise fp32 of the same shape -- image_processor.preprocess, the
+ *   repeat_interleave of the videos of an image, + noise_aug_strength * randn and .to(vae.dtype) in one store.
+ * AT MOST TWO launches.  ws holds the intermediate: tt_*_ws_bytes() = nimg h out_w 3 bytes when both sizes change, else 0 (ws may
+ * then be NULL); 16-byte aligned.
+ * Refused before the first HIP call.  TT_EINVAL: null src / dst; nimg, a size or nvid <= 0; a table that is NULL for an axis that
+ * changes, or given for one that does not; ksize < 1 for a given table; a bad dtype; dst (uint8) off a 4-byte boundary, dst / noise
+ * (tt_vae_image) off their element size, a table off a 4-byte boundary; a workspace that is missing, too small or misaligned.
+ * TT_EUNSUPPORTED: a size above TT_RESAMPLE_MAX_AXIS, or more elements than one grid covers. */
+#define TT_RESAMPLE_MAX_AXIS (1 << 20)
+enum { TT_RESAMPLE_LANCZOS = 1, TT_RESAMPLE_BILINEAR = 2, TT_RESAMPLE_BICUBIC = 3, TT_RESAMPLE_BOX = 4, TT_RESAMPLE_HAMMING = 5 };
+int tt_resample_coeffs(int32_t in_size, int32_t out_size, int32_t filter, int32_t* ksize /* host */, int32_t* bounds /* host [2 out] */,
+                       int32_t* kk /* host [out ksize] */);
+size_t tt_resize_u8_ws_bytes(int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w);
+int tt_resize_u8(const void* src, int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w, const int32_t* tab_x,
+                 int32_t ksize_x, const int32_t* tab_y, int32_t ksize_y, void* dst, void* ws, size_t ws_bytes, tt_stream_t stream);
+size_t tt_vae_image_ws_bytes(int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w);
+int tt_vae_image(const void* src, int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w, const int32_t* tab_x,
+                 int32_t ksize_x, const int32_t* tab_y, int32_t ksize_y, const float* noise, float na, int32_t nvid, void* dst,
+                 int32_t dtype, void* ws, size_t ws_bytes, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,12 @@ SIGNATURES = {
     # gesture maps rasterised from the annotated points (additive as well)
     "tt_gesture_maps_ws_bytes": (_sz, [_i32, _i32, _i32]),
     "tt_gesture_maps": (C.c_int, [C.POINTER(TtGesturePoint), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
+    # PIL's 8-bit resize and the VAE input computed from it (additive as well); tt_resample_coeffs is host-only
+    "tt_resample_coeffs": (C.c_int, [_i32, _i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tt_resize_u8_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "tt_resize_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "tt_vae_image_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "tt_vae_image": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _i32, _vp, _sz, _vp]),
 }
 
 _lib = None

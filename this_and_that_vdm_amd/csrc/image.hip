@@ -1,5 +1,6 @@
 // The request path around the models: CLIP image preprocessing (tt_clip_image), the context LayerNorm of use_text requests
-// (tt_layernorm_block) and the export of decoded frames (tt_frames_out).  None of it is in the denoise step; all of it is fp32
+// (tt_layernorm_block), the export of decoded frames (tt_frames_out), the gesture maps from their points (tt_gesture_maps) and the request
+// image itself: PIL's 8-bit resize and the VAE input (tt_resize_u8 / tt_vae_image).  None of it is in the denoise step; all of it is
 // arithmetic on a few hundred thousand elements, written for being on the stream (no host round trip, no vendor conv library).
 #include <math.h>
 
@@ -317,6 +318,132 @@ __global__ __launch_bounds__(256) void gesture_store_kernel(const double* __rest
     if (i < valid) store1<Tag>(dst + (e0 + i) * ES, f[i]);
 }
 
+// ------------------------------------------------------------------------------------------------ tt_resize_u8 / tt_vae_image
+// PIL's 8-bit resize as two integer passes over tables the host formed (tt_resample_coeffs, lib.cpp), and the VAE input computed in
+// the epilogue of the last pass (include/ttvdm.h).  One axis: the device table ([out] xmin, [out] n, [ksize][out]
+// kk -- tap-major, so the lanes of neighbouring outputs read neighbouring words) and the sizes it maps.
+struct ResampleAxis { const int* tab; int in, out, ksize; };
+
+// (first source index, taps) of output o, clamped to the source and to the table whatever the table holds
+__device__ __forceinline__ void resample_bounds(const ResampleAxis& ax, int o, int& first, int& n) {
+  first = min(max(ax.tab[o], 0), ax.in - 1);
+  n = min(max(ax.tab[ax.out + o], 0), min(ax.ksize, ax.in - first));
+}
+// Pillow's accumulation of one output byte of output o: n source bytes `step` apart from p, int32 from 1 << 21, >> 22, clip8
+__device__ __forceinline__ unsigned clip8(int acc) { return (unsigned)min(max(acc >> 22, 0), 255); }
+__device__ __forceinline__ unsigned resample_byte(const unsigned char* p, long step, const ResampleAxis& ax, int o, int n) {
+  const int* kk = ax.tab + 2 * ax.out + o;
+  int acc = 1 << 21;
+  for (int t = 0; t < n; ++t) acc += (int)p[t * step] * kk[t * ax.out];
+  return clip8(acc);
+}
+// one output byte of a pass: HORIZONTAL src [rows, ax.in, 3] at (row, ox, c); vertical src [nimg, ax.in, rb] at (img, oy, byte xb)
+__device__ __forceinline__ unsigned resample_h(const unsigned char* src, const ResampleAxis& ax, long row, int ox, int c) {
+  int first, n;
+  resample_bounds(ax, ox, first, n);
+  return resample_byte(src + (row * ax.in + first) * 3 + c, 3, ax, ox, n);
+}
+__device__ __forceinline__ unsigned resample_v(const unsigned char* src, const ResampleAxis& ax, long rb, long img, int oy, long xb) {
+  int first, n;
+  resample_bounds(ax, oy, first, n);
+  return resample_byte(src + (img * ax.in + first) * rb + xb, rb, ax, oy, n);
+}
+
+// One pass, uint8 to uint8.  The output is one flat array of bytes, four per lane, stored as a dword (the last total % 4 bytes leave
+// one by one); rb = 3 x (pixels per row) is the byte length of a row, the same on both sides of the vertical pass, which therefore
+// never looks at pixels: a row of coefficients is shared by every lane that works on the row, and with DWORDS (rb % 4 == 0 and an
+// aligned source: no dword crosses a row) each tap is one dword load of four source bytes.
+template <bool HORIZONTAL, bool DWORDS>
+__global__ __launch_bounds__(256) void resample_u8_kernel(const unsigned char* __restrict__ src, ResampleAxis ax, long rb, long total,
+                                                          unsigned char* __restrict__ dst) {
+  const long e0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (e0 >= total) return;
+  unsigned b[4] = {0, 0, 0, 0};
+  if constexpr (HORIZONTAL) {
+    long pix = e0 / 3, row = pix / ax.out;
+    int c = (int)(e0 - pix * 3), ox = (int)(pix - row * ax.out);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (e0 + i < total) b[i] = resample_h(src, ax, row, ox, c);
+      if (++c == 3) { c = 0; if (++ox == ax.out) { ox = 0; ++row; } }
+    }
+  } else {
+    long line = e0 / rb, xb = e0 - line * rb, img = line / ax.out;
+    int oy = (int)(line - img * ax.out);
+    if constexpr (DWORDS) {
+      int first, n;
+      resample_bounds(ax, oy, first, n);
+      const unsigned char* p = src + (img * ax.in + first) * rb + xb;
+      const int* kk = ax.tab + 2 * ax.out + oy;
+      int acc[4] = {1 << 21, 1 << 21, 1 << 21, 1 << 21};
+      for (int t = 0; t < n; ++t) {
+        const unsigned v = *(const unsigned*)(p + t * rb);
+        const int k = kk[t * ax.out];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] += (int)((v >> (8 * i)) & 255u) * k;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) b[i] = clip8(acc[i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (e0 + i < total) b[i] = resample_v(src, ax, rb, img, oy, xb);
+        if (++xb == rb) { xb = 0; if (++oy == ax.out) { oy = 0; ++img; } }
+      }
+    }
+  }
+  if (e0 + 4 <= total) { *(unsigned*)(dst + e0) = b[0] | b[1] << 8 | b[2] << 16 | b[3] << 24; return; }
+  for (int i = 0; i < 4 && e0 + i < total; ++i) dst[e0 + i] = (unsigned char)b[i];
+}
+
+// image_processor.preprocess and the noise augmentation on one byte: u / 255, 2 x - 1, + na * noise, each rounded to fp32 on its own
+// as the torch statements round them (contraction off: a fused na * noise + v would round once)
+__device__ __forceinline__ float vae_value(unsigned u, float na, float nz, bool noised) {
+#pragma clang fp contract(off)
+  const float x = (float)u / 255.0f;
+  const float v = 2.0f * x - 1.0f;
+  const float s = na * nz;
+  return noised ? v + s : v;
+}
+
+// The last pass with the VAE input as its epilogue, laid out by the OUTPUT: one lane per four consecutive x of one (image, channel,
+// row) of the NCHW result, so that the stores -- and the noise loads, the largest stream of the stage: 4 bytes per element against
+// the source's 1 -- are whole 8- / 16-byte vectors along x (VEC: out_w % 4 == 0 and aligned operands; otherwise element by element).
+// The source bytes of a channel are 3 apart; a wave reads all of a 768-byte span of each tap row and the other two channels' waves
+// find it in L2.  MODE 0: no resampling (src [nimg, oh, ow, 3]); 1: horizontal (src [nimg, oh, ax.in, 3]); 2: vertical
+// (src [nimg, ax.in, ow, 3]).  Image i serves requests i nvid .. i nvid + nvid - 1, each with its own noise.
+template <typename Tag, int MODE, bool VEC>
+__global__ __launch_bounds__(256) void vae_image_kernel(const unsigned char* __restrict__ src, ResampleAxis ax, int oh, int ow, long total,
+                                                        const float* __restrict__ noise, float na, int nvid, char* __restrict__ dst) {
+  constexpr int ES = Elem<Tag>::ES;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int q = (ow + 3) >> 2;
+  const long line = idx / q, plane = line / oh, img = plane / 3;
+  const int x0 = (int)(idx - line * q) * 4, oy = (int)(line - plane * oh), c = (int)(plane - img * 3);
+  const int valid = VEC ? 4 : min(4, ow - x0);
+  unsigned u[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (i >= valid) continue;
+    if constexpr (MODE == 0) u[i] = src[((img * oh + oy) * ow + x0 + i) * 3 + c];
+    else if constexpr (MODE == 1) u[i] = resample_h(src, ax, img * oh + oy, x0 + i, c);
+    else u[i] = resample_v(src, ax, 3L * ow, img, oy, 3L * (x0 + i) + c);
+  }
+  for (int j = 0; j < nvid; ++j) {
+    const long off = (((img * nvid + j) * 3 + c) * oh + oy) * ow + x0;
+    float nz[4] = {0.f, 0.f, 0.f, 0.f}, f[4];
+    if (noise) {
+      if constexpr (VEC) { const float4 v = *(const float4*)(noise + off); nz[0] = v.x; nz[1] = v.y; nz[2] = v.z; nz[3] = v.w; }
+      else for (int i = 0; i < valid; ++i) nz[i] = noise[off + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = vae_value(u[i], na, nz[i], noise != nullptr);
+    if constexpr (VEC) *(typename Elem<Tag>::quad_t*)(dst + off * ES) = f32_to_quad<Tag>(f);
+    else for (int i = 0; i < valid; ++i) store1<Tag>(dst + (off + i) * ES, f[i]);
+  }
+}
+
 bool dtype_ok(int32_t d) { return d == TT_BF16 || d == TT_F16 || d == TT_F32; }
 
 }  // namespace
@@ -479,4 +606,100 @@ extern "C" int tt_gesture_maps(const TtGesturePoint* points, int32_t npoints, in
 #undef TT_GS
   TT_CHECK_LAUNCH("tt_gesture_maps");
   return TT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ tt_resize_u8 / tt_vae_image
+namespace {
+size_t resample_ws_bytes(int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w) {
+  if (nimg <= 0 || h <= 0 || w <= 0 || out_h <= 0 || out_w <= 0 || out_w == w || out_h == h) return 0;
+  return (size_t)nimg * h * out_w * 3;                                 // the uint8 image between the two passes
+}
+
+struct VaeEpilogue { const float* noise; float na; int nvid; void* dst; int dtype; };      // null: the uint8 result of tt_resize_u8
+
+// what the two entry points share: every refusal, then at most two launches
+int resample_run(const char* name, const void* src, int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w, const int32_t* tab_x,
+                 int32_t ksize_x, const int32_t* tab_y, int32_t ksize_y, void* dst_u8, const VaeEpilogue* ep, void* ws, size_t ws_bytes,
+                 tt_stream_t stream) {
+  void* dst = ep ? ep->dst : dst_u8;
+  if (!src || !dst) TT_FAIL(TT_EINVAL, "%s: null operand", name);
+  if (nimg <= 0 || h <= 0 || w <= 0 || out_h <= 0 || out_w <= 0)
+    TT_FAIL(TT_EINVAL, "%s: %d image(s) of %d x %d -> %d x %d, every size must be positive", name, nimg, h, w, out_h, out_w);
+  if (h > TT_RESAMPLE_MAX_AXIS || w > TT_RESAMPLE_MAX_AXIS || out_h > TT_RESAMPLE_MAX_AXIS || out_w > TT_RESAMPLE_MAX_AXIS)
+    TT_FAIL(TT_EUNSUPPORTED, "%s: %d x %d -> %d x %d, an axis may be at most %d", name, h, w, out_h, out_w, TT_RESAMPLE_MAX_AXIS);
+  const bool need_x = out_w != w, need_y = out_h != h;
+  if (need_x != (tab_x != nullptr) || need_y != (tab_y != nullptr))
+    TT_FAIL(TT_EINVAL, "%s: %d x %d -> %d x %d takes a table for exactly the axes that change", name, h, w, out_h, out_w);
+  if ((need_x && ksize_x < 1) || (need_y && ksize_y < 1)) TT_FAIL(TT_EINVAL, "%s: ksize %d x %d", name, ksize_y, ksize_x);
+  if ((need_x && (long)(2 + (long)ksize_x) * out_w > 0x7fffffffL) || (need_y && (long)(2 + (long)ksize_y) * out_h > 0x7fffffffL))
+    TT_FAIL(TT_EUNSUPPORTED, "%s: a table of more than 2^31 words", name);
+  if (((size_t)tab_x | (size_t)tab_y) & 3) TT_FAIL(TT_EINVAL, "%s: the tables must start on 4-byte boundaries", name);
+  if (ep) {
+    if (!dtype_ok(ep->dtype)) TT_FAIL(TT_EINVAL, "%s: bad dtype", name);
+    if (ep->nvid <= 0) TT_FAIL(TT_EINVAL, "%s: %d videos per image", name, ep->nvid);
+    if (((size_t)dst & (ep->dtype == TT_F32 ? 3 : 1)) || ((size_t)ep->noise & 3)) TT_FAIL(TT_EINVAL, "%s: dst and noise must be aligned to their element size", name);
+  } else if ((size_t)dst & 3) TT_FAIL(TT_EINVAL, "%s: dst must start on a 4-byte boundary", name);
+  const long mid = 3L * nimg * h * out_w, total_u8 = 3L * nimg * out_h * out_w;                 // bytes after the horizontal / the last pass
+  const long lanes = ep ? 3L * nimg * out_h * ((out_w + 3) / 4) : (total_u8 + 3) / 4;           // of the last launch
+  if (mid > 0x7fffffffL * 1024 || lanes > 0x7fffffffL * 256 || (ep && total_u8 > 0x7fffffffffffL / ep->nvid))
+    TT_FAIL(TT_EUNSUPPORTED, "%s: more elements than one grid covers", name);
+  const size_t need = resample_ws_bytes(nimg, h, w, out_h, out_w);
+  if (need && (!ws || ((size_t)ws & 15) || ws_bytes < need))
+    TT_FAIL(TT_EINVAL, "%s: the workspace must hold %zu bytes on a 16-byte boundary", name, need);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 block(256);
+  const ResampleAxis ax = {tab_x, w, out_w, ksize_x}, ay = {tab_y, h, out_h, ksize_y}, none = {nullptr, 1, 1, 0};
+  const unsigned char* in = (const unsigned char*)src;
+  const auto pass_u8 = [&](bool horizontal, const unsigned char* from, long total, unsigned char* to) {
+    const dim3 grid((unsigned)((total + 1023) / 1024));
+    const long rb = 3L * out_w;                                  // the vertical pass runs after the horizontal one: rows are out_w pixels
+    if (horizontal) hipLaunchKernelGGL((resample_u8_kernel<true, false>), grid, block, 0, st, from, ax, rb, total, to);
+    else if ((rb & 3) == 0 && ((size_t)from & 3) == 0) hipLaunchKernelGGL((resample_u8_kernel<false, true>), grid, block, 0, st, from, ay, rb, total, to);
+    else hipLaunchKernelGGL((resample_u8_kernel<false, false>), grid, block, 0, st, from, ay, rb, total, to);
+  };
+  if (need_x && need_y) { pass_u8(true, in, mid, (unsigned char*)ws); in = (const unsigned char*)ws; }
+  if (!ep) {
+    if (need_y) pass_u8(false, in, total_u8, (unsigned char*)dst);
+    else if (need_x) pass_u8(true, in, total_u8, (unsigned char*)dst);
+    else {
+      const hipError_t e = hipMemcpyAsync(dst, src, (size_t)total_u8, hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "%s: %s", name, hipGetErrorString(e));
+    }
+  } else {
+    const int mode = need_y ? 2 : need_x ? 1 : 0;
+    const ResampleAxis& a = need_y ? ay : need_x ? ax : none;
+    const int es = ep->dtype == TT_F32 ? 4 : 2;
+    const bool vec = (out_w & 3) == 0 && !((size_t)dst & (4 * es - 1)) && !((size_t)ep->noise & 15);
+    const dim3 grid((unsigned)((lanes + 255) / 256));
+#define TT_VI(TAG, MODE, VEC) hipLaunchKernelGGL((vae_image_kernel<TAG, MODE, VEC>), grid, block, 0, st, in, a, (int)out_h, (int)out_w, lanes, \
+                                                ep->noise, ep->na, ep->nvid, (char*)dst)
+#define TT_VIM(TAG, VEC) do { if (mode == 0) TT_VI(TAG, 0, VEC); else if (mode == 1) TT_VI(TAG, 1, VEC); else TT_VI(TAG, 2, VEC); } while (0)
+#define TT_VIV(TAG) do { if (vec) TT_VIM(TAG, true); else TT_VIM(TAG, false); } while (0)
+    if (ep->dtype == TT_BF16) TT_VIV(bf16_tag); else if (ep->dtype == TT_F16) TT_VIV(f16_tag); else TT_VIV(f32_tag);
+#undef TT_VIV
+#undef TT_VIM
+#undef TT_VI
+  }
+  TT_CHECK_LAUNCH(name);
+  return TT_OK;
+}
+}  // namespace
+
+extern "C" size_t tt_resize_u8_ws_bytes(int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w) {
+  return resample_ws_bytes(nimg, h, w, out_h, out_w);
+}
+extern "C" size_t tt_vae_image_ws_bytes(int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w) {
+  return resample_ws_bytes(nimg, h, w, out_h, out_w);
+}
+
+extern "C" int tt_resize_u8(const void* src, int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w, const int32_t* tab_x,
+                            int32_t ksize_x, const int32_t* tab_y, int32_t ksize_y, void* dst, void* ws, size_t ws_bytes, tt_stream_t stream) {
+  return resample_run("tt_resize_u8", src, nimg, h, w, out_h, out_w, tab_x, ksize_x, tab_y, ksize_y, dst, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int tt_vae_image(const void* src, int32_t nimg, int32_t h, int32_t w, int32_t out_h, int32_t out_w, const int32_t* tab_x,
+                            int32_t ksize_x, const int32_t* tab_y, int32_t ksize_y, const float* noise, float na, int32_t nvid, void* dst,
+                            int32_t dtype, void* ws, size_t ws_bytes, tt_stream_t stream) {
+  const VaeEpilogue ep = {noise, na, nvid, dst, dtype};
+  return resample_run("tt_vae_image", src, nimg, h, w, out_h, out_w, tab_x, ksize_x, tab_y, ksize_y, nullptr, &ep, ws, ws_bytes, stream);
 }

@@ -773,3 +773,106 @@ def gesture_maps(records, nmaps: int, frames: int, org_hw, out_hw, dilate: bool,
                                   _p(out), _code(dtype), _p(ws), need, _stream()), "tt_gesture_maps")
     _wrote(out)
     return out
+
+
+# ---- the request image: PIL's 8-bit resize and the VAE input computed from it (tt_resample_coeffs / tt_resize_u8 / tt_vae_image)
+RESAMPLE = {"lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}          # PIL.Image.Resampling's codes
+_RESAMPLE_TABLES = {}          # (in, out, filter, device) -> (device table, ksize), least recently used first
+RESAMPLE_TABLES_MAX = 64       # a few KiB each; a caller whose image sizes keep changing rebuilds tables instead of piling them up
+
+
+def _resample_code(resample) -> int:
+    code = RESAMPLE.get(resample.lower()) if isinstance(resample, str) else resample
+    if isinstance(code, bool) or not isinstance(code, int) or code not in RESAMPLE.values():
+        raise RuntimeError(f"resample {resample!r}: one of {sorted(RESAMPLE)} (or PIL's code of one of them)")
+    return code
+
+
+def resample_coeffs(in_size: int, out_size: int, resample="lanczos"):
+    """The tables PIL's 8-bit resampler builds for one axis (tt_resample_coeffs; host only, no device): ``(ksize, bounds, kk)`` with
+    bounds int32 [out_size, 2] = (first source index, taps) and kk int32 [out_size, ksize], the taps in 2^-22 fixed point."""
+    import numpy as np
+    lib = _lib.load()
+    code, ksize = _resample_code(resample), C.c_int32(0)
+    check(lib.tt_resample_coeffs(int(in_size), int(out_size), code, C.byref(ksize), None, None), "tt_resample_coeffs")
+    bounds, kk = np.empty((int(out_size), 2), np.int32), np.empty((int(out_size), ksize.value), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    check(lib.tt_resample_coeffs(int(in_size), int(out_size), code, C.byref(ksize), bounds.ctypes.data_as(i32p), kk.ctypes.data_as(i32p)),
+          "tt_resample_coeffs")
+    return ksize.value, bounds, kk
+
+
+def _resample_table(in_size: int, out_size: int, code: int, device):
+    """(device table, ksize) of one axis in the layout the kernels read (include/ttvdm.h: [out] first, [out] taps, [ksize][out] kk),
+    (None, 0) for an axis that keeps its size.  Built and uploaded once per (in, out, filter, device); the RESAMPLE_TABLES_MAX most
+    recently used are kept."""
+    if in_size == out_size:
+        return None, 0
+    key = (int(in_size), int(out_size), code, torch.device(device))
+    hit = _RESAMPLE_TABLES.pop(key, None)
+    if hit is None:
+        import numpy as np
+        ksize, bounds, kk = resample_coeffs(in_size, out_size, code)
+        hit = (torch.from_numpy(np.ascontiguousarray(np.concatenate([bounds.T, kk.T], 0))).to(device), ksize)
+    _RESAMPLE_TABLES[key] = hit                       # (re)inserted last: the most recently used
+    while len(_RESAMPLE_TABLES) > RESAMPLE_TABLES_MAX:
+        # dropped, not retired like a workspace: the launches already on the stream keep the memory alive (the caching allocator reuses
+        # a block in stream order); a captured graph must hold its own reference to the tables it replays
+        del _RESAMPLE_TABLES[next(iter(_RESAMPLE_TABLES))]
+    return hit
+
+
+def _resample_args(name, src, size, resample):
+    _p(src)
+    if src.dtype != torch.uint8 or src.dim() not in (3, 4) or src.shape[-1] != 3:
+        raise RuntimeError(f"{name}: the source is uint8 [N, H, W, 3] (or [H, W, 3]), got {src.dtype} {tuple(src.shape)}")
+    src = (src[None] if src.dim() == 3 else src).contiguous()
+    n, h, w = src.shape[:3]
+    oh, ow = int(size[0]), int(size[1])
+    if min(n, h, w, oh, ow) <= 0:
+        raise RuntimeError(f"{name}: {n} image(s) of {h} x {w} -> {oh} x {ow}, every size must be positive")
+    code = _resample_code(resample)
+    tx, kx = _resample_table(w, ow, code, src.device)
+    ty, ky = _resample_table(h, oh, code, src.device)
+    return src, (n, h, w, oh, ow), (tx, kx, ty, ky)             # the tensors, not their addresses: the caller holds them across its launch
+
+
+def resize_u8(src, size, resample="lanczos"):
+    """``PIL.Image.resize((size[1], size[0]), resample)`` of RGB images on the device, byte for byte (tt_resize_u8): src uint8
+    [N, H, W, 3] (or [H, W, 3]) -> uint8 [N, size[0], size[1], 3].  resample: "box", "bilinear", "hamming", "bicubic" or "lanczos"."""
+    lib = _lib.load()
+    src, dims, tabs = _resample_args("resize_u8", src, size, resample)
+    out = torch.empty((dims[0], dims[3], dims[4], 3), dtype=torch.uint8, device=src.device)
+    need = lib.tt_resize_u8_ws_bytes(*dims)
+    ws = _workspace(need, src.device) if need else None
+    tx, kx, ty, ky = tabs
+    check(lib.tt_resize_u8(_p(src), *dims, _p(tx), kx, _p(ty), ky, _p(out), _p(ws), need, _stream()), "tt_resize_u8")
+    _wrote(out)
+    return out
+
+
+def vae_image(src, size, noise, noise_aug_strength, dtype, videos_per_image: int = 1, resample="lanczos"):
+    """The VAE input of a request from its uint8 pixels (tt_vae_image): PIL's resize to `size`, ``2 * (u / 255) - 1``, each image
+    repeated for its ``videos_per_image`` requests, ``+ noise_aug_strength * noise`` and the cast to `dtype` -- what
+    ``VaeImageProcessor.preprocess``, ``repeat_interleave``, the noise augmentation and ``.to(dtype)`` compute, bit for bit.
+    src uint8 [N, H, W, 3] (or [H, W, 3]); noise float32 [N * videos_per_image, 3, size[0], size[1]] on the device, or None.
+    -> [N * videos_per_image, 3, size[0], size[1]] in `dtype`."""
+    lib = _lib.load()
+    src, dims, tabs = _resample_args("vae_image", src, size, resample)
+    nvid = int(videos_per_image)
+    if nvid < 1:
+        raise RuntimeError(f"vae_image: {videos_per_image} videos per image")
+    shape = (dims[0] * nvid, 3, dims[3], dims[4])
+    if noise is not None:
+        _p(noise)
+        if noise.dtype != torch.float32 or tuple(noise.shape) != shape or noise.device != src.device:
+            raise RuntimeError(f"vae_image: noise must be float32 {shape} on {src.device}, got {noise.dtype} {tuple(noise.shape)} on {noise.device}")
+        noise = noise.contiguous()
+    out = torch.empty(shape, dtype=dtype, device=src.device)
+    need = lib.tt_vae_image_ws_bytes(*dims)
+    ws = _workspace(need, src.device) if need else None
+    tx, kx, ty, ky = tabs
+    check(lib.tt_vae_image(_p(src), *dims, _p(tx), kx, _p(ty), ky, _p(noise), float(noise_aug_strength), nvid, _p(out), _code(dtype), _p(ws), need, _stream()),
+          "tt_vae_image")
+    _wrote(out)
+    return out

@@ -8,7 +8,9 @@ LayerNorm((78,1024)) (reference :165-173), un-scaled VAE ``.mode()`` latents (:2
 ``latents=``, ``generator=``, ``callback_on_step_end``, a list of images and ``num_videos_per_prompt`` (one call carries
 R = images x videos-per-image independent requests, image-major; every video is what a call of its own would give -- DESIGN.md section 8).
 Opt-in (``native_image_io=True``, default off): the CLIP image preprocessing, the use_text context LayerNorm and the export of decoded
-frames run on the library's kernels (ops.clip_image / layernorm_block / frames_out) instead of stock torch ops.
+frames run on the library's kernels (ops.clip_image / layernorm_block / frames_out) instead of stock torch ops; RGB PIL / uint8 images
+are uploaded once, as uint8, and the VAE input (PIL's LANCZOS resize, 2 x - 1, the noise augmentation) is ops.vae_image on that upload;
+``image=DevicePixels(...)`` takes pixels that are on the device already.
 ``use_instructpix2pix`` (CFG batch of 3, reference :182-184,208-210,698-702) and ``guess_mode`` without CFG are built;
 ``guess_mode`` with CFG raises, as the reference's branch (:676-681) cannot run either.
 Changed on purpose: the gesture map is VAE-encoded ONCE per request instead of inside every step (reference :652 --
@@ -25,7 +27,7 @@ import torch.nn as nn
 from .. import ops
 from ..gesture_map import GesturePoints, rasterise_points_device
 from .denoise import DenoiseLoop
-from .pipeline_utils import (CLIPFeatureExtractor, PipelineBase, StableVideoDiffusionPipelineOutput, VaeImageProcessor,
+from .pipeline_utils import (CLIPFeatureExtractor, DevicePixels, PipelineBase, StableVideoDiffusionPipelineOutput, VaeImageProcessor,
                              append_dims, randn_tensor, resize_with_antialiasing, tensor2vid)
 from .temporal_controlnet import ControlNetModel
 
@@ -133,6 +135,8 @@ class _SVDPipelineCore(PipelineBase):
         refuses anything else, where the torch path would hand a grayscale / RGBA array on to the encoder."""
         if self.feature_extractor is None:
             raise RuntimeError(_NO_FEATURE_EXTRACTOR)
+        if isinstance(image, DevicePixels):                     # the request's one upload (_request_pixels), or the caller's own pixels
+            return ops.clip_image(image.pixels, (224, 224), self.feature_extractor.image_mean, self.feature_extractor.image_std, dtype)
         ims = [np.asarray(im) for im in (image if isinstance(image, (list, tuple)) else [image])]
         arr = np.stack([im[..., None] if im.ndim == 2 else im for im in ims], 0)
         if arr.dtype == np.uint8:
@@ -140,6 +144,24 @@ class _SVDPipelineCore(PipelineBase):
         else:
             src = self.image_processor.numpy_to_pt(arr.astype(np.float32) / 255.0).contiguous().to(device)
         return ops.clip_image(src, (224, 224), self.feature_extractor.image_mean, self.feature_extractor.image_std, dtype)
+
+    def _request_pixels(self, image, device):
+        """The uint8 pixels of a request on the device, uploaded ONCE for both of their readers (_clip_image_native and ops.vae_image),
+        when ``native_image_io`` is on and the image is what the kernels take: DevicePixels, RGB PIL image(s), or a list of uint8
+        [H, W, 3] arrays.  None otherwise (tensors, float arrays, other PIL modes, the option off): today's host path, unchanged."""
+        if isinstance(image, DevicePixels):
+            if not self.native_image_io:
+                raise ValueError("image=DevicePixels needs a pipeline with native_image_io=True: the torch request path starts from host "
+                                 "images (PIL / numpy / tensor)")
+            return image if image.device == torch.device(device) else DevicePixels(image.pixels.to(device))
+        if not self.native_image_io:
+            return None
+        ims = image if isinstance(image, list) else [image]
+        if not ims or not all((isinstance(im, PIL.Image.Image) and im.mode == "RGB" and im.size == ims[0].size)
+                              or (isinstance(im, np.ndarray) and im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3
+                                  and im.shape == ims[0].shape) for im in ims):
+            return None
+        return DevicePixels.from_pil(ims, device)
 
     def _encode_vae_image(self, image, device, num_videos_per_prompt, do_classifier_free_guidance, use_instructpix2pix=False):
         lat = self.vae.encode(image.to(device=device)).latent_dist.mode()
@@ -190,7 +212,7 @@ class _SVDPipelineCore(PipelineBase):
         return [[PIL.Image.fromarray(im.squeeze(-1) if im.shape[-1] == 1 else im) for im in video] for video in arr]
 
     def check_inputs(self, image, height, width):
-        if not isinstance(image, (torch.Tensor, PIL.Image.Image, list)):
+        if not isinstance(image, (torch.Tensor, PIL.Image.Image, list, DevicePixels)):
             raise ValueError("`image` has to be of type `torch.FloatTensor` or `PIL.Image.Image` or `List[PIL.Image.Image]` "
                              f"but is {type(image)}")
         if height % 8 != 0 or width % 8 != 0:
@@ -270,17 +292,26 @@ class _SVDPipelineCore(PipelineBase):
             if cond.ndim not in (4, 5) or cond.shape[-4] != num_frames or (cond.ndim == 5 and cond.shape[0] != batch_size):
                 raise ValueError(f"condition_img {tuple(cond.shape)}: expected [F,3,H,W] (shared by every request) or one [F,3,H,W] map per "
                                  f"image, [{batch_size},F,3,H,W], with F = {num_frames}")
-        ehs = self.encode_clip(image, prompt, use_text, text_encoder, device, nvid, do_cfg, ip2p)
+        pixels = self._request_pixels(image, device)
+        ehs = self.encode_clip(image if pixels is None else pixels, prompt, use_text, text_encoder, device, nvid, do_cfg, ip2p)
         if ehs.shape[0] != nreq * (1 if not do_cfg else 3 if ip2p else 2):
             raise ValueError(f"encode_clip returned {ehs.shape[0]} contexts for {nreq} request(s)")
         fps = fps - 1                                                            # SVD was conditioned on fps-1 (:527)
-        img = self.image_processor.preprocess(image, height=height, width=width)
-        if nvid > 1:
-            # every request noises its own copy of its image, as a call of its own would: generator r draws for request r.  (The reference
-            # noises once per image and then tiles cat([neg, lat]) with repeat (:211-214), which pairs videos with the wrong class.)
-            img = img.repeat_interleave(nvid, 0)
-        img = img + noise_aug_strength * randn_tensor(img.shape, generator=generator, device=img.device, dtype=img.dtype)
         upcast = self.vae.dtype == torch.float16 and getattr(self.vae.config, "force_upcast", False)
+        if pixels is None:
+            img = self.image_processor.preprocess(image, height=height, width=width)
+            if nvid > 1:
+                # every request noises its own copy of its image, as a call of its own would: generator r draws for request r.  (The
+                # reference noises once per image and then tiles cat([neg, lat]) with repeat (:211-214), which pairs videos with the wrong class.)
+                img = img.repeat_interleave(nvid, 0)
+            img = img + noise_aug_strength * randn_tensor(img.shape, generator=generator, device=img.device, dtype=img.dtype)
+        else:
+            # the same draw as above -- same generator, shape, dtype and device of generation (a CPU or no generator draws on the host) --
+            # handed to the kernel on the device; the kernel resizes, normalises, repeats each image for its videos (request r reads image
+            # r // nvid), adds the noise and writes the dtype the VAE has inside the force_upcast window
+            noise = randn_tensor((nreq, 3, height, width), generator=generator, device=torch.device("cpu") if generator is None else device,
+                                 dtype=torch.float32).to(device)
+            img = ops.vae_image(pixels.pixels, (height, width), noise, noise_aug_strength, torch.float32 if upcast else self.vae.dtype, nvid)
         if upcast:
             self.vae.to(dtype=torch.float32)
         # one image per request already: the CFG classes are concatenated around the R latents (class by class, the loop's order)

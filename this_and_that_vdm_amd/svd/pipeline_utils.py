@@ -127,6 +127,51 @@ def resize_with_antialiasing(img: torch.Tensor, size, interpolation: str = "bicu
     return F.interpolate(out, size=size, mode=interpolation, align_corners=align_corners)
 
 
+def upload_pixels(arr: np.ndarray, device) -> torch.Tensor:
+    """THE host-to-device copy of a request's pixels: uint8 [N, H, W, 3], once (everything downstream reads this tensor)"""
+    return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+
+
+class DevicePixels:
+    """The RGB pixels of a request's image(s) on the device: uint8 [N, H, W, 3], what ``np.asarray`` of a PIL RGB image holds and what
+    ``ops.frames_out(kind=1)`` returns -- a camera frame, a simulator's render or the last generated frame goes back into a pipeline
+    built with ``native_image_io=True`` as ``image=DevicePixels(frame)`` without a trip through PIL.  ``resize`` and ``flip`` are what
+    the reference's callers do to the PIL image before the pipeline sees it (test_code/inference.py:83,198: ``resize((w, h))``,
+    PIL's BICUBIC; ``transpose(FLIP_LEFT_RIGHT)``), byte for byte."""
+
+    def __init__(self, pixels: torch.Tensor):
+        if not torch.is_tensor(pixels) or pixels.dtype != torch.uint8 or pixels.dim() not in (3, 4) or pixels.shape[-1] != 3:
+            raise ValueError("DevicePixels holds uint8 RGB pixels, [N, H, W, 3] or [H, W, 3]")
+        if not pixels.is_cuda:
+            raise ValueError("DevicePixels holds pixels on the device; DevicePixels.from_pil(images, device) uploads host images")
+        self.pixels = (pixels[None] if pixels.dim() == 3 else pixels).contiguous()
+
+    @classmethod
+    def from_pil(cls, images, device) -> "DevicePixels":
+        """PIL RGB image(s) or uint8 [H, W, 3] array(s) of one size -> one upload"""
+        arrs = [np.asarray(im) for im in (images if isinstance(images, (list, tuple)) else [images])]
+        if not arrs or any(a.dtype != np.uint8 or a.ndim != 3 or a.shape != (*arrs[0].shape[:2], 3) for a in arrs):
+            raise ValueError("DevicePixels.from_pil: RGB images (uint8 [H, W, 3]) of one size; convert other modes with .convert('RGB')")
+        return cls(upload_pixels(np.stack(arrs, 0), device))
+
+    @property
+    def shape(self):
+        return self.pixels.shape
+
+    @property
+    def device(self):
+        return self.pixels.device
+
+    def resize(self, size, resample: str = "bicubic") -> "DevicePixels":
+        """``PIL.Image.resize((size[1], size[0]), resample)`` of every image; size = (height, width)"""
+        from .. import ops
+        return DevicePixels(ops.resize_u8(self.pixels, size, resample))
+
+    def flip(self) -> "DevicePixels":
+        """``transpose(FLIP_LEFT_RIGHT)`` of every image"""
+        return DevicePixels(self.pixels.flip(2))
+
+
 class _PixelValues(dict):
     """BatchFeature-like: ``.pixel_values`` and ``["pixel_values"]``."""
 
