@@ -309,6 +309,15 @@ int tt_groupnorm_apply(const void* x0, int32_t c0, const void* x1, int32_t c1, i
  * ResnetBlock2D norm1 / norm2 (diffusers resnet.py), TransformerSpatioTemporalModel.norm (transformer_temporal.py:323),
  * conv_norm_out (unet...:526). */
 int tt_groupnorm_small_supported(int32_t hw, int32_t c, int32_t dtype);
+/* Which kernels a GroupNorm of hw rows x c channels per image runs (host only; the launchers take their decisions from the same code).
+ * one_launch != 0: tt_groupnorm_small -- TT_GN_ROUTE_GROUPED (gn_group_kernel, one block per image and group slice), TT_GN_ROUTE_IMAGE
+ * (gn_stats_image_kernel, one block per image and row part) or 0 (not served: frames_per_group must be 1).  one_launch == 0:
+ * tt_groupnorm_stats -- TT_GN_ROUTE_IMAGE (gn_stats_image_kernel writes scale / shift) or TT_GN_ROUTE_PARTIAL (gn_partial_kernel +
+ * gn_finalize_kernel).  0 for channel counts no GroupNorm entry point accepts.  For launch traces and tests. */
+#define TT_GN_ROUTE_IMAGE 1
+#define TT_GN_ROUTE_GROUPED 2
+#define TT_GN_ROUTE_PARTIAL 3
+int tt_groupnorm_route(int32_t hw, int32_t c, int32_t dtype, int32_t frames_per_group, int32_t one_launch);
 int tt_groupnorm_small(const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t nimg, int32_t hw,
                        const float* gamma, const float* beta, float eps, int32_t silu, void* y, int64_t ldy,
                        int32_t dtype, tt_stream_t stream);

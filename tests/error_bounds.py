@@ -1,7 +1,8 @@
-"""Per-element error bounds for the dense contractions of libttvdm (tt_gemm's routes, tt_conv3x3), derived beforehand from the operands
+"""Per-element error bounds for the dense contractions of libttvdm (tt_gemm's routes, tt_conv3x3) and for its normalisations (every
+GroupNorm / LayerNorm route, the producers' tile sums: see groupnorm(), layernorm(), tile_sums() below), derived beforehand from the operands
 a kernel read and the arithmetic it is documented to do -- never fitted to measured errors.  A plain module (not a conftest): used by
-tests/test_error_bounds_cpu.py (the bound against emulated correct and deliberately wrong kernels) and tests/test_error_bounds_gpu.py
-(every GEMM route against it).
+tests/test_error_bounds_cpu.py (the bound against emulated correct and deliberately wrong kernels), tests/test_error_bounds_gpu.py
+(every GEMM route against it) and tests/test_norm_bounds_gpu.py (every normalisation route against it).
 
 For one output element with storage unit roundoff u_s (bf16 2^-8, fp16 2^-11, fp32 2^-24), u = 2^-24, K products a_k w_k and
 S = sum_k |a_k| |w_k|:
@@ -205,6 +206,17 @@ def check(got: torch.Tensor, b: Bound, dtype, what: str = "") -> float:
     return worst
 
 
+def ratio(got: torch.Tensor, b: Bound, dtype) -> float:
+    """check()'s figure without the assertion: max over the elements of |got - ref| / limit (inf for a non-finite output) -- for tests that
+    record every case of a sweep before they assert"""
+    us = UNIT[dtype]
+    g = got.to(b.ref.device).double()
+    lim = us * b.ref.abs() + (1 + us) * b.err + ABS_FLOOR.get(dtype, 0.0)
+    err = (g - b.ref).abs()
+    err = torch.where(torch.isfinite(g), err, torch.full_like(err, math.inf))
+    return float(torch.where(err == 0, torch.zeros_like(err), err / lim).max())
+
+
 # ---- operands whose magnitudes span decades
 
 def col_exponents(n: int) -> torch.Tensor:
@@ -232,3 +244,192 @@ def scaled(shape, cs: torch.Tensor, dtype, seed: int) -> torch.Tensor:
     """randn of `shape` with the last dim scaled by the column scales cs"""
     g = torch.Generator().manual_seed(seed)
     return (torch.randn(*shape, generator=g, dtype=torch.float64) * cs).to(dtype)
+
+
+# ---- GroupNorm / LayerNorm: reference and budget
+
+GN_GROUPS = 32
+RHO_GRID = (0, 5, 50, 300)         # |group mean| / group spread: the ratios of the fused-LayerNorm analysis in gemm_kernel.h and of its test
+GN_GUARD_RATIO, GN_GUARD_RATIO_TILES = 64.0, 4.0      # the conditioning guard of norm.hip -- keep in step
+GUARD_MARGIN = 1.0 + 2.0 ** -8
+SECOND_ORDER = 1.0 + 2.0 ** -10    # the budgets below are first order in u; the products of two roundings they drop are < 2^-20 of them
+
+
+def _activate(t: torch.Tensor, e_t: torch.Tensor, silu: bool):
+    """y = silu?(t) and its fp32 budget from the budget e_t of t: through |silu'| <= 1.1, plus silu_f's own 8u |y| (division, 1 + e,
+    exp2) and u |t| |y| (the rounded argument of exp2) -- the figures conv3x3_formed_err states"""
+    if not silu:
+        return t, e_t
+    y = t * torch.sigmoid(t)
+    return y, 1.1 * e_t + (8 * U + U * t.abs()) * y.abs()
+
+
+def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, *, seg_rows: int, silu: bool,
+              n_adds: int = 0, guard: float = math.inf, groups: int = GN_GROUPS) -> Bound:
+    """GroupNorm of the token-major tensor x [nseg * seg_rows, C] (STORED values; two sources already concatenated), statistics per
+    (segment of seg_rows rows, group of C / groups channels) -- one image, or the frames x hw rows of one video.
+
+    Reference (fp64): the exact population mean mu and variance s2 of each (segment, group), r = 1 / sqrt(s2 + eps) with eps the fp32
+    number the kernel receives, t = (x - mu) r gamma + beta, y = silu?(t).
+
+    Budget, from the arithmetic norm.hip and gemm_kernel.h state for EVERY GroupNorm route ("statistics in fp32 with fp64 block / group
+    combination", then s_mean = (float)mean, s_rstd = (float)(1 / sqrt(var + eps)), sc = s_rstd * gamma, sh = beta - s_mean * sc,
+    t = fmaf(x, sc, sh)): the fp64 statistics are taken as exact, so mu and r each carry ONE fp32 rounding, |d| <= u = 2^-24:
+        mu^ = mu (1 + d1),  r^ = r (1 + d2)
+        sc  = fl(r^ gamma)      = r gamma (1 + d2)(1 + d3)
+        m   = fl(mu^ sc)        = mu r gamma (1 + d1)(1 + d2)(1 + d3)(1 + d4)
+        sh  = fl(beta - m)      = (beta - m)(1 + d5)            (an fma here drops d4: covered)
+        t^  = fl(x sc + sh)     = (x sc + sh)(1 + d6)
+    With P = |x r gamma| and M = |mu r gamma|, to first order:  |x sc - x r gamma| <= 2u P,  |m - mu r gamma| <= 4u M,
+    |sh - (beta - mu r gamma)| <= 4u M + u (|beta| + M),  and the last rounding adds u |t|:
+        |t^ - t| <= u (2 P + 5 M + |beta| + |t|)
+    Linear in rho = |mu| / sigma (M <= rho |gamma|), never quadratic: a kernel whose variance loses digits to E[x^2] - mean^2 in fp32
+    -- an error of order u rho^2 -- is outside it by construction.  Through SiLU: _activate().  check() adds the half ulp of the
+    storage type at |y|.
+
+    n_adds and guard, the one term beyond "mu correct to one fp32 rounding".  The lowest level of every route's sums but one IS fp32 -- a
+    thread's running sum over its n_adds rows in the statistics-pass kernels, a producer's chain over the n_adds rows of a tile -- and a
+    sum of values x_i formed that way is off by up to n_adds u sum |x_i| (the fp64 levels above add nothing), so the mean such sums give is
+        |mean^ - mu| <= n_adds u A,   A = the group's mean |x|,   which enters t as   n_adds u A r |gamma|
+    That holds ONLY for a group whose statistics the kernel takes from those sums: one below the conditioning guard of norm.hip,
+    E[x^2] <= guard x var (guard = GN_GUARD_RATIO for the statistics-pass kernels, GN_GUARD_RATIO_TILES for tt_groupnorm_tiles).  Above
+    the guard the kernel recomputes the group centred, in fp64, and its mean carries the one rounding again: no term.  So A <= sqrt(guard)
+    sigma wherever the term applies -- it cannot grow with rho, and at rho = 50 or 300 the budget is the one above, unchanged.  The
+    reference decides from its own exact E[x^2] / var, widened by GUARD_MARGIN (the kernel's ratio comes from the fp32 sums, off by up to
+    2 n_adds u E[x^2] / var <= 2^-9 of itself at 256 additions and guard 64; a group that close to the guard may be on either side).
+    n_adds = 0: fp64 from the first addition (splitk_epilogue_gn_kernel).  The SAME sums cost the variance n_adds u (s2 + mu^2): that is
+    the rho^2 term, and it stays out."""
+    x = x.double()
+    rows, c = x.shape
+    cpg, nseg = c // groups, rows // seg_rows
+    assert c % groups == 0 and rows % seg_rows == 0, (rows, c, seg_rows)
+    xg = x.view(nseg, seg_rows, groups, cpg)
+    mu = xg.mean((1, 3), keepdim=True)
+    s2 = (xg - mu).square().mean((1, 3), keepdim=True)
+    r = (s2 + f32(eps)).rsqrt()
+    g, b = gamma.double().to(x.device).view(1, 1, groups, cpg), beta.double().to(x.device).view(1, 1, groups, cpg)
+    t = (xg - mu) * r * g + b
+    from_fp32_sums = (s2 + mu * mu) <= guard * GUARD_MARGIN * s2              # (never true for a constant group: s2 = 0 < E[x^2])
+    a_mean = torch.where(from_fp32_sums, xg.abs().mean((1, 3), keepdim=True), torch.zeros_like(s2))
+    e = U * SECOND_ORDER * (2 * (xg * r * g).abs() + 5 * (mu * r * g).abs() + b.abs() + t.abs() + n_adds * a_mean * r * g.abs())
+    y, e = _activate(t, e, silu)
+    return Bound(y.reshape(rows, c), e.reshape(rows, c))
+
+
+def layernorm(x: torch.Tensor, gamma, beta, eps: float, *, n_adds: int, pivot=None) -> Bound:
+    """LayerNorm of every row of x [rows, n] (STORED values) in the CENTRED form ln_kernel (norm.hip) and ln_block_kernel (image.hip; one
+    "row" = one [rows, c] block, gamma = beta = None) run:  mean = sum / n,  d = x - mean,  var = sum d^2 / n,
+    rstd = 1 / sqrt(var + eps),  y = d rstd gamma + beta, all in fp32.
+
+    n_adds: the fp32 additions on the longest path of the kernel's sums (ln_kernel: 8 values per 8-channel vector, ceil(n / 512)
+    vectors per lane, then 6 xor-shuffle levels -- ln_adds(); ln_block_kernel: 8 ceil(n / 2048) per thread plus the subtraction of the
+    pivot, fp64 across threads -- ln_block_adds()).  pivot [rows] or None: ln_block_kernel sums x - pivot (the block's first element).
+    With A = mean |x - pivot| (pivot 0 for ln_kernel), mu the exact mean, d = x - mu, s2 = mean d^2, r = 1 / sqrt(s2 + eps):
+        dm   = n_adds u A + u |mu|                       |mean^ - mu|: the sum, then the division (or the fp64 -> fp32 conversion)
+        d^   = fl(x - mean^):  |d^ - d| <= dm + u |d|
+        sum d^^2 - sum d^2 = n dm'^2 - 2 dm' sum d + O(u) sum d^2 and sum d = 0 EXACTLY: the error of the mean enters the variance
+                              only squared -- the centred form has no cancellation, which is why this budget is tighter than the
+                              GroupNorm one wherever the mean is large: its var term is u s2, not u (s2 + mu^2)
+        dvar = (n_adds + 3) u (s2 + dm^2) + dm^2         2u for d^^2, n_adds u for the chain, u for the division
+        rel  = (dvar + u (s2 + eps)) / (2 (s2 + eps)) + 2u       relative error of rstd (the addition rounds; rsqrt is faithful), as ln_rstd
+        |y^ - y| <= (dm + u |d|) r |gamma| + |d r gamma| (rel + 2u) + u |y|        two products and the final addition (or one fma)
+    """
+    x = x.double()
+    n = x.shape[1]
+    p = torch.zeros(x.shape[0], dtype=torch.float64, device=x.device) if pivot is None else pivot.double().to(x.device)
+    mu = x.mean(1, keepdim=True)
+    d = x - mu
+    s2 = d.square().mean(1, keepdim=True)
+    e32 = f32(eps)
+    r = (s2 + e32).rsqrt()
+    g = torch.ones(n, dtype=torch.float64, device=x.device) if gamma is None else gamma.double().to(x.device)
+    b = torch.zeros(n, dtype=torch.float64, device=x.device) if beta is None else beta.double().to(x.device)
+    dm = n_adds * U * (x - p[:, None]).abs().mean(1, keepdim=True) + U * mu.abs()
+    dvar = (n_adds + 3) * U * (s2 + dm * dm) + dm * dm
+    rel = (dvar + U * (s2 + e32)) / (2 * (s2 + e32)) + 2 * U
+    drg = (d * r * g).abs()
+    y = d * r * g + b
+    e = SECOND_ORDER * ((dm + U * d.abs()) * r * g.abs() + drg * (rel + 2 * U) + U * y.abs())
+    return Bound(y, e)
+
+
+def ln_adds(n: int) -> int:
+    """ln_kernel: a lane adds the 8 values of each of its ceil(n / 512) vectors in turn, then 6 xor-shuffle levels"""
+    return 8 * ((n // 8 + 63) // 64) + 6
+
+
+def ln_block_adds(rows: int, n: int) -> int:
+    """ln_block_kernel: thread t adds the 8 values of vectors t, t + 256, .. of the block (fp32), each after subtracting the pivot (one
+    more rounding per value, counted once on the path); the 256 threads then meet in fp64"""
+    return 8 * ((rows * (n // 8) + 255) // 256) + 1
+
+
+def tile_sums(x: torch.Tensor, tile_rows: int, n_adds=None) -> Bound:
+    """the producers' GroupNorm tile sums (TtGemmArgs.stats_out): [rows / R, 2, C] = per tile of R rows and per column the sum and the
+    sum of squares of the STORED output.  Summation orders, from the producers' comments: colstat_strip (gemm_kernel.h; the tiled
+    template and both 320-wide kernels) adds the 32 rows of a strip one after the other from 0, a wave chains its fragment rows
+    (read-add-store), w3_stats_tile / the tiled template's tile step chain the waves of a tile column; splitk_epilogue_stats_kernel gives
+    row r to lane r % 32 and then adds the 32 lanes in order.  Every one of them is a fixed tree over the R values of a column, so no
+    value passes more than R - 1 additions (the fully sequential chain), and for ANY order of n_adds roundings on the longest path
+        |S^ - S| <= n_adds u sum |x|,      |Q^ - Q| <= n_adds u sum x^2      (x^2 enters through an fma: no rounding of its own)
+    n_adds defaults to R (R - 1 additions and the store).  check(..., torch.float32) adds the last half ulp."""
+    x = x.double()
+    rows, c = x.shape
+    n_adds = tile_rows if n_adds is None else n_adds
+    xt = x.view(rows // tile_rows, tile_rows, c)
+    ref = torch.stack([xt.sum(1), xt.square().sum(1)], 1)
+    err = n_adds * U * SECOND_ORDER * torch.stack([xt.abs().sum(1), xt.square().sum(1)], 1)
+    return Bound(ref, err)
+
+
+# ---- normalisation inputs: per (segment, group) mean and spread, the mean rho spreads away from zero
+
+CONST_FACTOR = math.pi / 3
+CONST_GROUP, TINY_GROUP = 5, 11     # group 5 of every segment is constant; group 11 has spread 2^-9 (spread^2 = 3.8e-6, eps = 1e-5)
+
+
+def norm_input(nseg: int, seg_rows: int, c: int, rho: float, dtype, seed: int, device="cpu", groups: int = GN_GROUPS) -> torch.Tensor:
+    """x [nseg * seg_rows, c] = spread * randn + mean per (segment s, group g), rounded to `dtype`: spread 2^((g + 3 s) % 7 - 3) (2^-3 .. 2^3;
+    consecutive segments and consecutive groups differ), mean = (-1)^g rho spread.  Group CONST_GROUP is constant, at
+    (-1)^g max(rho, 1) spread (pi / 3) (1 + s / 7) (full fp32 mantissas, another one in every segment: their fp32 squares and sums round), group TINY_GROUP has spread 2^-9."""
+    cpg = c // groups
+    gen = torch.Generator(device=device).manual_seed(seed)
+    z = torch.randn(nseg, seg_rows, groups, cpg, generator=gen, dtype=torch.float64, device=device)
+    s = torch.arange(nseg, device=device)[:, None]
+    k = torch.arange(groups, device=device)[None, :]
+    spread = torch.exp2(((k + 3 * s) % 7 - 3).double())
+    sign = 1.0 - 2.0 * (k % 2).double()
+    mean = sign * rho * spread
+    tiny, const = (k == TINY_GROUP).expand_as(spread), (k == CONST_GROUP).expand_as(spread)
+    mean = torch.where(tiny, sign * rho * 2.0 ** -9, mean)
+    mean = torch.where(const, sign * max(rho, 1.0) * spread * CONST_FACTOR * (1.0 + s.double() / 7.0), mean)
+    spread = torch.where(tiny, torch.full_like(spread, 2.0 ** -9), spread)
+    spread = torch.where(const, torch.zeros_like(spread), spread)
+    x = z * spread[:, None, :, None] + mean[:, None, :, None]
+    return x.reshape(nseg * seg_rows, c).to(dtype)
+
+
+def norm_affine(c: int, seed: int):
+    """gamma, beta (fp32 [c]) with magnitudes cycled like col_exponents: gamma_j = +-2^e_j (1 + randn / 4), beta_j = 2^e_(j+4) randn"""
+    gen = torch.Generator().manual_seed(seed)
+    e = col_exponents(c)
+    sign = 1.0 - 2.0 * ((torch.arange(c) % 5) == 3).double()
+    gamma = sign * torch.exp2(e) * (1.0 + 0.25 * torch.randn(c, generator=gen, dtype=torch.float64))
+    beta = torch.exp2(col_exponents(c + 4)[4:]) * torch.randn(c, generator=gen, dtype=torch.float64)
+    return gamma.float(), beta.float()
+
+
+def ln_input(rows: int, n: int, rho: float, dtype, seed: int) -> torch.Tensor:
+    """LayerNorm rows: row i = 2^f_i randn + (-1)^i rho 2^f_i (f_i over -3 .. 3); row CONST_GROUP is constant (as in norm_input), row
+    TINY_GROUP has spread 2^-9"""
+    gen = torch.Generator().manual_seed(seed)
+    z = torch.randn(rows, n, generator=gen, dtype=torch.float64)
+    i = torch.arange(rows)
+    spread = torch.exp2(row_exponents(rows))
+    sign = 1.0 - 2.0 * (i % 2).double()
+    mean = sign * rho * spread
+    mean = torch.where(i == TINY_GROUP, sign * rho * 2.0 ** -9, mean)
+    mean = torch.where(i == CONST_GROUP, sign * max(rho, 1.0) * spread * CONST_FACTOR * (8.0 / 7.0), mean)
+    spread = torch.where(i == TINY_GROUP, torch.full_like(spread, 2.0 ** -9), spread)
+    spread = torch.where(i == CONST_GROUP, torch.zeros_like(spread), spread)
+    return (z * spread[:, None] + mean[:, None]).to(dtype)

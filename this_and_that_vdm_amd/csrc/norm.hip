@@ -1,5 +1,6 @@
 // GroupNorm (statistics -> per-(image,channel) affine -> apply+SiLU) and LayerNorm for token-major tensors.
-// All statistics in fp32 with fp64 block/group combination (inputs reach |x| ~ 1e2 after sigma scaling).
+// All statistics in fp32 with fp64 block/group combination (inputs reach |x| ~ 1e2 after sigma scaling); a group whose mean lies far
+// from zero against its spread is recomputed centred, in fp64 (the conditioning guard: GN_GUARD_RATIO below).
 #include "common.h"
 
 namespace {
@@ -13,6 +14,76 @@ __host__ __device__ inline int gn_rows_per_chunk(int C) {
   if (rpb < 1) rpb = 1;
   const int rows = rpb * 8;
   return rows > 128 ? 128 : rows;
+}
+
+// ---- the conditioning guard of every statistics route.  var = E[x^2] - mean^2 is formed from UNCENTRED sums whose lowest level is fp32:
+// a thread's running sums over its rows in the statistics-pass kernels (n <= 8 .. 16 additions each), the producers' tile sums in
+// gn_tiles_kernel (colstat_strip chains the 32 rows of a strip, the strips of a wave and the waves of a tile: n <= 256;
+// splitk_epilogue_stats_kernel n <= 35).  Each such sum is off by up to n u of itself (u = 2^-24), typically sqrt(n) u / 2, and the fp64
+// combination of P of them averages that to about sqrt(n / P) u / 2 of E[x^2] -- harmless against var while E[x^2] / var = 1 + rho^2
+// (rho = |mean| / sigma) is small, but it is an error of (1 + rho^2) sqrt(n / P) u / 2 RELATIVE TO var, against the u rho that the
+// rounding of mean and rstd to fp32 costs anyway.  The two meet near rho = 2 sqrt(P / n): P / n is 16 for the coarsest use (28 rows
+// x 40 channels, one row per thread; 7 tiles of 256 rows x 10 channels), so beyond rho = 8 -- E[x^2] > GN_GUARD_RATIO var -- the
+// block recomputes that group's statistics CENTRED on the uncentred mean, in fp64, from the rows (gn_centred_group).  A constant
+// group (var = 0 up to the rounding of its sums, which then decides rstd against eps and leaves mean off by n u / 2 of itself) is the
+// limit of that case.  The tile sums carry 16 to 32 times longer chains per sum than the per-thread sums, so their guard sits a
+// factor 16 lower (rho > 1.7): GN_GUARD_RATIO_TILES.  Below the guard nothing changes, bit for bit.
+constexpr double GN_GUARD_RATIO = 64.0, GN_GUARD_RATIO_TILES = 4.0;
+
+// centred statistics of channels [c_lo, c_lo + cpg) over `rows` rows from row `row0` of the token-major tensor (x0 | x1), by ALL
+// threads of the block (call under block-uniform control flow): sums of x - pivot and (x - pivot)^2 in fp64 -- thread t takes
+// one channel of the group and every (blockDim.x / cpg)-th row, lanes meet by xor shuffles, waves through red[32] in a fixed order
+// (bit-reproducible).  Every thread returns the same mean and variance.
+template <typename Tag>
+__device__ __forceinline__ void gn_centred_group(const char* x0, int c0, const char* x1, int c1, long row0, int rows, int c_lo, int cpg,
+                                                 float pivot, double* red, double& mean, double& var) {
+  constexpr int ES = Elem<Tag>::ES;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const long n = (long)rows * cpg;
+  double a = 0.0, b = 0.0;
+  // thread = (channel of the group, row lane): consecutive lanes read the consecutive channels of a row, so a wave's load touches a
+  // handful of cache lines, not one per lane; the thread's channel -- and with it its source -- is fixed, and eight rows are in flight
+  const double pv = (double)pivot;
+  const int rl_n = nthr / cpg, cl = tid % cpg, rl = tid / cpg;       // (cpg <= 256 <= blockDim.x)
+  if (rl < rl_n) {
+    const int c = c_lo + cl;
+    const char* src; long ld;
+    if (c < c0) { src = x0 + (long)c * ES; ld = (long)c0 * ES; } else { src = x1 + (long)(c - c0) * ES; ld = (long)c1 * ES; }
+    src += row0 * ld;
+    int r = rl;
+    for (; r + 7 * rl_n < rows; r += 8 * rl_n) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = load1<Tag>(src + (long)(r + k * rl_n) * ld);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { const double d = (double)v[k] - pv; a += d; b += d * d; }
+    }
+    for (; r < rows; r += rl_n) { const double d = (double)load1<Tag>(src + (long)r * ld) - pv; a += d; b += d * d; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+  __syncthreads();                                          // the previous call's readers are done with red
+  if ((tid & 63) == 0) { red[(tid >> 6) * 2] = a; red[(tid >> 6) * 2 + 1] = b; }
+  __syncthreads();
+  double sa = 0.0, sb = 0.0;
+  for (int w = 0; w < ((nthr + 63) >> 6); ++w) { sa += red[w * 2]; sb += red[w * 2 + 1]; }
+  const double dm = sa / (double)n;
+  mean = (double)pivot + dm;
+  var = sb / (double)n - dm * dm;
+  if (var < 0.0) var = 0.0;
+}
+// ... for the groups [0, ng) of a block whose s_redo flag is set (s_mean / s_rstd / s_redo: the block's shared statistics, indexed by the
+// block's own group number; channels of group g: c_base + g * cpg)
+template <typename Tag>
+__device__ __forceinline__ void gn_redo_groups(const char* x0, int c0, const char* x1, int c1, long row0, int rows, int c_base, int cpg, int ng,
+                                               float eps, float* s_mean, float* s_rstd, const int* s_redo, double* red) {
+  for (int g = 0; g < ng; ++g) {
+    if (!s_redo[g]) continue;                                // (shared: the same answer in every thread)
+    double mean, var;
+    gn_centred_group<Tag>(x0, c0, x1, c1, row0, rows, c_base + g * cpg, cpg, s_mean[g], red, mean, var);
+    if (threadIdx.x == 0) { s_mean[g] = (float)mean; s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps)); }    // (every thread read its pivot two barriers ago)
+  }
+  __syncthreads();
 }
 
 // partial sums per (image, row-chunk, group): ws[((img*chunks + chunk)*32 + g)*2 + {0,1}] (double)
@@ -75,11 +146,13 @@ __global__ void gn_partial_kernel(const char* x0, int c0, const char* x1, int c1
 // 32 slices are combined in a fixed order (deterministic).  (The cross-frame statistics of the temporal ResBlocks reduce
 // frames x chunks ~ 500 partials in 2 blocks: the slice count is what bounds this kernel's latency.)
 constexpr int GN_SLICES = 32;
+template <typename Tag>
 __global__ __launch_bounds__(1024) void gn_finalize_kernel(const double* ws, int chunks, int hw, int C, int fpg,
                                                           const float* gamma, const float* beta, float eps,
-                                                          float* scale, float* shift) {
+                                                          float* scale, float* shift, const char* x0, int c0, const char* x1, int c1) {
   __shared__ double s_a[GN_SLICES][GN_GROUPS], s_b[GN_SLICES][GN_GROUPS];
   __shared__ float s_mean[GN_GROUPS], s_rstd[GN_GROUPS];
+  __shared__ int s_redo[GN_GROUPS];
   const int ig = blockIdx.x, tid = threadIdx.x;
   const int g = tid & 31, slice = tid >> 5;
   {
@@ -113,9 +186,11 @@ __global__ __launch_bounds__(1024) void gn_finalize_kernel(const double* ws, int
     if (var < 0.0) var = 0.0;
     s_mean[tid] = (float)mean;
     s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
+    s_redo[tid] = b / cnt > GN_GUARD_RATIO * var;
   }
   __syncthreads();
   const int cpg = C / GN_GROUPS;
+  gn_redo_groups<Tag>(x0, c0, x1, c1, (long)ig * fpg * hw, fpg * hw, 0, cpg, GN_GROUPS, eps, s_mean, s_rstd, s_redo, &s_a[0][0]);
   for (int c = tid; c < C; c += blockDim.x) {
     const int gg = c / cpg;
     const float sc = s_rstd[gg] * gamma[c];
@@ -142,6 +217,8 @@ __global__ __launch_bounds__(1024) void gn_stats_image_kernel(const char* x0, in
   extern __shared__ __attribute__((aligned(16))) char smem[];
   kernarg_touch<104>();
   __shared__ float s_mean[GN_GROUPS], s_rstd[GN_GROUPS];
+  __shared__ int s_redo[GN_GROUPS];
+  __shared__ double s_red[32];
   const int C = c0 + c1, cv = C >> 3;
   const int img = blockIdx.x, tid = threadIdx.x;
   float* psum = (float*)smem;            // [rpb][C]
@@ -198,9 +275,11 @@ __global__ __launch_bounds__(1024) void gn_stats_image_kernel(const char* x0, in
       if (var < 0.0) var = 0.0;
       s_mean[g] = (float)mean;
       s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
+      s_redo[g] = b / cnt > GN_GUARD_RATIO * var;
     }
   }
   __syncthreads();
+  gn_redo_groups<Tag>(x0, c0, x1, c1, (long)img * hw, hw, 0, cpg, GN_GROUPS, eps, s_mean, s_rstd, s_redo, s_red);
   if (y == nullptr) {
     for (int c = tid; c < C; c += 1024) {
       const int gg = c / cpg;
@@ -330,6 +409,8 @@ __global__ __launch_bounds__(512) void gn_group_kernel(const char* x0, int c0, c
                                                        char* y, long ldy) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float s_mean[GN_GROUPS], s_rstd[GN_GROUPS];
+  __shared__ int s_redo[GN_GROUPS];
+  __shared__ double s_red[16];
   kernarg_touch<88>();
   const int C = c0 + c1, cpg = C / GN_GROUPS;
   const int L = blockIdx.x, xcd = L & 7, t = L >> 3;
@@ -390,10 +471,12 @@ __global__ __launch_bounds__(512) void gn_group_kernel(const char* x0, int c0, c
         if (var < 0.0) var = 0.0;
         s_mean[g] = (float)mean;
         s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
+        s_redo[g] = b / cnt > GN_GUARD_RATIO * var;
       }
     }
   }
   __syncthreads();
+  gn_redo_groups<Tag>(x0, c0, x1, c1, (long)img * hw, hw, ch_lo, cpg, gpb, eps, s_mean, s_rstd, s_redo, s_red);
   if (myr < rlanes) {
     float sc[8], sh[8];
 #pragma unroll
@@ -444,6 +527,8 @@ __global__ __launch_bounds__(512) void gn_tiles_kernel(const char* x, int C, con
                                                        int silu, char* y, long ldy) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float s_mean[GN_GROUPS], s_rstd[GN_GROUPS];
+  __shared__ int s_redo[GN_GROUPS];
+  __shared__ double s_red[16];
   kernarg_touch<96>();
   const int cpg = C / GN_GROUPS;
   const int L = blockIdx.x, xcd = L & 7, t = L >> 3;
@@ -480,8 +565,12 @@ __global__ __launch_bounds__(512) void gn_tiles_kernel(const char* x, int C, con
     if (var < 0.0) var = 0.0;
     s_mean[tid] = (float)mean;
     s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
+    s_redo[tid] = b / cnt > GN_GUARD_RATIO_TILES * var;
   }
   __syncthreads();
+  // (every row part of the segment recomputes a guarded group over the WHOLE segment: the same numbers in each of them; one source:
+  // no channel is >= C, the second pointer is never read)
+  gn_redo_groups<Tag>(x, C, x, 0, (long)seg * seg_rows, seg_rows, ch_lo, cpg, gpb, eps, s_mean, s_rstd, s_redo, s_red);
   // ---- apply: rows [r_lo, r_hi) of the segment, this slice's channels
   const int myv = tid % nv, myr = tid / nv;
   if (myr >= rlanes) return;
@@ -540,6 +629,16 @@ static int gn_group_gpb(int C, int es) {
 // each and the multi-launch route with its thousands of blocks streams better (64 x 112 x 320: 112 us against 84 us; 32 x 56 x 320:
 // 26 against 29 -- the slices' 80..240-byte row segments reach ~2.5 TB/s, full rows 3 to 4.5)
 constexpr int GN_GROUPED_MIN_ROWS = 256, GN_GROUPED_MAX_ROWS = 4096;
+static int g_gn_grouped = -1;          // TT_GN_GROUPED=0: the round-2 routes (A/B)
+static bool gn_grouped_on() {
+  if (g_gn_grouped < 0) { const char* e = getenv("TT_GN_GROUPED"); g_gn_grouped = e ? atoi(e) : 1; }
+  return g_gn_grouped != 0;
+}
+// the route decisions of tt_groupnorm_small / tt_groupnorm_stats, taken here for the launchers and for tt_groupnorm_route alike
+static int gn_grouped_gpb(int hw, int c, int es) {          // groups per block of gn_group_kernel; 0: not its problem
+  return gn_grouped_on() && hw >= GN_GROUPED_MIN_ROWS && hw <= GN_GROUPED_MAX_ROWS ? gn_group_gpb(c, es) : 0;
+}
+static bool gn_one_block_ok(int hw, int c, int es) { return (c >> 3) <= 1024 && (long)hw * c * es <= GN_ONE_BYTES; }
 
 // the per-image kernel keeps [rpb][C] x 2 fp32 partials in dynamic LDS (at most 96 KiB): ONE opt-in (per device) with that maximum
 constexpr int GN_IMAGE_LDS_MAX = 96 * 1024;
@@ -576,7 +675,7 @@ extern "C" int tt_groupnorm_stats(const void* x0, int32_t c0, const void* x1, in
   threads = (threads + 63) / 64 * 64;
   hipStream_t st = (hipStream_t)stream;
   const int es = dtype == TT_F32 ? 4 : 2;
-  if (fpg == 1 && (long)hw * C * es <= GN_ONE_BYTES && cv <= 1024) {
+  if (fpg == 1 && gn_one_block_ok(hw, C, es)) {
     int rpb1 = 1024 / cv;
     while (rpb1 > 1 && (size_t)2 * rpb1 * C * sizeof(float) > 96 * 1024) --rpb1;     // [rpb][C] x 2 fp32 in LDS
     if (rpb1 > hw) rpb1 = hw;
@@ -595,7 +694,10 @@ extern "C" int tt_groupnorm_stats(const void* x0, int32_t c0, const void* x1, in
     hipLaunchKernelGGL(gn_partial_kernel<f16_tag>, dim3(chunks, nimg), dim3(threads), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, chunks, (double*)ws);
   else
     hipLaunchKernelGGL(gn_partial_kernel<f32_tag>, dim3(chunks, nimg), dim3(threads), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, chunks, (double*)ws);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(nimg / fpg), dim3(32 * GN_SLICES), 0, st, (const double*)ws, chunks, hw, C, fpg, gamma, beta, eps, scale, shift);
+#define TT_GNF(TAG) hipLaunchKernelGGL(gn_finalize_kernel<TAG>, dim3(nimg / fpg), dim3(32 * GN_SLICES), 0, st, (const double*)ws, chunks, hw, C, fpg, gamma, beta, eps, \
+                                       scale, shift, (const char*)x0, c0, (const char*)x1, c1)
+  if (dtype == TT_BF16) TT_GNF(bf16_tag); else if (dtype == TT_F16) TT_GNF(f16_tag); else TT_GNF(f32_tag);
+#undef TT_GNF
   TT_CHECK_LAUNCH("tt_groupnorm_stats");
   return TT_OK;
 }
@@ -608,16 +710,21 @@ static int gn_small_rpb(int C, int hw) {
   if (rpb > hw) rpb = hw;
   return rpb;
 }
-static int g_gn_grouped = -1;          // TT_GN_GROUPED=0: the round-2 routes (A/B)
-static bool gn_grouped_on() {
-  if (g_gn_grouped < 0) { const char* e = getenv("TT_GN_GROUPED"); g_gn_grouped = e ? atoi(e) : 1; }
-  return g_gn_grouped != 0;
-}
 extern "C" int tt_groupnorm_small_supported(int32_t hw, int32_t c, int32_t dtype) {
   const int es = dtype == TT_F32 ? 4 : 2;
   if (hw <= 0 || c <= 0 || (c % GN_GROUPS) || (c & 7)) return 0;
-  if (gn_grouped_on() && hw >= GN_GROUPED_MIN_ROWS && hw <= GN_GROUPED_MAX_ROWS && gn_group_gpb(c, es) > 0) return 1;   // one block per (image, group slice)
-  return (c >> 3) <= 1024 && (long)hw * c * es <= GN_ONE_BYTES;
+  if (gn_grouped_gpb(hw, c, es) > 0) return 1;             // one block per (image, group slice)
+  return gn_one_block_ok(hw, c, es);
+}
+extern "C" int tt_groupnorm_route(int32_t hw, int32_t c, int32_t dtype, int32_t frames_per_group, int32_t one_launch) {
+  const int es = dtype == TT_F32 ? 4 : 2;
+  if (hw <= 0 || c <= 0 || frames_per_group <= 0 || (c % GN_GROUPS) || (c & 7)) return 0;
+  if (one_launch) {
+    if (frames_per_group != 1) return 0;
+    if (gn_grouped_gpb(hw, c, es) > 0) return TT_GN_ROUTE_GROUPED;
+    return gn_one_block_ok(hw, c, es) ? TT_GN_ROUTE_IMAGE : 0;
+  }
+  return frames_per_group == 1 && gn_one_block_ok(hw, c, es) ? TT_GN_ROUTE_IMAGE : TT_GN_ROUTE_PARTIAL;
 }
 extern "C" int tt_groupnorm_small(const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t nimg, int32_t hw,
                                   const float* gamma, const float* beta, float eps, int32_t silu, void* y, int64_t ldy,
@@ -631,7 +738,7 @@ extern "C" int tt_groupnorm_small(const void* x0, int32_t c0, const void* x1, in
     TT_FAIL(TT_EUNSUPPORTED, "tt_groupnorm_small: %d x %d per image is served by tt_groupnorm_stats + tt_groupnorm_apply", hw, C);
   hipStream_t st = (hipStream_t)stream;
   const int es = dtype == TT_F32 ? 4 : 2;
-  if (const int gpb = gn_grouped_on() && hw >= GN_GROUPED_MIN_ROWS && hw <= GN_GROUPED_MAX_ROWS ? gn_group_gpb(C, es) : 0) {
+  if (const int gpb = gn_grouped_gpb(hw, C, es)) {
     const int nslices = GN_GROUPS / gpb, nv = (gpb * (C / GN_GROUPS)) >> 3;
     int rlanes = 512 / nv;
     if (rlanes > hw) rlanes = hw;

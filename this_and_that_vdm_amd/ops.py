@@ -34,6 +34,23 @@ def _prof_end(start, name, flops, shape=None):
         PROFILE.append((name, flops, start, e, shape))
 
 
+# Optional record of the normalisation calls (tests): when set to a list, groupnorm_stats() / groupnorm_apply() / groupnorm() /
+# layernorm() / layernorm_block() append the kernel instance of the entry point they called.  It is this front end's record, not an
+# observation of a launch: an entry point with one kernel is named outright; for tt_groupnorm_small / tt_groupnorm_stats, which choose
+# between kernels, the name is tt_groupnorm_route's answer -- the same host code the launchers decide with.  It tells a test which
+# dispatch branch and which route decision a call went through.  Not part of PROFILE: its entries are the MFMA launches bench.py's
+# roofline table is built from.
+NORM_TRACE = None
+
+
+def _norm_trace(name: str, dtype) -> None:
+    if NORM_TRACE is not None:
+        NORM_TRACE.append(f"{name}<{_TAG[_code(dtype)]}>")
+
+
+_GN_ROUTE = {1: "gn_stats_image_kernel", 2: "gn_group_kernel", 3: "gn_partial_kernel + gn_finalize_kernel"}
+
+
 # ---- producer -> GroupNorm hand-off (gemm(..., stats=) / gemm(..., gn=) -> groupnorm()).  The producer's per-tile column sums (or the
 # tensor its reduction pass already normalised) travel with the OUTPUT TENSOR OBJECT as `_tt_stats` / `_tt_gn`, because producer and
 # consumer sit in different modules (a ResBlock's conv feeds the next block's norm).  What makes that safe is the write ledger below:
@@ -352,6 +369,8 @@ def groupnorm_stats(x0, x1, nimg, hw, frames_per_group, gamma, beta, eps):
     shift = torch.empty_like(scale)
     check(lib.tt_groupnorm_stats(_p(x0), c0, _p(x1), c1, nimg, hw, frames_per_group, _p(gamma), _p(beta), eps,
                                  _p(scale), _p(shift), _p(ws), ws_bytes, _code(x0.dtype), _stream()), "tt_groupnorm_stats")
+    if NORM_TRACE is not None:
+        _norm_trace(_GN_ROUTE[lib.tt_groupnorm_route(hw, c, _code(x0.dtype), frames_per_group, 0)], x0.dtype)
     return scale, shift
 
 
@@ -363,6 +382,7 @@ def groupnorm_apply(x0, x1, nimg, hw, scale, shift, silu: bool, out=None):
         out = torch.empty((nimg * hw, c0 + c1), dtype=x0.dtype, device=x0.device)
     check(lib.tt_groupnorm_apply(_p(x0), c0, _p(x1), c1, nimg, hw, _p(scale), _p(shift), int(silu), _p(out), out.stride(0),
                                  _code(x0.dtype), _stream()), "tt_groupnorm_apply")
+    _norm_trace("gn_apply_kernel", x0.dtype)
     _wrote(out)
     return out
 
@@ -407,6 +427,7 @@ def groupnorm(x0, x1, nimg, hw, frames_per_group, gamma, beta, eps, silu: bool):
         out = torch.empty((nimg * hw, c0), dtype=x0.dtype, device=x0.device)
         check(lib.tt_groupnorm_tiles(_p(x0), c0, _p(st[0]), st[1], nimg // frames_per_group, frames_per_group * hw, _p(gamma), _p(beta), eps,
                                      int(silu), _p(out), out.stride(0), _code(x0.dtype), _stream()), "tt_groupnorm_tiles")
+        _norm_trace("gn_tiles_kernel", x0.dtype)
         return out
     if GN_SMALL and frames_per_group > 1 and nimg % frames_per_group == 0 and frames_per_group * hw <= GN_CROSS_MAX_ROWS and \
             lib.tt_groupnorm_small_supported(frames_per_group * hw, c0 + c1, _code(x0.dtype)):
@@ -415,6 +436,8 @@ def groupnorm(x0, x1, nimg, hw, frames_per_group, gamma, beta, eps, silu: bool):
         out = torch.empty((nimg * hw, c0 + c1), dtype=x0.dtype, device=x0.device)
         check(lib.tt_groupnorm_small(_p(x0), c0, _p(x1), c1, nimg, hw, _p(gamma), _p(beta), eps, int(silu), _p(out), out.stride(0),
                                      _code(x0.dtype), _stream()), "tt_groupnorm_small")
+        if NORM_TRACE is not None:
+            _norm_trace(_GN_ROUTE[lib.tt_groupnorm_route(hw, c0 + c1, _code(x0.dtype), 1, 1)], x0.dtype)
         return out
     sc, sh = groupnorm_stats(x0, x1, nimg, hw, frames_per_group, gamma, beta, eps)
     return groupnorm_apply(x0, x1, nimg, hw, sc, sh, silu)
@@ -430,6 +453,7 @@ def layernorm(x, gamma, beta, eps=1e-5, rowvec=None, rows_per_vec=0, nvec=0):
         assert x.stride(0) == c
     check(lib.tt_layernorm(_p(x), x.stride(0), rows, c, _p(gamma), _p(beta), eps, _p(rowvec), rows_per_vec, nvec, _p(xs),
                            _p(y), y.stride(0), _code(x.dtype), _stream()), "tt_layernorm")
+    _norm_trace("ln_kernel", x.dtype)
     return (xs, y) if xs is not None else y
 
 
@@ -723,6 +747,7 @@ def layernorm_block(x, rows: int, eps: float = 1e-5, out=None):
         raise RuntimeError("layernorm_block: out must have x's shape, strides and dtype")
     check(lib.tt_layernorm_block(_p(x), x.stride(0), x.shape[0] // rows, rows, x.shape[1], float(eps), _p(y), _code(x.dtype), _stream()),
           "tt_layernorm_block")
+    _norm_trace("ln_block_kernel", x.dtype)
     _wrote(y)
     return y
 
