@@ -63,6 +63,14 @@ const char* tt_last_error(void);
  *                             configuration makes tt_gemm / tt_gemm_plan return TT_EUNSUPPORTED for mode 3.
  * W is [n, taps*(k0+k1)] row-major with k index (tap, source, channel); two sources implement
  * torch.cat([h, skip], dim=1) (unet_3d_blocks.py:2242,2352) without a concat buffer.
+ * upsample (mode 1): 0 none; 1 nearest x2 as an index map of the 9-tap gather (hout = 2 hin, wout = 2 win); 2 the same conv on
+ * PHASE-PACKED weights, W [n, 16*k0] with k index (phase py*2+px, tap r*2+c, channel): output pixel (Y, X) of phase (Y & 1, X & 1)
+ * sees 2 x 2 distinct input pixels, so its nine taps collapse onto four -- tap (r, c) reads input pixel (Y/2 + r - 1 + py,
+ * X/2 + c - 1 + px) and carries the sum of the 3x3 weights whose rows {0},{1,2} (py = 0) / {0,1},{2} (py = 1) and columns (same rule)
+ * fall on it (packing.pack_upsample_phases).  4/9 of the products of upsample = 1, one launch, same m / geometry fields / output
+ * layout.  Served by the tiled template only, with one source and a bias-only epilogue: a1 / k1, residual, blend, rowvec, stats_out,
+ * gn_out, geglu, ln_fold, out_fp8, out_f32, out_col_hw or stride != 1 make tt_gemm and tt_gemm_plan return TT_EINVAL; never split
+ * along K (tt_gemm_ws_bytes = 0, tt_gemm_stats_rows = 0).
  * Epilogue, in this order (every term optional):
  *   acc *= 1/sigma of the LayerNorm-folded operand row (ln_fold, below)
  *   v = (acc + bias[n]) * acc_scale + rowvec[m / rowvec_rows][n]        (row index taken modulo rowvec_mod when that is > 0)
@@ -78,7 +86,7 @@ typedef struct TtGemmArgs {
   const void* w; int64_t ldw;          /* [n, taps*(k0+k1)] */
   int32_t m, n;                        /* n multiple of 4 */
   int32_t mode;                        /* 0 linear, 1 conv3x3, 2 tconv3, 3 conv3x3 padded bottom / right only */
-  int32_t nimg, hin, win, hout, wout, stride, upsample;   /* modes 1 and 3 (hin/win = stored input size) */
+  int32_t nimg, hin, win, hout, wout, stride, upsample;   /* modes 1 and 3 (hin/win = stored input size); upsample 0 / 1 / 2: above */
   int32_t frames, hw;                  /* mode 2: row = (b*frames + f)*hw + p */
   const float* bias;
   float acc_scale;

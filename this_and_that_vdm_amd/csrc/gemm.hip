@@ -38,6 +38,21 @@ namespace {
 // taps per output row: 9 for both 3x3 gathers (mode 1: pad 1 all round, mode 3: pad on the bottom / right only), 3 for the temporal conv
 inline int gemm_taps(int mode) { return mode == 1 || mode == 3 ? 9 : (mode == 2 ? 3 : 1); }
 
+// upsample = 2: the nearest-x2 upsampling 3x3 conv on phase-packed weights (packing.pack_upsample_phases: [n, 16 * k0], phase-major).  An
+// output pixel of phase (py, px) = (Y & 1, X & 1) sees 2 x 2 distinct low-res pixels, so its nine taps collapse onto four whose weights
+// were added at pack time: 4/9 of the products of upsample = 1.  One launch of the tiled template: blocks tile the LOW-RES rows, the four
+// phases of a tile are neighbouring slices (each walks its 4 taps and owns its output rows: no slab, no reduction pass).
+inline bool is_up2(const TtGemmArgs* a) { return a->mode == 1 && a->upsample == 2; }
+// what such a problem may carry (tt_gemm and tt_gemm_plan refuse the rest alike): one source, bias, stride 1, any storage type
+const char* up2_refusal(const TtGemmArgs* a) {
+  if (a->stride != 1 || a->hout != 2 * a->hin || a->wout != 2 * a->win) return "stride 1 with hout = 2 hin and wout = 2 win";
+  if (a->a1 || a->k1) return "one source (no a1 / k1)";
+  if (a->residual || a->blend || a->rowvec) return "a bias-only epilogue (no residual / blend / rowvec)";
+  if (a->stats_out || a->gn_out) return "no stats_out / gn_out";
+  if (a->geglu || a->ln_fold || a->out_fp8 || a->out_f32 || a->out_col_hw) return "no geglu / ln_fold / out_fp8 / out_f32 / out_col_hw";
+  return nullptr;
+}
+
 // Every tuning knob of the planner.  All of them are read from the environment together, once per process, by the first call that asks
 // for one (the function-local static of knobs(): initialised exactly once, also under concurrent callers); the four tt_gemm_set_*
 // setters overwrite theirs afterwards.  What each one steers is written at the predicate that reads it.
@@ -276,7 +291,17 @@ Plan mode3_plan(const TtGemmArgs* a, Plan pl) {
 bool mode3_served(const TtGemmArgs* a, const Plan& pl) { return a->mode != 3 || tile_of(a->dtype, pl.cfg).m3; }
 // TT_F32 products: 0 = exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, 157 TFLOP/s peak), 1 = "split16": every fp32 operand split on the fly into
 // fp16 hi + lo, three 16-bit MFMAs per product block (gemm_kernel.h, `mma`): ~2^-21 relative per product at 3 / 16 of the issue time.
+// upsample = 2: never split along K (the four phase slices are the launch's slices).  Tile by the number of blocks, phases included:
+// two resident double-buffered 128 x 128 workgroups per CU from more than one block per CU on, else one with the 4-deep ring.
+Plan up2_plan(const TtGemmArgs* a) {
+  const long blocks = 4L * ceil_div(a->m / 4, 128) * ceil_div(a->n, 128);
+  if (a->dtype == TT_F32) return Plan{blocks >= 256 ? 0 : 1, 1};
+  const int f = knobs().forced_cfg;
+  if (f >= 0 && f < kNumCfgs) return Plan{f, 1};
+  return Plan{blocks > 256 ? 11 : 16, 1};
+}
 Plan plan_for(const TtGemmArgs* a) {
+  if (is_up2(a)) return up2_plan(a);
   if (a->dtype == TT_F32) {
     // split16: the 64 x 64 tiles' 32 x 32 wave tiles convert two operand fragments per product block (VALU-bound, ~110 TFLOP/s against
     // ~210 on the 128 x 128 tiles' 64 x 64 wave tiles), so the big tile is taken from 160 tiles on (3136 x 1280: 250 tiles = one round)
@@ -371,6 +396,7 @@ TileCfg route_tile(const TtGemmArgs* a, const Route& r) {
 
 // tt_gemm_stats_rows on a resolved route
 int32_t stats_rows_on(const TtGemmArgs* a, const Route& r) {
+  if (is_up2(a)) return 0;                                             // bias-only epilogue
   if (a->geglu || a->out_fp8 || a->out_f32 || a->out_col_hw > 0 || a->ln_fold == 2) return 0;
   if (r.kind == Kind::PP || r.kind == Kind::PP_TWO_PART || r.kind == Kind::SQ320 || r.kind == Kind::UNSUPPORTED) return 0;
   // the statistics variants exist for the straight-line epilogues: bias / scale / row vector of >= 32-row groups (or the even / odd
@@ -398,6 +424,7 @@ int32_t stats_rows_on(const TtGemmArgs* a, const Route& r) {
 }
 // tt_gemm_gn_fused on a resolved route
 int32_t gn_fused_on(const TtGemmArgs* a, const Route& r) {
+  if (is_up2(a)) return 0;
   if (a->dtype == TT_F32 || a->geglu || a->out_fp8 || a->out_f32 || a->out_col_hw > 0 || a->stats_out) return 0;
   const int seg = a->stats_seg;
   if (seg <= 0 || a->m % seg || (a->n & 127)) return 0;               // 32 groups of a whole number of column quads
@@ -423,6 +450,7 @@ extern "C" int tt_gemm_set_big_tile(int32_t on) { knobs().w320 = big_tile_bits(o
 
 extern "C" int tt_gemm_plan(const TtGemmArgs* a, int32_t cfg[7]) {
   if (!a || !cfg || a->m <= 0 || a->n <= 0) TT_FAIL(TT_EINVAL, "tt_gemm_plan: bad arguments");
+  if (is_up2(a)) if (const char* why = up2_refusal(a)) TT_FAIL(TT_EINVAL, "tt_gemm_plan: upsample = 2 needs %s", why);
   const Route r = resolve(a);
   if (r.kind == Kind::UNSUPPORTED)
     TT_FAIL(TT_EUNSUPPORTED, "tt_gemm_plan: forced tile configuration %d has no mode-3 variant (mode 3 is built for 1, 2, 11, 16)", r.cfg);
@@ -501,7 +529,7 @@ int fill_params(const TtGemmArgs* a, const Route& r, GemmP& p) {
   if (p.mode == 2) {
     if (p.frames <= 0 || p.hw <= 0 || p.m % ((long)p.frames * p.hw)) TT_FAIL(TT_EINVAL, "tt_gemm: tconv geometry");
   }
-  p.taps = gemm_taps(p.mode);
+  p.taps = is_up2(a) ? 16 : gemm_taps(p.mode);            // (upsample = 2: 4 phases x 4 taps of the phase-packed weight)
   {
     const long rows = p.mode == 1 || p.mode == 3 ? (long)p.nimg * p.hin * p.win : (long)p.m;
     const long a0b = ((rows - 1) * p.lda0 + p.k0) * es, a1b = p.k1 ? ((rows - 1) * p.lda1 + p.k1) * es : 16;
@@ -527,6 +555,12 @@ int fill_params(const TtGemmArgs* a, const Route& r, GemmP& p) {
   p.group_m_override = r.kind == Kind::PP || r.kind == Kind::TILED ? knobs().group_m : 0;
   p.ws = r.splitk > 1 ? (float*)a->ws : nullptr;
   p.ws_bytes = r.splitk > 1 ? (unsigned)slab_bytes(a, r.splitk) : 0u;
+  p.slices = r.splitk; p.phases = 0;
+  if (is_up2(a)) {                                   // the tile domain is the low-res image; the extents above are those of the real operands
+    if (r.kind != Kind::TILED || r.splitk != 1) TT_FAIL(TT_EUNSUPPORTED, "tt_gemm: upsample = 2 runs on the tiled template, unsplit");
+    p.phases = 1; p.upsample = 0;
+    p.m = p.nimg * p.hin * p.win; p.hout = p.hin; p.wout = p.win;
+  }
   return TT_OK;
 }
 }  // namespace
@@ -540,6 +574,7 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
   if (a->k1 && !a->a1) TT_FAIL(TT_EINVAL, "tt_gemm: k1 > 0 without a1");
   if (a->mode < 0 || a->mode > 3) TT_FAIL(TT_EINVAL, "tt_gemm: bad mode %d", a->mode);
   if (a->mode == 3 && a->upsample) TT_FAIL(TT_EINVAL, "tt_gemm: mode 3 (bottom / right zero padding) has no fused upsample");
+  if (is_up2(a)) if (const char* why = up2_refusal(a)) TT_FAIL(TT_EINVAL, "tt_gemm: upsample = 2 needs %s", why);
   const Route r = resolve(a);
   if (r.kind == Kind::PP_TWO_PART) {                        // whole tile rows -> persistent kernel, the rest -> whatever serves it; each half is checked in full below
     TtGemmArgs head, tail;

@@ -47,6 +47,9 @@ struct GemmP {
   unsigned a0_bytes, a1_bytes, w_bytes;   // extents for the buffer descriptors (< 2 GiB each)
   unsigned out_bytes, res_bytes, blend_bytes, bias_bytes, rowvec_bytes, ws_bytes;   // epilogue descriptors (0 = absent)
   int splitk;                       // > 1: block (tile, s) reduces K slice s and writes an fp32 slab to ws
+  int slices;                       // blocks per tile, neighbours in the launch order: splitk, or the 4 phases of an upsample = 2 conv
+  int phases;                       // 1: TtGemmArgs.upsample = 2 -- m / hout / wout describe the LOW-RES image (the tile domain); slice ph =
+                                    // (py, px) walks taps 4 ph .. 4 ph + 3 of the phase-packed weight and owns output rows (2 y + py, 2 x + px)
   float* ws;                        // [splitk][m][n] fp32 partial sums
   int ln_fold; float ln_eps;        // fused LayerNorm of the A rows (1) / W rows (2): see gemm_kernel, MODE 3 / 4
   int out_fp8;                      // store e4m3 bytes (operands of the fp8 attention path) instead of 16-bit values
@@ -301,7 +304,7 @@ void gemm_kernel(const GemmP p) {
 
   int bid = xcd_remap(blockIdx.x, gridDim.x);
   int split = 0;                                           // slices of one tile sit next to each other
-  if (p.splitk > 1) { const int t = fdiv(bid, p.fd_splitk); split = bid - t * p.splitk; bid = t; }
+  if (p.slices > 1) { const int t = fdiv(bid, p.fd_splitk); split = bid - t * p.slices; bid = t; }
   // Within an XCD's run the tiles go in groups of `group_m` tile rows, column by column inside a group: the ~64 workgroups
   // that are resident on an XCD at a time then cover group_m rows x 64/group_m columns, i.e. every K slice they fetch is
   // shared by group_m (W) or 64/group_m (A) of them instead of the whole window sharing ONE A row and streaming every W
@@ -322,9 +325,9 @@ void gemm_kernel(const GemmP p) {
   }
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   // K-tile range of this block
-  // (kt_total * splitk < 2^31: at most a few thousand K steps, splitk <= 16)
-  const int kt_lo = p.splitk > 1 ? fdiv(p.kt_total * split, p.fd_splitk) : 0;
-  const int KT = p.splitk > 1 ? fdiv(p.kt_total * (split + 1), p.fd_splitk) - kt_lo : p.kt_total;
+  // (kt_total * splitk < 2^31: at most a few thousand K steps, splitk <= 16; the 4 phases of an upsample = 2 conv: 4 of its 16 taps each)
+  const int kt_lo = p.slices > 1 ? fdiv(p.kt_total * split, p.fd_splitk) : 0;
+  const int KT = p.slices > 1 ? fdiv(p.kt_total * (split + 1), p.fd_splitk) - kt_lo : p.kt_total;
 
   // ---- staging: buffer_load ... lds through 128-bit resource descriptors.  Every lane owns a 32-bit byte offset per
   // staged 16-byte chunk (computed once per tile, or once per conv tap); the K position is a SCALAR offset.  Lanes that
@@ -394,7 +397,9 @@ void gemm_kernel(const GemmP p) {
           long row;
           if constexpr (MODE == 1) {
             constexpr int OFF = PAD_BR ? 0 : 1;          // taps -1..1 (pad 1 all round) or 0..2 (pad on the bottom / right only)
-            const int dy = s_tap / 3 - OFF, dx = s_tap - (dy + OFF) * 3 - OFF;
+            int dy = s_tap / 3 - OFF, dx = s_tap - (dy + OFF) * 3 - OFF;
+            // phase (py, px) of a phase-packed upsampling conv: tap (r, c) = (s_tap & 3) reads low-res pixel (y + r - 1 + py, x + c - 1 + px)
+            if (!PAD_BR && p.phases) { dy = ((s_tap >> 1) & 1) - 1 + (split >> 1); dx = (s_tap & 1) - 1 + (split & 1); }
             int iy = a_y[i] * p.stride + dy, ix = a_x[i] * p.stride + dx;
             const bool up = !PAD_BR && p.upsample;     // (tt_gemm refuses upsample with mode 3)
             const int hv = up ? p.hin * 2 : p.hin, wv = up ? p.win * 2 : p.win;
@@ -888,8 +893,12 @@ void gemm_kernel(const GemmP p) {
       //          128-VGPR budget has no room for the preload -- the residual.  A load issued after a store waits for
       //          that store (in-order vmcnt), so each batch loads first and stores last; the planner keeps such
       //          epilogues off the 256-row tiles.
-      auto run = [&](auto film_tag, auto inpass_tag, auto out8_tag, auto stats_tag) {
+      auto run = [&](auto film_tag, auto inpass_tag, auto out8_tag, auto stats_tag, auto phase_tag) {
         constexpr bool FILM = decltype(film_tag)::value, INPASS = decltype(inpass_tag)::value, OUT8 = decltype(out8_tag)::value;
+        // GemmP.phases (bias-only epilogue): tile row gm is low-res pixel (img, y, x); slice (py, px) stores output row
+        // (img * 2 hin + 2 y + py) * 2 win + 2 x + px.  Compile-time as well: the other launches do not pay for the row map.
+        constexpr bool PHASE = decltype(phase_tag)::value;
+        const int ph_row0 = (split >> 1) * 2 * p.win + (split & 1), ph_hw = p.hin * p.win;
         // GemmP.stats, compile-time like the operand variants (a run-time `if` inside the pass loops breaks the straight-line code)
         constexpr bool STATS = decltype(stats_tag)::value;
         const __amdgpu_buffer_rsrc_t r_rv = make_rsrc(p.rowvec, (FILM || INPASS) ? p.rowvec_bytes : 0);
@@ -961,6 +970,11 @@ void gemm_kernel(const GemmP p) {
                   const float4 t = *(const float4*)(ebuf + strip_off(r, qq, q_per_row));
                   const int gm = mb + r;
                   const bool ok = gm < p.m && gn < p.n;
+                  int orow = gm;                           // row of `out`
+                  if constexpr (PHASE) {
+                    const int img = fdiv(gm, p.fd_hwo), rem = gm - img * ph_hw, y = fdiv(rem, p.fd_wout), x = rem - y * p.win;
+                    orow = (img * p.hin + y) * 4 * p.win + 2 * x + ph_row0;      // (img * 2 hin + 2 y) * 2 win + 2 x + (py * 2 win + px)
+                  }
                   if (p.splitk > 1) {                    // uniform: fp32 partial sums of K slice `split`
                     st128f(r_out, ok ? (int)((((long)split * p.m + gm) * p.n + gn) * 4) : kInv, t);
                   } else {
@@ -984,8 +998,8 @@ void gemm_kernel(const GemmP p) {
                     if constexpr (OUT8) st32(r_out, ok ? (int)((long)gm * p.ldo + gn) : kInv, pack4_fp8(v));
                     else {
                       const quad_t packed = f32_to_quad<Tag>(v);
-                      if constexpr (ES == 2) st64(r_out, ok ? (int)(((long)gm * p.ldo + gn) * ES) : kInv, packed.x, packed.y);
-                      else stq<Tag>(r_out, ok ? (int)(((long)gm * p.ldo + gn) * ES) : kInv, v);
+                      if constexpr (ES == 2) st64(r_out, ok ? (int)(((long)orow * p.ldo + gn) * ES) : kInv, packed.x, packed.y);
+                      else stq<Tag>(r_out, ok ? (int)(((long)orow * p.ldo + gn) * ES) : kInv, v);
                       if constexpr (STATS) {               // (rows >= m of a ragged last tile add nothing)
                         float sv[4];
                         quad_to_f32<Tag>(packed, sv);
@@ -1006,11 +1020,13 @@ void gemm_kernel(const GemmP p) {
       constexpr std::false_type no{};
       constexpr std::true_type yes{};
       const bool kstats = p.stats && p.splitk == 1;          // (a K slice leaves the sums to the reduction kernel)
-      if (inpass) run(no, yes, no, no);                      // (never with statistics: tt_gemm_stats_rows)
-      else if (p.rowvec) { if (kstats) run(yes, no, no, yes); else run(yes, no, no, no); }
+      if (inpass) run(no, yes, no, no, no);                  // (never with statistics: tt_gemm_stats_rows)
+      else if (p.rowvec) { if (kstats) run(yes, no, no, yes, no); else run(yes, no, no, no, no); }
       else if (MODE == 0 && ES == 2 && p.out_fp8) {          // Q | K and V^T of the fp8 attention path (linear, no residual)
-        if constexpr (MODE == 0 && ES == 2) run(no, no, yes, no);
-      } else { if (kstats) run(no, no, no, yes); else run(no, no, no, no); }
+        if constexpr (MODE == 0 && ES == 2) run(no, no, yes, no, no);
+      } else if (MODE == 1 && !PAD_BR && p.phases) {         // phase-packed upsampling conv (bias only: tt_gemm refuses the rest)
+        if constexpr (MODE == 1 && !PAD_BR) run(no, no, no, no, yes);
+      } else { if (kstats) run(no, no, no, yes, no); else run(no, no, no, no, no); }
       if (kstats) {
         __syncthreads();
         const float* st0 = (const float*)(smem + STAT_OFF);
@@ -1478,7 +1494,7 @@ void launch_mode(const GemmP& p, hipStream_t st) {
   constexpr size_t stat_lds = (size_t)WGM * WGN * 2 * (BN / WGN) * sizeof(float);        // per wave: sum and sum-of-squares rows of its columns
   static unsigned long long attr_done = 0;     // per kernel instance, one bit per device (see tt_lds_opt_in)
   tt_lds_opt_in((const void*)gemm_kernel<Tag, BM, BN, BK, NST, WGM, WGN, MODE>, (int)(lds + stat_lds), &attr_done);
-  hipLaunchKernelGGL((gemm_kernel<Tag, BM, BN, BK, NST, WGM, WGN, MODE>), dim3(p.tiles_m * p.tiles_n * p.splitk),
+  hipLaunchKernelGGL((gemm_kernel<Tag, BM, BN, BK, NST, WGM, WGN, MODE>), dim3(p.tiles_m * p.tiles_n * p.slices),
                      dim3(64 * WGM * WGN), (p.stats && p.splitk == 1) ? lds + stat_lds : lds, st, p);
   if (p.splitk > 1) launch_splitk_epilogue<Tag>(p, st);
 }
@@ -1487,7 +1503,7 @@ void launch_mode(const GemmP& p, hipStream_t st) {
 // problems on them).  M3OK: likewise the mode-3 gather (KMODE 5).  Both are columns of the tile table below.
 // multiply-shift pairs of every launch-uniform divisor the kernel meets (tile order, K split, conv / frame geometry, row groups)
 static inline void fill_fastdivs(GemmP& p) {
-  p.fd_splitk = make_fastdiv(p.splitk);
+  p.fd_splitk = make_fastdiv(p.slices);
   p.fd_per_group = make_fastdiv((long)p.group_m * p.tiles_n);
   p.fd_group_m = make_fastdiv(p.group_m);
   p.fd_last_rows = make_fastdiv(p.tiles_m % p.group_m ? p.tiles_m % p.group_m : p.group_m);
@@ -1520,6 +1536,7 @@ void launch_cfg(GemmP& p, hipStream_t st) {
   }
   p.nk0 = ceil_div(p.k0, BK); p.nk1 = p.k1 ? ceil_div(p.k1, BK) : 0;
   p.kt_total = p.taps * (p.nk0 + p.nk1);
+  p.slices = p.phases ? 4 : p.splitk;
   fill_fastdivs(p);
   if (p.mode == 3) {                         // routed explicitly: the switches below send unknown modes elsewhere
     if constexpr (M3OK) {

@@ -160,6 +160,7 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
     with the same parameters returns it without a launch; elsewhere `gn` is ignored and the statistics route above applies.
     conv = (nimg, hin, win, hout, wout, stride, upsample) for mode 1 (3x3, zero padding 1 all round) and mode 3 (3x3, zero padding on the
     bottom / right only: F.pad(x, (0, 1, 0, 1)) + conv(padding=0), the VAE encoder's downsample; upsample 0); tconv = (frames, hw).
+    upsample = 2 (mode 1): `w` is the phase pack [n, 16 * k0] of packing.pack_upsample_phases; one source, bias only.
     ln_fold: 1 = rows of a0 / 2 = rows of w are LayerNorm inputs (weights pre-folded by packing.fold_layernorm).
     out_fp8: the output is stored as OCP e4m3 (torch.float8_e4m3fn), the operand format of attention(..., fp8 path)."""
     lib = _lib.load()
@@ -237,6 +238,8 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
         cfg = (C.c_int32 * 7)()
         lib.tt_gemm_plan(C.byref(g), cfg)
         taps = 9 if mode in (1, 3) else (3 if mode == 2 else 1)
+        if mode == 1 and g.upsample == 2:            # phase-packed upsampling conv: the EXECUTED products, four taps per output pixel
+            taps = 4
         tag = _TAG[g.dtype]
         if cfg[3] == 0 and cfg[1] == 320:            # the 256 x 320 big-tile kernel (gemm_w320.hip)
             kname = f"gemm_w320{'h' if cfg[0] == 128 else ''}_kernel<{tag}, {mode}, {int(bool(ln_fold))}>"

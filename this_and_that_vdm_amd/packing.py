@@ -12,6 +12,28 @@ def pack_conv3x3(w: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 2, 3, 1).reshape(o, 9 * i).contiguous()
 
 
+def pack_upsample_phases(w: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """Conv weight [O, I, 3, 3] of a nearest-x2 upsample + 3x3 conv -> [O, 16*I] in ``dtype`` for tt_gemm's ``upsample = 2``: k index =
+    (phase py*2 + px, tap r*2 + c, ci).  Output pixel (Y, X) of phase (Y & 1, X & 1) sees only 2 x 2 distinct low-res pixels: tap (r, c)
+    reads low-res pixel (Y // 2 + r - 1 + py, X // 2 + c - 1 + px) and carries the sum of the 3x3 weights that fall on it -- rows
+    {0}, {1, 2} for py = 0 and {0, 1}, {2} for py = 1, columns by the same rule.  The addends are the weights AS STORED (rounded to
+    ``dtype`` first, what the upsample = 1 route multiplies), summed in fp32 and rounded once; fp32 storage keeps the fp32 sum
+    (``dtype`` = float64, the packing identity's test: summed in fp64)."""
+    o, i = w.shape[:2]
+    acc = torch.float64 if dtype == torch.float64 else torch.float32
+    ws = w.detach().to(dtype).to(acc)
+    rows = {0: ((0,), (1, 2)), 1: ((0, 1), (2,))}
+    out = torch.zeros((o, 2, 2, 2, 2, i), dtype=acc, device=w.device)       # [O, py, px, r, c, I]
+    for py in (0, 1):
+        for px in (0, 1):
+            for r in (0, 1):
+                for c in (0, 1):
+                    for ky in rows[py][r]:                    # (fixed order: the sums are reproducible)
+                        for kx in rows[px][c]:
+                            out[:, py, px, r, c] += ws[:, :, ky, kx]
+    return out.reshape(o, 16 * i).to(dtype).contiguous()
+
+
 def pack_tconv3(w: torch.Tensor) -> torch.Tensor:
     """Conv3d (3,1,1) weight [O, I, 3, 1, 1] -> [O, 3*I], k index = (frame tap, ci)."""
     o, i = w.shape[:2]

@@ -19,12 +19,13 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..packing import fold_layernorm, pack_conv1x1, pack_conv3x3, pack_geglu, pack_tconv3, permute_q_rows, zero_sum_round
+from ..packing import fold_layernorm, pack_conv1x1, pack_conv3x3, pack_geglu, pack_tconv3, pack_upsample_phases, permute_q_rows, zero_sum_round
 
 
 ZERO_CTX_TEMPORAL = os.environ.get("TT_ZERO_CTX_T", "1") != "0"      # A/B switch of the temporal zero-context shortcut
 ATTN_V_ROWS = os.environ.get("TT_ATTN_V_ROWS", "1") != "0"            # spatial self-attention from ONE Q | K | V launch, V not transposed (tt_attention v_rows)
 MERGE_FRAMES = os.environ.get("TT_XATTN_MERGE_FRAMES", "1") != "0"    # spatial cross-attention: the frames of a batch element as one sequence (A/B)
+UPSAMPLE_PHASES = os.environ.get("TT_UPSAMPLE_PHASES", "1") != "0"     # Upsample2D as four 2 x 2 phase convs in one launch (tt_gemm upsample = 2); 0: the nine-tap index map (A/B)
 
 
 @dataclass
@@ -424,11 +425,19 @@ class Upsample2D(_Packable):
         self.conv = nn.Conv2d(channels, out_channels or channels, 3, padding=1)
 
     def pack(self, reg, dtype):
-        self.w, self.b = pack_conv3x3(self.conv.weight.detach().to(dtype)), _f32(self.conv.bias)
+        # one pack resident: the phase pack (16 / 9 of the size) or, with TT_UPSAMPLE_PHASES=0, the nine-tap one
+        self.phases = UPSAMPLE_PHASES
+        self.w = pack_upsample_phases(self.conv.weight, dtype) if self.phases else pack_conv3x3(self.conv.weight.detach().to(dtype))
+        self.b = _f32(self.conv.bias)
 
     def forward(self, x, g: Geom):
         # nearest x2 is an index map inside the conv gather: never materialised
-        out = ops.gemm(x, self.w, mode=1, conv=(g.n, g.h, g.w, 2 * g.h, 2 * g.w, 1, 1), bias=self.b, stats=4 * g.hw)
+        if self.phases:
+            # four 2 x 2 phase convs in one launch (tt_gemm upsample = 2): 4 / 9 of the products.  No stats=: the readers of these outputs
+            # are two-source GroupNorms, which take the statistics-pass kernels anyway
+            out = ops.gemm(x, self.w, mode=1, conv=(g.n, g.h, g.w, 2 * g.h, 2 * g.w, 1, 2), bias=self.b)
+        else:
+            out = ops.gemm(x, self.w, mode=1, conv=(g.n, g.h, g.w, 2 * g.h, 2 * g.w, 1, 1), bias=self.b, stats=4 * g.hw)
         return out, Geom(g.batch, g.frames, 2 * g.h, 2 * g.w, g.batch0, g.batch_total, g.requests)
 
 
