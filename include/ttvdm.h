@@ -78,6 +78,18 @@ const char* tt_last_error(void);
  *   v += residual[m][n];  v = alpha*blend[m][n] + (1-alpha)*v   (AlphaBlender, video branch)
  * `out` may alias `residual` (same pointer and stride: in-place update of the hidden states -- every element's residual is
  * read by the lane that writes it, in the tile kernels and in the split-K reduction); it must not alias a0 / a1 / blend.
+ * Operand sizes.  Every kernel of the family indexes an operand with 32-bit byte offsets from its base, so a problem whose a0, a1,
+ * out, residual and blend each span less than 2 GiB (first byte to the end of the last row, strides included) runs on any route.  A
+ * problem in which one of them spans 2 GiB or more runs on the WIDE route: the tiled template's windowed variant, in which every
+ * workgroup rebases its descriptors once per tile onto the first row the tile can touch (64-bit arithmetic) and the lanes' offsets
+ * count from there.  Same tile, K order and epilogue arithmetic as the narrow route -- bit-equal results on the same values --,
+ * never split along K.  It serves modes 0 / 1 / 2 (upsample 0 / 1 / 2 included) with one source and the bias / acc_scale /
+ * residual (also aliasing out) / blend / out_f32 epilogue terms and stats_out on bf16, fp16 and TT_F32 storage (exact and split16
+ * products).  TT_EUNSUPPORTED, with a message that names the cause, for: a second source, geglu, ln_fold, rowvec, gn_out, out_fp8,
+ * out_col_hw, presplit or mode 3 on such a problem; W of 2 GiB or more; and a problem in which the window of ONE tile would itself
+ * reach 2 GiB (mode 0: the tile's 64 / 128 rows of a0; mode 1: the images its output rows lie in; mode 2: its rows and one frame
+ * either side; out / residual / blend: the tile's rows) -- e.g. mode 0 on 16-bit storage with lda0 = 2^25.  The ~302 MB frames of
+ * the temporal VAE decoder at 576x1024 (svd/pipeline_stable_video_diffusion_controlnet.py:257-283) are what it is for.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct TtGemmArgs {
   const void* a0; const void* a1;      /* activation sources; a1 NULL if k1 == 0 */
@@ -198,6 +210,15 @@ int tt_gemm_set_big_tile(int32_t on);
  *      tt_attention on fp32 storage (head_dim 64) follows the same switch; few-tile long-K problems take a split-K plan in this mode
  *      (fp32 slabs in the tt_gemm_ws_bytes workspace, summed in a fixed order). */
 int tt_gemm_set_f32_split(int32_t on);
+/* The wide route (see "Operand sizes" above; additive entry points, the ABI version is unchanged).
+ * tt_gemm_is_wide: 1 if tt_gemm would run `args` on the wide route, else 0 (also for problems it refuses).  Host-only. */
+int32_t tt_gemm_is_wide(const TtGemmArgs* args);
+/* When tt_gemm takes the wide route (process-wide; also TT_GEMM_WIDE=0|1|2 in the environment):
+ *   0  never: a problem with an operand of 2 GiB or more is refused (TT_EUNSUPPORTED "operand larger than 2 GiB"), for A/B runs;
+ *   1  (default) when an operand needs it;
+ *   2  for every problem the wide variant can serve without changing its plan (tiled template, un-split, a tile shape whose wide
+ *      variant is built): tests and measurements of the wide kernels against the narrow ones on the same problem. */
+int tt_gemm_set_wide(int32_t on);
 
 /* ------------------------------------------------------------------------------------------------
  * tt_conv3x3: Conv2d 3x3 / stride 1 / pad 1 with the GroupNorm (+SiLU) of its INPUT fused in -- the ResnetBlock2D convs

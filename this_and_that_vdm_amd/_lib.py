@@ -92,6 +92,9 @@ SIGNATURES = {
     "tt_gemm_plan": (C.c_int, [C.POINTER(TtGemmArgs), C.POINTER(C.c_int32)]),
     "tt_gemm_set_tile_override": (C.c_int, [_i32]),
     "tt_gemm_ws_bytes": (_sz, [C.POINTER(TtGemmArgs)]),
+    # the wide route for operands of 2 GiB and more (additive; the ABI version is unchanged)
+    "tt_gemm_is_wide": (C.c_int32, [C.POINTER(TtGemmArgs)]),
+    "tt_gemm_set_wide": (C.c_int, [C.c_int32]),
     "tt_attention": (C.c_int, [C.POINTER(TtAttnArgs), _vp]),
     "tt_conv3x3_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "tt_conv3x3": (C.c_int, [C.POINTER(TtConvArgs), _vp]),

@@ -13,7 +13,12 @@
 //   * LDS image is lane-linear with the XOR swizzle applied on the SOURCE chunk and on the read
 //     (conflict-free ds_read_b128, see common.h);
 //   * MFMA operands are swapped (W fragment as the MFMA "A" operand) so each lane ends up with 4
-//     consecutive output columns of one row: 8-byte epilogue loads/stores.
+//     consecutive output columns of one row: 8-byte epilogue loads/stores;
+//   * every lane addresses an operand with a 32-bit byte offset into a buffer descriptor.  The narrow instances (and the persistent /
+//     big-tile / streaming kernels) put the descriptor on the operand's base: operands below 2 GiB.  A problem in which a0, out, residual
+//     or blend spans 2 GiB or more runs the template's WIDE variant (KMODE + 64, gemm_inst_wide_*.hip), in which each workgroup rebases
+//     its descriptors once per tile, in 64-bit scalar arithmetic, onto the first row the tile can touch: same tile, ring, K order and
+//     epilogue arithmetic, the same bits (the temporal VAE decoder at 576x1024: 302 MB of activations per frame).
 //
 // Host side of this file: the per-route predicates (pp_ok, sq320_ok, w320_route, ... -- each with the measurements behind its thresholds),
 // ONE resolver that sequences them (wanted_route / granted_route -> Route), and five short entry points that read its answer.
@@ -26,6 +31,9 @@ namespace ttg {
 void launch_bf16(GemmP& p, int cfg, hipStream_t st);
 void launch_f16(GemmP& p, int cfg, hipStream_t st);
 void launch_f32(GemmP& p, int cfg, hipStream_t st);
+void launch_wide_bf16(GemmP& p, int cfg, hipStream_t st);   // gemm_inst_wide_*.hip: the windowed variants (operands of 2 GiB and more)
+void launch_wide_f16(GemmP& p, int cfg, hipStream_t st);
+void launch_wide_f32(GemmP& p, int cfg, hipStream_t st);
 void launch_sq320_bf16(const GemmP& p, hipStream_t st);
 void launch_sq320_f16(const GemmP& p, hipStream_t st);
 void launch_pp_bf16(GemmP& p, hipStream_t st);         // gemm_pp.hip: persistent 256 x 256 x 64 ping-pong kernel
@@ -80,6 +88,7 @@ struct Knobs {
   int f32_split = env_int("TT_F32_SPLIT", 0) ? 1 : 0;             // tt_gemm_set_f32_split
   int f32_split_min_tiles = env_int("TT_F32_SPLIT_MIN_TILES", 160);
   int f32_splitk = env_int("TT_F32_SPLITK", 1);
+  int wide = env_int("TT_GEMM_WIDE", 1);                          // tt_gemm_set_wide
 };
 Knobs& knobs() { static Knobs k; return k; }
 
@@ -362,17 +371,17 @@ Plan unsplit_plan(const TtGemmArgs* a) {
 //   * tt_gemm_stats_rows tells "big-tile kernel" from "tiled template" by the tile (BN = 320 or no ring), so a forced 128 x 320 x 32
 //     tile (cfg 8) gets the big-tile kernels' answer.
 enum class Kind { PP, PP_TWO_PART, SQ320, W320, W320H, W320H_SPLIT, TILED, UNSUPPORTED };
-struct Route { Kind kind; int cfg; int splitk; int head_rows; };       // cfg: tile table index (TILED / UNSUPPORTED); head_rows: PP_TWO_PART
+struct Route { Kind kind; int cfg; int splitk; int head_rows; bool wide; };       // cfg: tile table index (TILED / UNSUPPORTED); head_rows: PP_TWO_PART; wide: the windowed variant of the tile
 
-Route tiled_route(const TtGemmArgs* a, Plan pl) { return Route{mode3_served(a, pl) ? Kind::TILED : Kind::UNSUPPORTED, pl.cfg, pl.splitk, 0}; }
+Route tiled_route(const TtGemmArgs* a, Plan pl) { return Route{mode3_served(a, pl) ? Kind::TILED : Kind::UNSUPPORTED, pl.cfg, pl.splitk, 0, false}; }
 Route wanted_route(const TtGemmArgs* a) {
-  if (pp_ok(a)) return Route{Kind::PP, -1, 1, 0};
+  if (pp_ok(a)) return Route{Kind::PP, -1, 1, 0, false};
   const bool sq = sq320_ok(a);
   const int big = w320_route(a);
-  if (const int rows = pp_head_rows(a, sq || big)) return Route{Kind::PP_TWO_PART, -1, 1, rows};
-  if (sq) return Route{Kind::SQ320, -1, 1, 0};
-  if (big) return Route{big == 1 ? Kind::W320 : Kind::W320H, -1, 1, 0};
-  if (const int split = w320_split(a)) return Route{Kind::W320H_SPLIT, -1, split, 0};
+  if (const int rows = pp_head_rows(a, sq || big)) return Route{Kind::PP_TWO_PART, -1, 1, rows, false};
+  if (sq) return Route{Kind::SQ320, -1, 1, 0, false};
+  if (big) return Route{big == 1 ? Kind::W320 : Kind::W320H, -1, 1, 0, false};
+  if (const int split = w320_split(a)) return Route{Kind::W320H_SPLIT, -1, split, 0, false};
   return tiled_route(a, plan_for(a));
 }
 Route granted_route(const TtGemmArgs* a, Route r) {
@@ -381,7 +390,132 @@ Route granted_route(const TtGemmArgs* a, Route r) {
   if (r.kind == Kind::TILED && r.splitk > 1 && (!ws_fits(a, r.splitk) || slab_bytes(a, r.splitk) >= ((size_t)1 << 31))) r = tiled_route(a, unsplit_plan(a));
   return r;
 }
-Route resolve(const TtGemmArgs* a) { return granted_route(a, wanted_route(a)); }
+
+// ---- the wide route: the tiled template's windowed variant (gemm_kernel.h, KMODE + 64) for problems in which a0, a1, out, residual or
+// blend spans 2 GiB or more -- every other kernel, and the narrow template, index an operand with 32-bit byte offsets from its base.
+// tt_gemm_set_wide / TT_GEMM_WIDE: 0 never (such a problem is refused, as before the route existed), 1 (default) the problems that need
+// it, 2 every problem it can serve (tests, A/B measurements: the same bits as the narrow route).
+struct Extents { long a0, a1, w, out, res, blend, rowvec; };          // bytes from each operand's base to the end of its last row
+Extents extents_of(const TtGemmArgs* a) {
+  const long es = a->dtype == TT_F32 ? 4 : 2;
+  const long rows = a->mode == 1 || a->mode == 3 ? (long)a->nimg * a->hin * a->win : (long)a->m;
+  const long taps = is_up2(a) ? 16 : gemm_taps(a->mode);
+  const long n_out = a->geglu ? a->n / 2 : a->n;
+  const bool f32o = a->dtype != TT_F32 && a->out_f32;
+  Extents e;
+  e.a0 = ((rows - 1) * a->lda0 + a->k0) * es;
+  e.a1 = a->k1 ? ((rows - 1) * a->lda1 + a->k1) * es : 16;
+  e.w = ((long)(a->n - 1) * a->ldw + taps * (a->k0 + a->k1)) * es;
+  e.out = ((long)(a->m - 1) * a->ldo + (a->out_col_hw > 0 ? a->ldo : n_out)) * (f32o ? 4 : (a->out_fp8 ? 1 : es));
+  e.res = a->residual ? ((long)(a->m - 1) * a->ld_res + a->n) * es : 0;
+  e.blend = a->blend ? ((long)(a->m - 1) * a->ld_blend + a->n) * es : 0;
+  long rv_last = a->rowvec && a->rowvec_rows > 0 ? (a->m - 1) / a->rowvec_rows : 0;   // last row-vector index the kernel can form
+  if (a->rowvec_mod > 0 && rv_last > a->rowvec_mod - 1) rv_last = a->rowvec_mod - 1;
+  e.rowvec = a->rowvec ? (rv_last * a->ld_rowvec + a->n) * 4 : 0;
+  return e;
+}
+constexpr long k2G = 1L << 31;
+bool needs_wide(const TtGemmArgs* a) {
+  const Extents e = extents_of(a);
+  return e.a0 >= k2G || e.a1 >= k2G || e.out >= k2G || e.res >= k2G || e.blend >= k2G;
+}
+// what the wide variant does not carry (nullptr: nothing)
+const char* wide_unserved(const TtGemmArgs* a) {
+  if (a->mode == 3) return "mode 3";
+  if (a->a1 || a->k1) return "a second source (a1 / k1)";
+  if (a->geglu) return "geglu";
+  if (a->ln_fold) return "ln_fold";
+  if (a->rowvec) return "rowvec";
+  if (a->gn_out) return "gn_out";
+  if (a->out_fp8) return "out_fp8";
+  if (a->out_col_hw) return "out_col_hw";
+  if (a->presplit) return "presplit operands";
+  return nullptr;
+}
+// The plan of a wide launch: the narrow plan of the same problem, un-split (the window arithmetic covers `out`, not fp32 slabs), on its
+// own tile where that tile's wide variant is built, else on the 128 x 128 tile the planner gives every large problem.
+Plan wide_plan(const TtGemmArgs* a) {
+  Plan pl = plan_for(a);
+  if (pl.splitk > 1) pl = unsplit_plan(a);
+  const bool f32 = a->dtype == TT_F32;
+  if (!wide_capable(f32, pl.cfg)) pl.cfg = f32 ? 0 : 11;
+  return Plan{pl.cfg, 1};
+}
+// Rows and bytes one tile's window spans per operand, worst case over the tiles (the kernel's origins: gemm_kernel.h, WIDE).
+struct Windows { long a_rows, a_bytes, o_rows, o_bytes, e_rows, r_bytes, b_bytes; };
+Windows wide_windows(const TtGemmArgs* a, int bm) {
+  const long es = a->dtype == TT_F32 ? 4 : 2;
+  Windows w;
+  const long tile_m = is_up2(a) ? (long)a->nimg * a->hin * a->win : (long)a->m;      // rows of the tile domain
+  const long tm = bm < tile_m ? bm : tile_m;
+  if (a->mode == 1) {                      // from the start of the first image a tile touches to the end of the last
+    const long hwo = is_up2(a) ? (long)a->hin * a->win : (long)a->hout * a->wout;
+    long imgs = (tm - 2 + hwo) / hwo + 1;
+    if (imgs > a->nimg) imgs = a->nimg;
+    w.a_rows = imgs * a->hin * a->win;
+  } else if (a->mode == 2) {               // one frame before the tile's first row to one frame behind its last
+    w.a_rows = tm + 2L * a->hw < a->m ? tm + 2L * a->hw : a->m;
+  } else {
+    w.a_rows = tm;
+  }
+  w.a_bytes = ((w.a_rows - 1) * a->lda0 + a->k0) * es;
+  // out: the tile's rows; phase-packed upsampling conv: low-res row gm -> output row 4 gm - 2 x + (py 2 win + px)
+  w.o_rows = is_up2(a) ? 4L * tm + 4L * a->win + 2 : tm;
+  if (w.o_rows > a->m) w.o_rows = a->m;
+  w.o_bytes = (a->dtype != TT_F32 && a->out_f32) ? 0 : ((w.o_rows - 1) * a->ldo + a->n) * es;     // (fp32 out of 16-bit storage: 64-bit pointers)
+  w.e_rows = tm;
+  w.r_bytes = a->residual ? ((tm - 1) * a->ld_res + a->n) * es : 0;
+  w.b_bytes = a->blend ? ((tm - 1) * a->ld_blend + a->n) * es : 0;
+  return w;
+}
+// nullptr if `a` can run wide on tile row count bm; else the reason (names the window and the rows it spans)
+const char* wide_window_refusal(const TtGemmArgs* a, int bm) {
+  static thread_local char msg[192];
+  const Windows w = wide_windows(a, bm);
+  const char* which = nullptr; long rows = 0, bytes = 0;
+  if (w.a_bytes >= k2G) { which = "a0"; rows = w.a_rows; bytes = w.a_bytes; }
+  else if (w.o_bytes >= k2G) { which = "out"; rows = w.o_rows; bytes = w.o_bytes; }
+  else if (w.r_bytes >= k2G) { which = "residual"; rows = w.e_rows; bytes = w.r_bytes; }
+  else if (w.b_bytes >= k2G) { which = "blend"; rows = w.e_rows; bytes = w.b_bytes; }
+  if (!which) return nullptr;
+  snprintf(msg, sizeof msg, "the window of one tile on %s spans %ld rows = %ld bytes (2 GiB or more)", which, rows, bytes);
+  return msg;
+}
+// does tt_gemm ask for the wide route for `a` (before looking at what it can serve)?
+bool wide_asked(const TtGemmArgs* a) { const int on = knobs().wide; return on == 2 || (on == 1 && needs_wide(a)); }
+// Which problems go wide, and on which tile.  (1) A problem whose own plan is the tiled template, un-split (with or without a workspace),
+// on a tile whose wide variant is built: the same plan with the windowed kernel -- no answer of tt_gemm_plan / tt_gemm_ws_bytes /
+// tt_gemm_stats_rows / tt_gemm_gn_fused changes, and tt_gemm_set_wide(2) takes exactly these.  (2) A problem whose a0 itself spans 2 GiB
+// or more: no other kernel can read it, so the wide route comes before every other one, on wide_plan()'s tile (the decoder's 1 x 1
+// shortcut at 576x1024 would otherwise be the persistent kernel's).  A problem in which only out / residual / blend reach 2 GiB and that
+// the planner gives to the persistent / big-tile / streaming kernels, to a split plan or to another tile keeps that plan and its refusal
+// by tt_gemm (those kernels are as they were; tests/golden/gemm_route_census.json pins their answers at such sizes).
+bool wide_own_plan(const TtGemmArgs* a, const Route& narrow) {
+  return narrow.kind == Kind::TILED && narrow.splitk == 1 && wide_capable(a->dtype == TT_F32, narrow.cfg);
+}
+bool wide_plan_of(const TtGemmArgs* a, Plan* pl) {
+  const Route narrow = wanted_route(a);
+  if (wide_own_plan(a, narrow)) { *pl = Plan{narrow.cfg, 1}; return true; }
+  if (knobs().wide != 0 && extents_of(a).a0 >= k2G) { *pl = wide_plan(a); return true; }
+  return false;
+}
+// tt_gemm only: the reason a problem that needs the wide route and would get it cannot have it (nullptr: it can, does not need it, or
+// stays with the narrow route's own refusal)
+const char* wide_refusal(const TtGemmArgs* a) {
+  if (knobs().wide == 0 || !needs_wide(a)) return nullptr;
+  if (extents_of(a).w >= k2G) return nullptr;                // (W stays refused with the narrow route's message)
+  if (const char* what = wide_unserved(a)) { static thread_local char msg[160]; snprintf(msg, sizeof msg, "the wide route (an operand of 2 GiB or more) does not serve %s", what); return msg; }
+  Plan pl;
+  if (!wide_plan_of(a, &pl)) return nullptr;
+  return wide_window_refusal(a, tile_of(a->dtype, pl.cfg).bm);
+}
+Route resolve(const TtGemmArgs* a) {
+  if (wide_asked(a) && !wide_unserved(a) && extents_of(a).w < k2G) {
+    Plan pl;
+    if (wide_plan_of(a, &pl) && !wide_window_refusal(a, tile_of(a->dtype, pl.cfg).bm)) return Route{Kind::TILED, pl.cfg, 1, 0, true};
+  }
+  return granted_route(a, wanted_route(a));
+}
 
 // the tile of a route as tt_gemm_plan reports it: nst = 0 marks the kernels that are not the tiled template's ring
 TileCfg route_tile(const TtGemmArgs* a, const Route& r) {
@@ -424,7 +558,7 @@ int32_t stats_rows_on(const TtGemmArgs* a, const Route& r) {
 }
 // tt_gemm_gn_fused on a resolved route
 int32_t gn_fused_on(const TtGemmArgs* a, const Route& r) {
-  if (is_up2(a)) return 0;
+  if (is_up2(a) || r.wide) return 0;
   if (a->dtype == TT_F32 || a->geglu || a->out_fp8 || a->out_f32 || a->out_col_hw > 0 || a->stats_out) return 0;
   const int seg = a->stats_seg;
   if (seg <= 0 || a->m % seg || (a->n & 127)) return 0;               // 32 groups of a whole number of column quads
@@ -447,6 +581,15 @@ extern "C" int tt_gemm_set_streaming_square(int32_t on) {
 }
 extern "C" int tt_gemm_set_f32_split(int32_t on) { knobs().f32_split = on ? 1 : 0; return TT_OK; }
 extern "C" int tt_gemm_set_big_tile(int32_t on) { knobs().w320 = big_tile_bits(on); return TT_OK; }
+extern "C" int tt_gemm_set_wide(int32_t on) {
+  if (on < 0 || on > 2) TT_FAIL(TT_EINVAL, "tt_gemm_set_wide: %d (0 never, 1 when an operand needs it, 2 whenever it can serve)", on);
+  knobs().wide = on;
+  return TT_OK;
+}
+extern "C" int32_t tt_gemm_is_wide(const TtGemmArgs* a) {
+  if (!a || a->m <= 0 || a->n <= 0) return 0;
+  return resolve(a).wide ? 1 : 0;
+}
 
 extern "C" int tt_gemm_plan(const TtGemmArgs* a, int32_t cfg[7]) {
   if (!a || !cfg || a->m <= 0 || a->n <= 0) TT_FAIL(TT_EINVAL, "tt_gemm_plan: bad arguments");
@@ -474,6 +617,7 @@ extern "C" int32_t tt_gemm_gn_fused(const TtGemmArgs* a) {
 // the slabs of the wanted route (a two-part launch: of its tail, the only part that may split)
 extern "C" size_t tt_gemm_ws_bytes(const TtGemmArgs* a) {
   if (!a || a->m <= 0 || a->n <= 0) return 0;
+  if (resolve(a).wide) return 0;                        // never split along K
   const Route r = wanted_route(a);
   if (r.kind == Kind::PP_TWO_PART) { TtGemmArgs head, tail; pp_split(a, r.head_rows, &head, &tail); return tt_gemm_ws_bytes(&tail); }
   return (r.kind == Kind::W320H_SPLIT || r.kind == Kind::TILED) && r.splitk > 1 ? slab_bytes(a, r.splitk) : 0;
@@ -532,16 +676,24 @@ int fill_params(const TtGemmArgs* a, const Route& r, GemmP& p) {
   p.taps = is_up2(a) ? 16 : gemm_taps(p.mode);            // (upsample = 2: 4 phases x 4 taps of the phase-packed weight)
   {
     const long rows = p.mode == 1 || p.mode == 3 ? (long)p.nimg * p.hin * p.win : (long)p.m;
-    const long a0b = ((rows - 1) * p.lda0 + p.k0) * es, a1b = p.k1 ? ((rows - 1) * p.lda1 + p.k1) * es : 16;
+    long a0b = ((rows - 1) * p.lda0 + p.k0) * es;
+    const long a1b = p.k1 ? ((rows - 1) * p.lda1 + p.k1) * es : 16;
     const long wb = ((long)(p.n - 1) * p.ldw + (long)p.taps * (p.k0 + p.k1)) * es;
+    if (r.wide && a0b >= (1L << 31)) a0b = (1L << 31) - 1;           // (the wide variant windows a0 itself: the field is not read)
     if (a0b >= (1L << 31) || a1b >= (1L << 31) || wb >= (1L << 31))
       TT_FAIL(TT_EUNSUPPORTED, "tt_gemm: operand larger than 2 GiB (32-bit buffer offsets)");
     p.a0_bytes = (unsigned)a0b; p.a1_bytes = (unsigned)a1b; p.w_bytes = (unsigned)wb;
     // epilogue operands (bounds-checked descriptors; 0 bytes = absent -> loads return 0)
     const long n_out = p.geglu ? p.n / 2 : p.n;
-    const long outb = ((long)(p.m - 1) * p.ldo + (p.out_col_hw > 0 ? p.ldo : n_out)) * (p.out_f32 ? 4 : (p.out_fp8 ? 1 : es));
-    const long resb = p.residual ? ((long)(p.m - 1) * p.ld_res + p.n) * es : 0;
-    const long blb = p.blend ? ((long)(p.m - 1) * p.ld_blend + p.n) * es : 0;
+    long outb = ((long)(p.m - 1) * p.ldo + (p.out_col_hw > 0 ? p.ldo : n_out)) * (p.out_f32 ? 4 : (p.out_fp8 ? 1 : es));
+    long resb = p.residual ? ((long)(p.m - 1) * p.ld_res + p.n) * es : 0;
+    long blb = p.blend ? ((long)(p.m - 1) * p.ld_blend + p.n) * es : 0;
+    if (r.wide) {                                                     // (windowed by the kernel / reached through 64-bit pointers: not read)
+      const long cap = (1L << 31) - 1;
+      if (outb > cap) outb = cap;
+      if (resb > cap) resb = cap;
+      if (blb > cap) blb = cap;
+    }
     long rv_last = p.rowvec ? (p.m - 1) / p.rowvec_rows : 0;             // last row-vector index the kernel can form
     if (p.rowvec_mod > 0 && rv_last > p.rowvec_mod - 1) rv_last = p.rowvec_mod - 1;
     const long rvb = p.rowvec ? (rv_last * p.ld_rowvec + p.n) * 4 : 0;
@@ -575,6 +727,7 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
   if (a->mode < 0 || a->mode > 3) TT_FAIL(TT_EINVAL, "tt_gemm: bad mode %d", a->mode);
   if (a->mode == 3 && a->upsample) TT_FAIL(TT_EINVAL, "tt_gemm: mode 3 (bottom / right zero padding) has no fused upsample");
   if (is_up2(a)) if (const char* why = up2_refusal(a)) TT_FAIL(TT_EINVAL, "tt_gemm: upsample = 2 needs %s", why);
+  if (const char* why = wide_refusal(a)) TT_FAIL(TT_EUNSUPPORTED, "tt_gemm: %s", why);
   const Route r = resolve(a);
   if (r.kind == Kind::PP_TWO_PART) {                        // whole tile rows -> persistent kernel, the rest -> whatever serves it; each half is checked in full below
     TtGemmArgs head, tail;
@@ -592,7 +745,11 @@ extern "C" int tt_gemm(const TtGemmArgs* a, tt_stream_t stream) {
     case Kind::W320: launch_w320(p, st, 256, bf16); break;
     case Kind::W320H: case Kind::W320H_SPLIT: launch_w320(p, st, 128, bf16); break;
     case Kind::TILED:
-      if (bf16) launch_bf16(p, r.cfg, st);
+      if (r.wide) {
+        if (bf16) launch_wide_bf16(p, r.cfg, st);
+        else if (a->dtype == TT_F16) launch_wide_f16(p, r.cfg, st);
+        else launch_wide_f32(p, r.cfg, st);
+      } else if (bf16) launch_bf16(p, r.cfg, st);
       else if (a->dtype == TT_F16) launch_f16(p, r.cfg, st);
       else launch_f32(p, r.cfg, st);
       break;

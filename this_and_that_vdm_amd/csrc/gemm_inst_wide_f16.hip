@@ -1,0 +1,8 @@
+// instantiation unit: the wide (windowed) variants of tt_gemm's tiled template for one storage type (TT_GEMM_WIDE_TILES in gemm_kernel.h)
+#include "gemm_kernel.h"
+namespace ttg {
+void launch_wide_f16(GemmP& p, int cfg, hipStream_t st) {
+  using Tag = f16_tag;
+  switch (cfg) { TT_GEMM_WIDE_TILES(TT_WIDE_CASE) }
+}
+}

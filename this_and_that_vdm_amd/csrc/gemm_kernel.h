@@ -230,6 +230,25 @@ __device__ __forceinline__ void epilogue_quad(const GemmP& p, int gm, int gn, fl
   epi_finish<Tag>(p, o, gm, gn, v);
 }
 
+// The pass-loop epilogue arithmetic of one element, spelled out operation by operation for the WIDE variant of gemm_kernel.  The narrow
+// instances leave `(t + bias) * scale + rowvec`, `+ residual` and `alpha * blend + (1 - alpha) * w` to hipcc, which contracts them the same
+// way in every one of them (disassembly: add, fma, [add,] mul, fma); in the wide variant's slightly different surroundings it fused some
+// elements and not others, which costs the last bit of an fp32 result.  Written out, the wide variant's bits are the narrow ones' by
+// construction.  INPASS: the row vector (zero where absent) rides on the scale's fma and the residual is added after it; otherwise the
+// residual rides on the fma.  BLEND_MUL_FIRST: the instances that read the residual in-pass (the split16 ones among the wide tiles) form
+// alpha * blend first and fuse (1 - alpha) * w onto it; the ones that preload it fuse alpha * blend onto (1 - alpha) * w.
+template <bool INPASS, bool BLEND_MUL_FIRST>
+__device__ __forceinline__ float wide_epi_elem(float t, float bias, float scale, float rv, float res, float bl, float alpha, float one_m_alpha) {
+#pragma clang fp contract(off)
+  const float u = t + bias;
+  float w;
+  if constexpr (INPASS) { w = __builtin_fmaf(scale, u, rv); w = w + res; }
+  else w = __builtin_fmaf(scale, u, res);
+  if constexpr (BLEND_MUL_FIRST) { const float x = alpha * bl; return __builtin_fmaf(one_m_alpha, w, x); }
+  const float x = one_m_alpha * w;
+  return __builtin_fmaf(alpha, bl, x);
+}
+
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
@@ -277,9 +296,17 @@ void gemm_kernel(const GemmP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool SPLIT = (KMODE_ & 8) != 0;            // f32_tag only: KMODE + 8 = the same kernel with split-fp16 products (see `mma`)
   constexpr bool PRE_B = (KMODE_ & 16) != 0, PRE_A = (KMODE_ & 32) != 0;      // ... + 16 / + 32: the W / A operand arrives pre-split (GemmP.presplit)
+  // + 64: the WINDOWED ("wide") variant for operands of 2 GiB and more.  The narrow kernel puts one descriptor on each operand's base and
+  // gives every lane a 32-bit byte offset into it; here every workgroup rebases the descriptors of a0 / out / residual / blend once per
+  // tile in 64-bit scalar arithmetic -- onto the first row the tile can touch -- and the lanes' offsets count from that row.  num_records
+  // is the rest of the operand capped below 2^31, so an offset of 0x80000000 still reads zeros / drops the store; tt_gemm refuses a
+  // problem in which one tile's window itself reaches 2 GiB.  Same tile, ring, K order and epilogue arithmetic as KMODE_ - 64: the same
+  // bits.  Built for modes 0 / 1 / 2 with the bias / scale / residual / blend / fp32-out epilogues and stats_out (launch_cfg_wide).
+  constexpr bool WIDE = (KMODE_ & 64) != 0;
   constexpr int KMODE = KMODE_ & 7;
   static_assert(SPLIT || (!PRE_A && !PRE_B), "pre-split operands belong to the split variants");
   static_assert(!SPLIT || std::is_same<Tag, f32_tag>::value, "split products are a TT_F32 mode");
+  static_assert(!WIDE || ((KMODE_ & 7) <= 2 && !PRE_A && !PRE_B), "the wide variant: modes 0 / 1 / 2, operands not pre-split");
   constexpr bool PAD_BR = KMODE == 5;                  // mode-3 conv: taps start at the output pixel's own (strided) position
   constexpr int MODE = PAD_BR ? 1 : (KMODE >= 3 ? 0 : KMODE);                   // gather mode
   constexpr int LN = KMODE == 3 || KMODE == 4 ? KMODE - 2 : 0;                  // 0 none, 1 statistics of A rows, 2 of W rows
@@ -334,7 +361,25 @@ void gemm_kernel(const GemmP p) {
   // must read zeros (ragged M/N, conv halo, K tail) use an offset beyond num_records: the hardware bounds check returns 0.
   // This keeps the per-K-step instruction count at ~1 per load (the loop is otherwise instruction-issue bound).
   constexpr int INV = (int)0x80000000;
-  const __amdgpu_buffer_rsrc_t ra0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.a0, 0, p.a0_bytes, 0x00020000);
+  // WIDE: window of operand `base` (row stride ld elements, `total` bytes in all) from row `row0` on
+  auto window = [&](const char* base, long row0, long ld, long total) {
+    const long off = row0 * ld * ES;
+    long rest = total - off;
+    if (rest > 0x7fffffffL) rest = 0x7fffffffL;
+    return make_rsrc(base + off, (!base || rest < 0) ? 0u : (unsigned)rest);
+  };
+  long a_org = 0;                   // WIDE: first row of a0 the tile can read -- the window's origin
+  if constexpr (WIDE) {
+    if constexpr (MODE == 0) a_org = m0;
+    else if constexpr (MODE == 1) a_org = (long)fdiv(m0, p.fd_hwo) * p.hin * p.win;       // start of the image that holds output row m0
+    else {                                                                              // m0 - hw, not before the start of m0's frame group
+      const int grp0 = fdiv(fdiv(m0, p.fd_hw), p.fd_frames) * p.frames * p.hw;
+      a_org = m0 - p.hw > grp0 ? m0 - p.hw : grp0;
+    }
+  }
+  const long a_rows_all = MODE == 1 ? (long)p.nimg * p.hin * p.win : (long)p.m;
+  const __amdgpu_buffer_rsrc_t ra0 = WIDE ? window(p.a0, a_org, p.lda0, ((a_rows_all - 1) * p.lda0 + p.k0) * ES)
+                                          : __builtin_amdgcn_make_buffer_rsrc((void*)p.a0, 0, p.a0_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t ra1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.a1 ? p.a1 : p.a0), 0, p.a1_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
   const int crow = tid / CPR, cchunk = tid % CPR;
@@ -353,7 +398,7 @@ void gemm_kernel(const GemmP p) {
     a_img[i] = a_y[i] = a_x[i] = 0;
     if constexpr (MODE == 0) {
       if (a_valid[i]) {
-        va0[i] = (int)(((long)g * p.lda0 + a_chunk[i] * EPC) * ES);
+        va0[i] = (int)(((long)(g - a_org) * p.lda0 + a_chunk[i] * EPC) * ES);
         va1[i] = (int)(((long)g * p.lda1 + a_chunk[i] * EPC) * ES);
       }
     } else if constexpr (MODE == 1) {
@@ -411,7 +456,7 @@ void gemm_kernel(const GemmP p) {
             ok = ok && f >= 0 && f < p.frames;
             row = (long)a_y[i] + (long)(s_tap - 1) * p.hw;
           }
-          va0[i] = ok ? (int)((row * p.lda0 + a_chunk[i] * EPC) * ES) : INV;
+          va0[i] = ok ? (int)(((row - a_org) * p.lda0 + a_chunk[i] * EPC) * ES) : INV;
           va1[i] = ok ? (int)((row * p.lda1 + a_chunk[i] * EPC) * ES) : INV;
         }
       }
@@ -708,6 +753,7 @@ void gemm_kernel(const GemmP p) {
   quad_t resv[EARLY_RES ? FM : 1][EARLY_RES ? NCH : 1][8];   // 256-row tiles read the residual inside the passes
   const bool direct = (p.out_col_hw > 0 || p.out_f32) && p.splitk == 1;   // rare layouts keep the simple per-fragment path
   const bool blend_is_res = p.blend && p.blend == p.residual && p.ld_blend == p.ld_res;
+  const int e_org = WIDE ? m0 : 0;       // WIDE: first row of the tile -- origin of the residual / blend / out windows
   auto preload_residual = [&]() {
     if constexpr (EARLY_RES) {
 #pragma unroll
@@ -720,7 +766,7 @@ void gemm_kernel(const GemmP p) {
     // (no residual: nothing is requested -- loads through a 0-byte descriptor return 0, but still cost their issue slots in the
     // texture addresser: 0.5 us per launch for two resident 128 x 128 tiles, tools/gemm_timeline.py)
     if constexpr (EARLY_RES) if (!direct && !p.geglu && p.splitk == 1 && p.residual) {
-      const __amdgpu_buffer_rsrc_t r_res = make_rsrc(p.residual, p.res_bytes);
+      const __amdgpu_buffer_rsrc_t r_res = WIDE ? window(p.residual, e_org, p.ld_res, ((long)(p.m - 1) * p.ld_res + p.n) * ES) : make_rsrc(p.residual, p.res_bytes);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -733,7 +779,7 @@ void gemm_kernel(const GemmP p) {
             resv[i][c][pass] = zero_quad<Tag>();
             if (pass * rows_per_pass < 32) {
               const int gm = m0 + wr * WTM + i * 32 + pass * rows_per_pass + lane / q_per_row;
-              resv[i][c][pass] = ldq<Tag>(r_res, (gm < p.m && gn < p.n) ? (int)(((long)gm * p.ld_res + gn) * ES) : kInv);
+              resv[i][c][pass] = ldq<Tag>(r_res, (gm < p.m && gn < p.n) ? (int)(((long)(gm - e_org) * p.ld_res + gn) * ES) : kInv);
             }
           }
         }
@@ -868,12 +914,17 @@ void gemm_kernel(const GemmP p) {
   TL(3);
   if (!direct) {
     const __amdgpu_buffer_rsrc_t r_bias = make_rsrc(p.bias, p.bias_bytes);
-    const __amdgpu_buffer_rsrc_t r_out = p.splitk > 1 ? make_rsrc(p.ws, p.ws_bytes) : make_rsrc(p.out, p.out_bytes);
+    // WIDE (never split along K): the out window starts at the tile's first output row; phase-packed form: slice (py, px) stores low-res
+    // row gm = (img, y, x) to output row 4 gm - 2 x + (py 2 win + px), which grows with gm -- the origin is that of m0 in phase (0, 0)
+    const int o_org = !WIDE ? 0 : ((MODE == 1 && !PAD_BR && p.phases) ? 4 * m0 - 2 * (m0 - fdiv(m0, p.fd_wout) * p.win) : m0);
+    const long o_rows_all = (MODE == 1 && !PAD_BR && p.phases) ? 4L * p.m : (long)p.m;
+    const __amdgpu_buffer_rsrc_t r_out = WIDE ? window(p.out, o_org, p.ldo, ((o_rows_all - 1) * p.ldo + p.n) * ES)
+                                         : (p.splitk > 1 ? make_rsrc(p.ws, p.ws_bytes) : make_rsrc(p.out, p.out_bytes));
     // strip = 32 rows x 256 bytes per wave, 16-byte quads XOR-swizzled by the row (no padding: 8 KiB per wave)
     auto strip_off = [](int row, int quad, int nq) { return row * 256 + ((quad ^ (row & (nq - 1))) << 4); };
     char* ebuf = smem + wid * 8192;
     static_assert(WGM * WGN * 8192 <= NST * STAGE, "epilogue strips do not fit the ring");
-    if (!p.geglu) {
+    if (WIDE || !p.geglu) {
       // bias of the 4 columns this lane finishes in each 64-column chunk (row-independent: loaded once)
       float4 bias4[NCH];
 #pragma unroll
@@ -902,8 +953,10 @@ void gemm_kernel(const GemmP p) {
         // GemmP.stats, compile-time like the operand variants (a run-time `if` inside the pass loops breaks the straight-line code)
         constexpr bool STATS = decltype(stats_tag)::value;
         const __amdgpu_buffer_rsrc_t r_rv = make_rsrc(p.rowvec, (FILM || INPASS) ? p.rowvec_bytes : 0);
-        const __amdgpu_buffer_rsrc_t r_bl = make_rsrc(p.blend, INPASS ? p.blend_bytes : 0);
-        const __amdgpu_buffer_rsrc_t r_res = make_rsrc(p.residual, (INPASS && !EARLY_RES) ? p.res_bytes : 0);
+        const __amdgpu_buffer_rsrc_t r_bl = (WIDE && INPASS) ? window(p.blend, e_org, p.ld_blend, ((long)(p.m - 1) * p.ld_blend + p.n) * ES)
+                                                             : make_rsrc(p.blend, INPASS ? p.blend_bytes : 0);
+        const __amdgpu_buffer_rsrc_t r_res = (WIDE && INPASS && !EARLY_RES) ? window(p.residual, e_org, p.ld_res, ((long)(p.m - 1) * p.ld_res + p.n) * ES)
+                                                                            : make_rsrc(p.residual, (INPASS && !EARLY_RES) ? p.res_bytes : 0);
         const int rv_rows = p.rowvec ? p.rowvec_rows : 1;
         // periodic row vector (rowvec_mod): group indices wrap; the even / odd form (one row per group, period 2) stays on the
         // two-vector path below with the row's parity as the selector
@@ -955,10 +1008,10 @@ void gemm_kernel(const GemmP p) {
                   const int gm = mb + pass * rows_per_pass + rr;
                   const bool ok = gm < p.m && gn < p.n;
                   if constexpr (EARLY_RES) rqv[k] = resv[i][jc / 2][pass];
-                  else if constexpr (INPASS) rqv[k] = ldq<Tag>(r_res, ok ? (int)(((long)gm * p.ld_res + gn) * ES) : kInv);
+                  else if constexpr (INPASS) rqv[k] = ldq<Tag>(r_res, ok ? (int)(((long)(gm - e_org) * p.ld_res + gn) * ES) : kInv);
                   if constexpr (INPASS) {
                     rvv[k] = ld128f(r_rv, ok ? (int)(((long)wrap(fdiv(gm, p.fd_rv_rows)) * p.ld_rowvec + gn) * 4) : kInv);
-                    blv[k] = ldq<Tag>(r_bl, ok ? (int)(((long)gm * p.ld_blend + gn) * ES) : kInv);
+                    blv[k] = ldq<Tag>(r_bl, ok ? (int)(((long)(gm - e_org) * p.ld_blend + gn) * ES) : kInv);
                   }
                 }
               }
@@ -995,11 +1048,16 @@ void gemm_kernel(const GemmP p) {
                     quad_to_f32<Tag>(bq, b4v);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = alpha * b4v[e] + one_m_alpha * (v[e] + r4[e]);
+                    if constexpr (WIDE) {                // the same arithmetic with its contractions written out (wide_epi_elem)
+                      const float tv[4] = {t.x, t.y, t.z, t.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w}, rv4[4] = {rvv[k].x, rvv[k].y, rvv[k].z, rvv[k].w};
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) v[e] = wide_epi_elem<INPASS, !EARLY_RES>(tv[e], bv[e], p.acc_scale, rv4[e], r4[e], b4v[e], alpha, one_m_alpha);
+                    }
                     if constexpr (OUT8) st32(r_out, ok ? (int)((long)gm * p.ldo + gn) : kInv, pack4_fp8(v));
                     else {
                       const quad_t packed = f32_to_quad<Tag>(v);
-                      if constexpr (ES == 2) st64(r_out, ok ? (int)(((long)orow * p.ldo + gn) * ES) : kInv, packed.x, packed.y);
-                      else stq<Tag>(r_out, ok ? (int)(((long)orow * p.ldo + gn) * ES) : kInv, v);
+                      if constexpr (ES == 2) st64(r_out, ok ? (int)(((long)(orow - o_org) * p.ldo + gn) * ES) : kInv, packed.x, packed.y);
+                      else stq<Tag>(r_out, ok ? (int)(((long)(orow - o_org) * p.ldo + gn) * ES) : kInv, v);
                       if constexpr (STATS) {               // (rows >= m of a ragged last tile add nothing)
                         float sv[4];
                         quad_to_f32<Tag>(packed, sv);
@@ -1020,7 +1078,11 @@ void gemm_kernel(const GemmP p) {
       constexpr std::false_type no{};
       constexpr std::true_type yes{};
       const bool kstats = p.stats && p.splitk == 1;          // (a K slice leaves the sums to the reduction kernel)
-      if (inpass) run(no, yes, no, no, no);                  // (never with statistics: tt_gemm_stats_rows)
+      if constexpr (WIDE) {                                  // the wide variant's epilogues: bias / scale / residual / blend (+ statistics), and the phase form
+        if (inpass) run(no, yes, no, no, no);
+        else if (MODE == 1 && p.phases) { if constexpr (MODE == 1) run(no, no, no, no, yes); }
+        else { if (kstats) run(no, no, no, yes, no); else run(no, no, no, no, no); }
+      } else if (inpass) run(no, yes, no, no, no);                  // (never with statistics: tt_gemm_stats_rows)
       else if (p.rowvec) { if (kstats) run(yes, no, no, yes, no); else run(yes, no, no, no, no); }
       else if (MODE == 0 && ES == 2 && p.out_fp8) {          // Q | K and V^T of the fp8 attention path (linear, no residual)
         if constexpr (MODE == 0 && ES == 2) run(no, no, yes, no, no);
@@ -1496,7 +1558,9 @@ void launch_mode(const GemmP& p, hipStream_t st) {
   tt_lds_opt_in((const void*)gemm_kernel<Tag, BM, BN, BK, NST, WGM, WGN, MODE>, (int)(lds + stat_lds), &attr_done);
   hipLaunchKernelGGL((gemm_kernel<Tag, BM, BN, BK, NST, WGM, WGN, MODE>), dim3(p.tiles_m * p.tiles_n * p.slices),
                      dim3(64 * WGM * WGN), (p.stats && p.splitk == 1) ? lds + stat_lds : lds, st, p);
-  if (p.splitk > 1) launch_splitk_epilogue<Tag>(p, st);
+  if constexpr ((MODE & 64) == 0) {            // (the wide variant never splits along K)
+    if (p.splitk > 1) launch_splitk_epilogue<Tag>(p, st);
+  }
 }
 
 // LNOK: also instantiate the fused-LayerNorm variants (only the tile shapes the planner picks; gemm.hip keeps LayerNorm
@@ -1516,8 +1580,9 @@ static inline void fill_fastdivs(GemmP& p) {
   p.fd_rv_mod = make_fastdiv(p.rowvec_mod > 0 ? p.rowvec_mod : 1);
 }
 
-template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN, bool LNOK = false, bool M3OK = false>
-void launch_cfg(GemmP& p, hipStream_t st) {
+// what every launch on a tile shape derives from the problem first: tile counts, the launch order's group height, K steps, divisors
+template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN>
+void tile_params(GemmP& p) {
   p.tiles_m = ceil_div(p.m, BM);
   p.tiles_n = ceil_div(p.n, BN);
   {
@@ -1538,6 +1603,32 @@ void launch_cfg(GemmP& p, hipStream_t st) {
   p.kt_total = p.taps * (p.nk0 + p.nk1);
   p.slices = p.phases ? 4 : p.splitk;
   fill_fastdivs(p);
+}
+
+// the wide variant (KMODE + 64, see gemm_kernel) of a tile shape: modes 0 / 1 / 2, un-split, operands not pre-split (tt_gemm refuses the rest)
+template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN>
+void launch_cfg_wide(GemmP& p, hipStream_t st) {
+  tile_params<Tag, BM, BN, BK, NST, WGM, WGN>(p);
+  if constexpr (std::is_same<Tag, f32_tag>::value) {
+    if (p.f32_split) {
+      switch (p.mode) {
+        case 0: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 8>(p, st); break;
+        case 1: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 9>(p, st); break;
+        default: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 10>(p, st); break;
+      }
+      return;
+    }
+  }
+  switch (p.mode) {
+    case 0: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64>(p, st); break;
+    case 1: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 1>(p, st); break;
+    default: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 2>(p, st); break;
+  }
+}
+
+template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN, bool LNOK = false, bool M3OK = false>
+void launch_cfg(GemmP& p, hipStream_t st) {
+  tile_params<Tag, BM, BN, BK, NST, WGM, WGN>(p);
   if (p.mode == 3) {                         // routed explicitly: the switches below send unknown modes elsewhere
     if constexpr (M3OK) {
       if constexpr (std::is_same<Tag, f32_tag>::value) {
@@ -1638,6 +1729,25 @@ template <int N> constexpr bool tiles_in_order(const TileCfg (&t)[N]) {
   return true;
 }
 static_assert(tiles_in_order(kCfgs) && tiles_in_order(kCfgsF32), "a tile's index is its position in the table (the planner and launch() both go by it)");
+
+// ---- the tile shapes whose wide variant is built, by index into the tables above: what the planner gives a problem with an operand of
+// 2 GiB or more -- 128 x 128 with 8 waves from 384 tiles on (16-bit) / from 256 tiles on (TT_F32) -- and what it gives the small strided
+// problems of the tests (one block per CU with the 4-deep ring; the 64 x 64 TT_F32 tile).  X(index, BM, BN, BK, NST, WGM, WGN)
+#define TT_GEMM_WIDE_TILES(X) \
+  X(11, 128, 128,  64, 2, 4, 2) \
+  X(16, 128, 128,  64, 4, 4, 2)
+#define TT_GEMM_WIDE_TILES_F32(X) \
+  X( 0, 128, 128,  32, 2, 2, 2) \
+  X( 1,  64,  64,  32, 4, 2, 2)
+#define TT_WIDE_SAME(i, bm_, bn_, bk_, nst_, wgm_, wgn_) && t[i].bm == bm_ && t[i].bn == bn_ && t[i].bk == bk_ && t[i].nst == nst_ && t[i].wgm == wgm_ && t[i].wgn == wgn_
+template <int N> constexpr bool wide_tiles_match16(const TileCfg (&t)[N]) { return true TT_GEMM_WIDE_TILES(TT_WIDE_SAME); }
+template <int N> constexpr bool wide_tiles_match32(const TileCfg (&t)[N]) { return true TT_GEMM_WIDE_TILES_F32(TT_WIDE_SAME); }
+#undef TT_WIDE_SAME
+static_assert(wide_tiles_match16(kCfgs) && wide_tiles_match32(kCfgsF32), "a wide tile is the narrow tile of the same index");
+#define TT_WIDE_IS(i, bm, bn, bk, nst, wgm, wgn) || cfg == i
+constexpr bool wide_capable(bool f32, int cfg) { return f32 ? (false TT_GEMM_WIDE_TILES_F32(TT_WIDE_IS)) : (false TT_GEMM_WIDE_TILES(TT_WIDE_IS)); }
+#undef TT_WIDE_IS
+#define TT_WIDE_CASE(i, bm, bn, bk, nst, wgm, wgn) case i: launch_cfg_wide<Tag, bm, bn, bk, nst, wgm, wgn>(p, st); break;
 
 // cfg = index into the table of Tag's storage type; an index outside it launches nothing (the planner hands out none)
 #define TT_TILE_CASE(i, bm, bn, bk, nst, wgm, wgn, ln, m3) case i: launch_cfg<Tag, bm, bn, bk, nst, wgm, wgn, ln, m3>(p, st); break;

@@ -123,6 +123,15 @@ def f32_split() -> bool:
     return _F32_SPLIT
 
 
+def set_gemm_wide(on: int) -> None:
+    """Process-wide: when gemm() takes tt_gemm's wide route (windowed descriptors for operands of 2 GiB and more): 0 never (such a
+    problem is refused), 1 (default) when an operand needs it, 2 whenever the wide kernels can serve the problem (tests, measurements)."""
+    check(_lib.load().tt_gemm_set_wide(int(on)), "tt_gemm_set_wide")
+
+
+WIDE_LAUNCHES = 0          # gemm() launches that ran on the wide route since the process started (tests and tools read the difference)
+
+
 _TAG = {TT_BF16: "bf16_tag", TT_F16: "f16_tag", TT_F32: "f32_tag"}
 FP8 = torch.float8_e4m3fn          # OCP e4m3 (gfx950's fp8; not MI300's fnuz)
 
@@ -229,6 +238,10 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
             g.stats_out = sbuf.data_ptr()
     ev = _prof_begin()
     check(lib.tt_gemm(C.byref(g), _stream()), "tt_gemm")
+    wide = bool(lib.tt_gemm_is_wide(C.byref(g)))           # (host-only: the resolved route of the launch just made)
+    if wide:
+        global WIDE_LAUNCHES
+        WIDE_LAUNCHES += 1
     serial = _wrote(out)                                    # `out` was overwritten: sums attached by an earlier launch are dropped
     if sbuf is not None:
         out._tt_stats = (sbuf, srows, serial, out.data_ptr(), tuple(out.shape))
@@ -251,6 +264,8 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
             kmode = (5 if mode == 3 else mode if not ln_fold else 2 + ln_fold) + (8 if (g.dtype == TT_F32 and _F32_SPLIT) else 0)     # + 8: split-fp16 products
             if mode == 3:                            # (the mode-3 gather, gemm_kernel.h KMODE 5: + 16 when the weight arrives pre-split)
                 kmode += 16 if g.presplit & 2 else 0
+            if wide:                                 # the windowed variant of the same tile (gemm_kernel.h KMODE + 64)
+                kmode += 64
             kname = f"gemm_kernel<{tag}, {', '.join(str(v) for v in cfg[:6])}, {kmode}>"
         _prof_end(ev, kname, 2.0 * g.m * n * taps * (g.k0 + g.k1),
                   shape=(mode, g.m, n, taps * (g.k0 + g.k1), int(geglu), int(residual is not None)))
