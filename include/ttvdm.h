@@ -640,6 +640,58 @@ int tt_vae_image(const void* src, int32_t nimg, int32_t h, int32_t w, int32_t ou
                  int32_t ksize_x, const int32_t* tab_y, int32_t ksize_y, const float* noise, float na, int32_t nvid, void* dst,
                  int32_t dtype, void* ws, size_t ws_bytes, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * tt_tensor_stats: the range audit's instrument -- ONE pass over a row-strided 2-D tensor x [rows, cols] (row stride ldx elements,
+ * columns cols..ldx-1 of a row are never read) fills a fixed-size DEVICE record with exact integer counts and bit-exact extrema.
+ * Nothing in the denoise path calls it unless an audit is active (this_and_that_vdm_amd/audit.py).  Additive: the ABI version is
+ * unchanged.
+ *
+ * dtype: TT_BF16, TT_F16, TT_F32 or TT_FP8_E4M3 (OCP e4m3 bytes, what tt_gemm's out_fp8 writes: no infinities, S.1111.111 is NaN).
+ * Every value is widened to fp32 first (exact for all four) and classified on the fp32 bit pattern u, a = u & 0x7fffffff:
+ *   NaN a > 0x7f800000, +-inf a == 0x7f800000 (by sign), zero a == 0 (both signs), everything else "finite non-zero".
+ *
+ * TtTensorStats -- 616 bytes, every field naturally aligned, no padding (byte offsets in brackets):
+ *   [  0] uint64 count             rows * cols
+ *   [  8] uint64 n_nan   [ 16] n_pinf   [ 24] n_ninf   [ 32] n_zero
+ *   [ 40] uint64 n_ge[4]           finite values with |x| >= thr[i] (thr: four fp32 thresholds, >= 0, not NaN; +inf never counts)
+ *   [ 72] uint64 hist[64]          finite non-zero values by biased fp32 exponent E = a >> 23: bin = clamp(E - 127 + 40, 0, 63), i.e. bin b
+ *                                  holds [2^(b-40), 2^(b-39)); fp32 subnormals (E = 0) and everything below 2^-40 land in bin 0
+ *   [584] double sum               over finite values, fp64
+ *   [592] double sum_sq            over finite values, fp64 (the square of an fp32 value is exact in fp64)
+ *   [600] float  max_abs           over finite non-zero values; 0 when there are none
+ *   [604] float  min_abs_nonzero   over finite non-zero values; +inf when there are none
+ *   [608] float  max_val           over finite values (zeros included); -inf when there are none
+ *   [612] float  min_val           over finite values; +inf when there are none
+ * max_val / min_val order the bit patterns (-0 below +0), so every field but sum / sum_sq is independent of the summation order, and
+ * the launch order is fixed: the same input gives a byte-identical record every time.
+ *
+ * Launches: workgroups of TT_STATS_BLOCK lanes walk the tensor grid-strided (at most TT_STATS_MAX_GRID of them; 16-byte loads when
+ * x, ldx and cols allow -- a contiguous tensor, ldx == cols, is walked as one flat run with a scalar tail -- else one element per
+ * lane and trip), each writes its partial record to ws, and a second one-workgroup launch merges the partials into rec in a fixed
+ * order (eight runs of consecutive partials, each run in index order, then the runs in order).  A tensor that one workgroup covers takes one launch and no workspace.  No atomics on global memory, no flags or counters
+ * between workgroups.  No allocation and no synchronisation: capturable.
+ * accumulate != 0 merges into the record already at rec (counts, histogram and sums add, extrema combine) -- a replayed graph
+ * accumulates over steps; accumulate == 0 overwrites it.  rows == 0 or cols == 0: the empty record (accumulate: rec unchanged, no
+ * launch at all).
+ * ws: tt_tensor_stats_ws_bytes(rows, cols, dtype) bytes (0 for a one-workgroup tensor: ws may then be NULL), 8-byte aligned.
+ * tt_tensor_stats_launch reports (TT_STATS_MAX_GRID, TT_STATS_BLOCK, elements per 16-byte load of `dtype`) for tests and tools.
+ * TT_EINVAL: null x (non-empty tensor) / thr / rec; rows or cols < 0; ldx < cols with more than one row; a bad dtype; a threshold
+ * that is negative or NaN; x off its element size, rec or ws off an 8-byte boundary; a workspace that is missing or too small. */
+enum { TT_FP8_E4M3 = 3 };               /* tt_tensor_stats only: the other entry points name fp8 operands by their own switches */
+#define TT_STATS_BLOCK 256
+#define TT_STATS_MAX_GRID 1024
+typedef struct TtTensorStats {
+  uint64_t count, n_nan, n_pinf, n_ninf, n_zero;
+  uint64_t n_ge[4];
+  uint64_t hist[64];
+  double sum, sum_sq;
+  float max_abs, min_abs_nonzero, max_val, min_val;
+} TtTensorStats;
+int64_t tt_tensor_stats_ws_bytes(int64_t rows, int32_t cols, int32_t dtype);
+int tt_tensor_stats_launch(int32_t dtype, int32_t* max_grid /* host */, int32_t* block /* host */, int32_t* elems_per_load /* host */);
+int tt_tensor_stats(const void* x, int64_t ldx, int64_t rows, int32_t cols, int32_t dtype, const float* thr /* host [4] */,
+                    TtTensorStats* rec, void* ws, int64_t ws_bytes, int32_t accumulate, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("TT_LIBTTVDM") or os.path.join(CSRC, "libttvdm.so")      # TT_LIBTTVDM: A/B builds of the same ABI
 
 TT_BF16, TT_F16, TT_F32 = 0, 1, 2
+TT_FP8_E4M3 = 3          # tt_tensor_stats only (OCP e4m3 bytes, what gemm(out_fp8=True) writes)
 
 
 class TtGemmArgs(C.Structure):
@@ -75,6 +76,17 @@ class TtEncAttnArgs(C.Structure):
         ("v", C.c_void_p), ("ldv", C.c_int64), ("out", C.c_void_p), ("ldo", C.c_int64),
         ("nseq", C.c_int32), ("l", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
         ("causal", C.c_int32), ("k_seq_stride", C.c_int32), ("v_seq_stride", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
+class TtTensorStats(C.Structure):
+    """The device record of tt_tensor_stats: 616 bytes, the field order and offsets of include/ttvdm.h."""
+    _fields_ = [
+        ("count", C.c_uint64), ("n_nan", C.c_uint64), ("n_pinf", C.c_uint64), ("n_ninf", C.c_uint64), ("n_zero", C.c_uint64),
+        ("n_ge", C.c_uint64 * 4),
+        ("hist", C.c_uint64 * 64),
+        ("sum", C.c_double), ("sum_sq", C.c_double),
+        ("max_abs", C.c_float), ("min_abs_nonzero", C.c_float), ("max_val", C.c_float), ("min_val", C.c_float),
     ]
 
 
@@ -143,6 +155,10 @@ SIGNATURES = {
     "tt_resize_u8": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp]),
     "tt_vae_image_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "tt_vae_image": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _i32, _vp, _sz, _vp]),
+    # the range audit's one-pass tensor statistics (additive as well)
+    "tt_tensor_stats_ws_bytes": (_i64, [_i64, _i32, _i32]),
+    "tt_tensor_stats_launch": (C.c_int, [_i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tt_tensor_stats": (C.c_int, [_vp, _i64, _i64, _i32, _i32, C.POINTER(C.c_float), _vp, _vp, _i64, _i32, _vp]),
 }
 
 _lib = None

@@ -64,13 +64,21 @@ _SERIAL = itertools.count(1)
 _LAST_WRITE = {}
 
 
-def _wrote(t: torch.Tensor) -> int:
-    """record a raw-pointer write to (a view of) t's storage; returns the write's serial number"""
+# Optional range audit (audit.RangeAudit sets it for the length of a `with` block): every write the ledger records is then followed, on
+# the same stream, by a tt_tensor_stats pass over the tensor just written, into the record slot of the call's site.  None (the default):
+# one `is None` test per ledger write and nothing else -- no launch, no allocation, the same graph.
+AUDIT = None
+
+
+def _wrote(t: torch.Tensor, op: str = "op") -> int:
+    """record a raw-pointer write to (a view of) t's storage by the ops function `op`; returns the write's serial number"""
     n = next(_SERIAL)
     _LAST_WRITE[t.untyped_storage().data_ptr()] = n
     for name in ("_tt_stats", "_tt_gn"):
         if hasattr(t, name):
             delattr(t, name)
+    if AUDIT is not None:
+        AUDIT.record(t, op)
     return n
 
 
@@ -242,7 +250,9 @@ def gemm(a0: torch.Tensor, w: torch.Tensor, *, a1: Optional[torch.Tensor] = None
     if wide:
         global WIDE_LAUNCHES
         WIDE_LAUNCHES += 1
-    serial = _wrote(out)                                    # `out` was overwritten: sums attached by an earlier launch are dropped
+    serial = _wrote(out, "gemm")                            # `out` was overwritten: sums attached by an earlier launch are dropped
+    if gnbuf is not None:
+        _wrote(gnbuf, "gemm.gn_out")                        # the normalised copy the reduction pass wrote (a later launch reads it as an activation)
     if sbuf is not None:
         out._tt_stats = (sbuf, srows, serial, out.data_ptr(), tuple(out.shape))
     if gnbuf is not None:
@@ -307,7 +317,7 @@ def conv3x3(x0, x1, w, nimg: int, h: int, wd: int, *, gn=None, silu: bool = True
     a.out, a.ldo, a.dtype = _p(out), out.stride(0), _code(x0.dtype)
     ev = _prof_begin()
     check(lib.tt_conv3x3(C.byref(a), _stream()), "tt_conv3x3")
-    _wrote(out)
+    _wrote(out, "conv3x3")
     if ev is not None:
         k = 9 * (a.c0 + a.c1)
         _prof_end(ev, f"conv_patch_kernel<{_TAG[a.dtype]}>", 2.0 * nimg * h * wd * n * k, shape=(1, nimg * h * wd, n, k, 0, int(residual is not None)))
@@ -353,7 +363,7 @@ def attention(q, k, vt, out, *, nseq, lq, heads, head_dim, mask, lk, k_seq_strid
     a.v_rows = int(bool(v_rows))
     ev = _prof_begin()
     check(lib.tt_attention(C.byref(a), _stream()), "tt_attention")
-    _wrote(out)
+    _wrote(out, "attention")
     if ev is not None:
         tag = _TAG[a.dtype]
         if fp8:
@@ -371,7 +381,7 @@ def temporal_attention(qkv, out, *, batch, frames, hw, heads, head_dim):
     lib = _lib.load()
     check(lib.tt_temporal_attention(_p(qkv), qkv.stride(0), _p(out), out.stride(0), batch, frames, hw, heads, head_dim,
                                     _code(qkv.dtype), _stream()), "tt_temporal_attention")
-    _wrote(out)
+    _wrote(out, "temporal_attention")
     return out
 
 
@@ -401,7 +411,7 @@ def groupnorm_apply(x0, x1, nimg, hw, scale, shift, silu: bool, out=None):
     check(lib.tt_groupnorm_apply(_p(x0), c0, _p(x1), c1, nimg, hw, _p(scale), _p(shift), int(silu), _p(out), out.stride(0),
                                  _code(x0.dtype), _stream()), "tt_groupnorm_apply")
     _norm_trace("gn_apply_kernel", x0.dtype)
-    _wrote(out)
+    _wrote(out, "groupnorm_apply")
     return out
 
 
@@ -446,6 +456,7 @@ def groupnorm(x0, x1, nimg, hw, frames_per_group, gamma, beta, eps, silu: bool):
         check(lib.tt_groupnorm_tiles(_p(x0), c0, _p(st[0]), st[1], nimg // frames_per_group, frames_per_group * hw, _p(gamma), _p(beta), eps,
                                      int(silu), _p(out), out.stride(0), _code(x0.dtype), _stream()), "tt_groupnorm_tiles")
         _norm_trace("gn_tiles_kernel", x0.dtype)
+        _wrote(out, "groupnorm")
         return out
     if GN_SMALL and frames_per_group > 1 and nimg % frames_per_group == 0 and frames_per_group * hw <= GN_CROSS_MAX_ROWS and \
             lib.tt_groupnorm_small_supported(frames_per_group * hw, c0 + c1, _code(x0.dtype)):
@@ -456,6 +467,7 @@ def groupnorm(x0, x1, nimg, hw, frames_per_group, gamma, beta, eps, silu: bool):
                                      _code(x0.dtype), _stream()), "tt_groupnorm_small")
         if NORM_TRACE is not None:
             _norm_trace(_GN_ROUTE[lib.tt_groupnorm_route(hw, c0 + c1, _code(x0.dtype), 1, 1)], x0.dtype)
+        _wrote(out, "groupnorm")
         return out
     sc, sh = groupnorm_stats(x0, x1, nimg, hw, frames_per_group, gamma, beta, eps)
     return groupnorm_apply(x0, x1, nimg, hw, sc, sh, silu)
@@ -472,6 +484,9 @@ def layernorm(x, gamma, beta, eps=1e-5, rowvec=None, rows_per_vec=0, nvec=0):
     check(lib.tt_layernorm(_p(x), x.stride(0), rows, c, _p(gamma), _p(beta), eps, _p(rowvec), rows_per_vec, nvec, _p(xs),
                            _p(y), y.stride(0), _code(x.dtype), _stream()), "tt_layernorm")
     _norm_trace("ln_kernel", x.dtype)
+    if xs is not None:
+        _wrote(xs, "layernorm.sum")
+    _wrote(y, "layernorm")
     return (xs, y) if xs is not None else y
 
 
@@ -485,7 +500,7 @@ def add_rowvec(x, rowvec, rows_per_vec: int, nvec: int, out=None):
     assert y.shape == x.shape and y.stride(1) == 1 and y.dtype == x.dtype
     check(lib.tt_add_rowvec(_p(x), x.stride(0), rows, c, _p(rowvec), rowvec.stride(0), rows_per_vec, nvec, _p(y), y.stride(0),
                             _code(x.dtype), _stream()), "tt_add_rowvec")
-    _wrote(y)
+    _wrote(y, "add_rowvec")
     return y
 
 
@@ -508,7 +523,7 @@ def softmax_rows(x, dtype, cols: Optional[int] = None, out=None):
         raise ValueError(f"softmax_rows: output needs >= {cols_pad} columns, got {out.shape[1]}")
     check(lib.tt_softmax_rows(_p(x), x.stride(0), rows, cols, _p(out), out.stride(0), out.shape[1], _code(dtype), _stream()),
           "tt_softmax_rows")
-    _wrote(out)
+    _wrote(out, "softmax_rows")
     return out
 
 
@@ -521,7 +536,7 @@ def small_linear(x, w, bias=None, act_in=False, act_out=False, out=None, accumul
     assert x.dtype == torch.float32 and out.dtype == torch.float32
     check(lib.tt_small_linear(_p(x), x.stride(0), rows, k, _p(w), w.stride(0), n, _p(bias), int(act_in), int(act_out),
                               int(accumulate), _p(out), out.stride(0), _code(w.dtype), _stream()), "tt_small_linear")
-    _wrote(out)
+    _wrote(out, "small_linear")
     return out
 
 
@@ -530,6 +545,7 @@ def timestep_embedding(t, dim):
     assert t.dtype == torch.float32 and t.dim() == 1
     out = torch.empty((t.shape[0], dim), dtype=torch.float32, device=t.device)
     check(lib.tt_timestep_embedding(_p(t), t.shape[0], dim, _p(out), out.stride(0), _stream()), "tt_timestep_embedding")
+    _wrote(out, "timestep_embedding")
     return out
 
 
@@ -538,6 +554,7 @@ def prep_model_input(latents, image_latents, cond, sigmas, step, batch, frames, 
     x = torch.empty((batch * frames * h * w, cpad), dtype=dtype, device=latents.device)
     check(lib.tt_prep_model_input(_p(latents), _p(image_latents), _p(cond), _p(sigmas), step, batch, frames, h, w, cpad,
                                   _p(x), _code(dtype), _stream()), "tt_prep_model_input")
+    _wrote(x, "prep_model_input")
     return x
 
 
@@ -549,9 +566,11 @@ def cfg_euler_step(eps, latents, guidance, sigmas, step, batch, frames, h, w, im
             raise ValueError("a CFG batch of 3 needs guidance and image_guidance_scale")
         check(lib.tt_cfg3_euler_step(_p(eps), eps.stride(0), _p(latents), _p(guidance), float(image_guidance_scale), _p(sigmas),
                                      step, frames, h, w, _stream()), "tt_cfg3_euler_step")
+        _wrote(latents, "cfg_euler_step")
         return latents
     check(lib.tt_cfg_euler_step(_p(eps), eps.stride(0), _p(latents), _p(guidance), _p(sigmas), step, batch, frames, h, w,
                                 _stream()), "tt_cfg_euler_step")
+    _wrote(latents, "cfg_euler_step")
     return latents
 
 
@@ -568,6 +587,7 @@ def prep_model_input_requests(latents, image_latents, cond, sigmas, step, reques
     x = torch.empty((requests * cfg * frames * h * w, cpad), dtype=dtype, device=latents.device)
     check(lib.tt_prep_model_input_requests(_p(latents), _p(image_latents), _p(cond), per_request, _p(sigmas), step, requests, cfg,
                                            frames, h, w, cpad, _p(x), _code(dtype), _stream()), "tt_prep_model_input_requests")
+    _wrote(x, "prep_model_input")
     return x
 
 
@@ -586,6 +606,7 @@ def cfg_euler_step_requests(eps, latents, guidance, sigmas, step, requests, cfg,
     check(lib.tt_cfg_euler_step_requests(_p(eps), eps.stride(0), _p(latents), _p(guidance), per_request,
                                          float(image_guidance_scale) if cfg == 3 else 0.0, _p(sigmas), step, requests, cfg, frames, h, w,
                                          _stream()), "tt_cfg_euler_step_requests")
+    _wrote(latents, "cfg_euler_step")
     return latents
 
 
@@ -603,7 +624,7 @@ def nchw_to_tokens(src, dtype, ld=None, out=None):
     assert out.dtype == dtype and out.stride(1) == 1
     check(lib.tt_nchw_to_tokens(_p(src), int(src.dtype == torch.float32), n, c, h * w, _p(out), out.stride(0), _code(dtype),
                                 _stream()), "tt_nchw_to_tokens")
-    _wrote(out)
+    _wrote(out, "nchw_to_tokens")
     return out
 
 
@@ -618,6 +639,7 @@ def tokens_to_nchw(src, n, c, h, w, out_dtype):
     dst = torch.empty((n, c, h, w), dtype=out_dtype, device=src.device)
     check(lib.tt_tokens_to_nchw(_p(src), int(src_f32), src.stride(0), n, c, h * w, _p(dst), int(dst_f32), _code(tok_dtype),
                                 _stream()), "tt_tokens_to_nchw")
+    _wrote(dst, "tokens_to_nchw")
     return dst
 
 
@@ -627,7 +649,7 @@ def add_scaled(a, b, scale=1.0, out=None):
     if out is None:
         out = torch.empty_like(a)
     check(lib.tt_add_scaled(_p(a), _p(b), scale, _p(out), a.numel(), _code(a.dtype), _stream()), "tt_add_scaled")
-    _wrote(out)
+    _wrote(out, "add_scaled")
     return out
 
 
@@ -651,7 +673,7 @@ def encoder_attention(q, k, v, out, *, nseq, l, heads, head_dim, causal=False, k
     a.dtype = _code(q.dtype)
     ev = _prof_begin()
     check(lib.tt_encoder_attention(C.byref(a), _stream()), "tt_encoder_attention")
-    _wrote(out)
+    _wrote(out, "encoder_attention")
     if ev is not None:
         _prof_end(ev, f"enc_attn_kernel<{_TAG[a.dtype]}, {head_dim}, {'true' if causal else 'false'}>",
                   4.0 * nseq * heads * l * l * head_dim * (0.5 if causal else 1.0), shape=("attn", nseq * heads, l, l, int(bool(causal)), 0))
@@ -670,7 +692,7 @@ def act_rows(x, act: str = "gelu", out=None):
     y = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device) if out is None else out
     assert y.shape == x.shape and y.stride(1) == 1 and y.dtype == x.dtype
     check(lib.tt_act_rows(_p(x), x.stride(0), x.shape[0], x.shape[1], ACTS[act], _p(y), y.stride(0), _code(x.dtype), _stream()), "tt_act_rows")
-    _wrote(y)
+    _wrote(y, "act_rows")
     return y
 
 
@@ -688,7 +710,7 @@ def patch_tokens(src, patch: int, dtype, kpad=None):
     out = torch.empty((n * (h // patch) * (w // patch), kpad), dtype=dtype, device=src.device)
     check(lib.tt_patch_tokens(_p(src), int(src.dtype == torch.float32), n, c, h, w, patch, _p(out), out.stride(0), kpad, _code(dtype),
                               _stream()), "tt_patch_tokens")
-    _wrote(out)
+    _wrote(out, "patch_tokens")
     return out
 
 
@@ -716,7 +738,7 @@ def embed_rows(table, pos, *, ids=None, cls=None, l: int, out=None):
     assert out.shape == (rows, c) and out.stride(1) == 1 and out.dtype == table.dtype
     check(lib.tt_embed_rows(mode, _p(ids), _p(table), table.stride(0), table.shape[0], _p(cls), _p(pos), pos.stride(0), rows, l, c,
                             _p(out), out.stride(0), _code(table.dtype), _stream()), "tt_embed_rows")
-    _wrote(out)
+    _wrote(out, "embed_rows")
     return out
 
 
@@ -747,7 +769,7 @@ def clip_image(src, size, mean, std, dtype):
     ws = _workspace(need, src.device)
     check(lib.tt_clip_image(_p(src), kind, n, h, w, oh, ow, *[float(v) for v in mean], *[float(v) for v in std], _p(out), _code(dtype),
                             _p(ws), need, _stream()), "tt_clip_image")
-    _wrote(out)
+    _wrote(out, "clip_image")
     return out
 
 
@@ -766,7 +788,7 @@ def layernorm_block(x, rows: int, eps: float = 1e-5, out=None):
     check(lib.tt_layernorm_block(_p(x), x.stride(0), x.shape[0] // rows, rows, x.shape[1], float(eps), _p(y), _code(x.dtype), _stream()),
           "tt_layernorm_block")
     _norm_trace("ln_block_kernel", x.dtype)
-    _wrote(y)
+    _wrote(y, "layernorm_block")
     return y
 
 
@@ -783,7 +805,7 @@ def frames_out(x, kind: int):
     n, ch, h, w = x.shape
     out = torch.empty((n, h, w, ch), dtype=torch.float32 if kind == 0 else torch.uint8, device=x.device)
     check(lib.tt_frames_out(_p(x), _code(x.dtype), n, ch, h, w, kind, _p(out), _stream()), "tt_frames_out")
-    _wrote(out)
+    _wrote(out, "frames_out")
     return out
 
 
@@ -814,7 +836,7 @@ def gesture_maps(records, nmaps: int, frames: int, org_hw, out_hw, dilate: bool,
         ws = _workspace(need, out.device) if need else None
         check(lib.tt_gesture_maps(recs if n else None, n, int(nmaps), int(frames), int(org_hw[0]), int(org_hw[1]), oh, ow, int(dilate), int(flip),
                                   _p(out), _code(dtype), _p(ws), need, _stream()), "tt_gesture_maps")
-    _wrote(out)
+    _wrote(out, "gesture_maps")
     return out
 
 
@@ -890,7 +912,7 @@ def resize_u8(src, size, resample="lanczos"):
     ws = _workspace(need, src.device) if need else None
     tx, kx, ty, ky = tabs
     check(lib.tt_resize_u8(_p(src), *dims, _p(tx), kx, _p(ty), ky, _p(out), _p(ws), need, _stream()), "tt_resize_u8")
-    _wrote(out)
+    _wrote(out, "resize_u8")
     return out
 
 
@@ -917,5 +939,82 @@ def vae_image(src, size, noise, noise_aug_strength, dtype, videos_per_image: int
     tx, kx, ty, ky = tabs
     check(lib.tt_vae_image(_p(src), *dims, _p(tx), kx, _p(ty), ky, _p(noise), float(noise_aug_strength), nvid, _p(out), _code(dtype), _p(ws), need, _stream()),
           "tt_vae_image")
-    _wrote(out)
+    _wrote(out, "vae_image")
     return out
+
+
+# ---- the range audit's instrument (tt_tensor_stats; audit.py decodes the records and names the sites)
+STATS_BYTES = C.sizeof(_lib.TtTensorStats)
+# |x| >= 448: e4m3 saturates (on an e4m3 tensor: values sitting at the clip); >= 65520: rounds to inf in fp16; >= 65520 * 2^8: split16's
+# high term h = fp16(x 2^-8) overflows; the fourth is free (default 2^15: within one binade of fp16's largest value)
+STATS_THRESHOLDS = (448.0, 65520.0, 16773120.0, 32768.0)
+
+
+def _stats_code(dt: torch.dtype) -> int:
+    if dt == FP8:
+        return _lib.TT_FP8_E4M3
+    if dt in (torch.bfloat16, torch.float16, torch.float32):
+        return _code(dt)
+    raise RuntimeError(f"tensor_stats: bfloat16, float16, float32 or float8_e4m3fn, got {dt}")
+
+
+def _rows_view(x: torch.Tensor):
+    """(rows, cols, row stride) of x read as a row-strided 2-D tensor: the last dimension contiguous, the leading ones collapsing to
+    one row stride; raises for any other layout."""
+    dims = [(n, st) for n, st in zip(x.shape, x.stride()) if n != 1]
+    if x.numel() == 0:
+        return 0, 0, 0
+    if not dims:
+        return 1, 1, 1
+    cols, st = dims[-1]
+    if st != 1:
+        raise RuntimeError(f"tensor_stats: the last dimension must be contiguous (shape {tuple(x.shape)}, strides {tuple(x.stride())})")
+    lead = dims[:-1]
+    if not lead:
+        return 1, cols, cols
+    for (_, s0), (n1, s1) in zip(lead[:-1], lead[1:]):
+        if s0 != s1 * n1:
+            raise RuntimeError(f"tensor_stats: the leading dimensions must collapse to one row stride (shape {tuple(x.shape)}, strides "
+                               f"{tuple(x.stride())})")
+    rows = 1
+    for n, _ in lead:
+        rows *= n
+    ld = lead[-1][1]
+    if ld < cols:
+        raise RuntimeError(f"tensor_stats: rows overlap (shape {tuple(x.shape)}, strides {tuple(x.stride())})")
+    if cols >= 1 << 31:
+        raise RuntimeError(f"tensor_stats: {cols} columns; reshape the tensor to rows of fewer than 2^31 elements")
+    return rows, cols, ld
+
+
+def tensor_stats_launch(dtype: torch.dtype):
+    """(most workgroups of a launch, lanes per workgroup, elements per 16-byte load of `dtype`): the constants tt_tensor_stats launches with"""
+    g, b, e = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(_lib.load().tt_tensor_stats_launch(_stats_code(dtype), C.byref(g), C.byref(b), C.byref(e)), "tt_tensor_stats_launch")
+    return g.value, b.value, e.value
+
+
+def tensor_stats(x: torch.Tensor, *, thresholds=None, out: Optional[torch.Tensor] = None, slot: int = 0, accumulate: bool = False):
+    """One pass over x (bf16 / fp16 / fp32 / float8_e4m3fn; last dimension contiguous, leading dimensions collapsing to one row stride)
+    -> the TtTensorStats record (include/ttvdm.h) as a uint8 device tensor of STATS_BYTES bytes: record `slot` of ``out`` (a uint8 buffer
+    of whole records) or a new one.  thresholds: four fp32 values for n_ge (default STATS_THRESHOLDS).  accumulate: merge into the record
+    already there.  Asynchronous and capturable; ``audit.decode`` turns records into Python objects after one device-to-host copy."""
+    lib = _lib.load()
+    _p(x)
+    rows, cols, ld = _rows_view(x)
+    code = _stats_code(x.dtype)
+    thr = thresholds if isinstance(thresholds, C.Array) else (C.c_float * 4)(*(STATS_THRESHOLDS if thresholds is None else thresholds))
+    if len(thr) != 4:
+        raise RuntimeError("tensor_stats: four thresholds")
+    if out is None:
+        if accumulate:
+            raise RuntimeError("tensor_stats: accumulate needs the record to merge into (out=)")
+        out = torch.empty(STATS_BYTES, dtype=torch.uint8, device=x.device)
+        slot = 0
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != x.device or slot < 0 or (slot + 1) * STATS_BYTES > out.numel():
+        raise RuntimeError(f"tensor_stats: out must be a contiguous uint8 tensor on {x.device} holding record {slot} ({STATS_BYTES} bytes each)")
+    need = lib.tt_tensor_stats_ws_bytes(rows, cols, code)
+    ws = _workspace(need, x.device) if need else None
+    check(lib.tt_tensor_stats(x.data_ptr() if rows else None, ld, rows, cols, code, thr, out.data_ptr() + slot * STATS_BYTES, _p(ws), need,
+                              int(bool(accumulate)), _stream()), "tt_tensor_stats")
+    return out[slot * STATS_BYTES:(slot + 1) * STATS_BYTES]

@@ -45,6 +45,7 @@ class DenoiseLoop:
         self._graph_off = None              # the UNet-only step for controlnet_keep[i] == 0
         self._key = None
         self._static = {}
+        self._audit = None                  # the range audit the graphs were captured under (kept alive with them), or None
 
     # ---- request set-up (everything step-invariant)
     def begin(self, latents: torch.Tensor, image_latents: torch.Tensor, encoder_hidden_states: torch.Tensor,
@@ -96,10 +97,14 @@ class DenoiseLoop:
         packs = self._pack_state()
         key = (nr, b, f, h, w, dtype, self.controlnet is not None, tuple(encoder_hidden_states.shape), len(timesteps),
                guidance_scale is not None, self.image_guidance_scale, packs,   # the image scale is baked into the graph
-               ops.f32_split())                                                # ... and so is the TT_F32 product mode (kernel variants)
+               ops.f32_split(),                                                # ... and so is the TT_F32 product mode (kernel variants)
+               None if ops.AUDIT is None else ops.AUDIT.generation)           # ... and the range audit whose statistics launches a captured step holds
         if key != self._key:                    # new shapes or new weights: new static buffers, new graph
             self._graph, self._graph_off, self._key, self._static = None, None, key, {}
         self._packs = packs                     # what the FiLM table, the context projections and the graphs below were built from
+        # a graph captured under an audit writes into that audit's records: the loop holds the audit (and so its buffer) for as long as it
+        # holds such a graph -- the rule of ops._WS_RETIRED -- and step() refuses to run under another audit, or none, than begin() saw
+        self._audit = ops.AUDIT
         self.geom, self.dtype = Geom(b, f, h, w, requests=nr), dtype
         f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
         sig = f32(sigmas)
@@ -188,6 +193,13 @@ class DenoiseLoop:
 
     # ---- one step's launches (captured once)
     def _launch_step(self, use_cn: bool = True):
+        if ops.AUDIT is None:
+            return self._launch_step_branches(use_cn)
+        # under a range audit every step names its sites alike: the ordinals restart where the first step started them
+        with ops.AUDIT.region("step" if use_cn or self.controlnet is None else "step.unet_only"):
+            return self._launch_step_branches(use_cn)
+
+    def _launch_step_branches(self, use_cn: bool = True):
         """One step as concurrent branches (fork/join with events; captured as parallel hipGraph branches).
         GestureNet's encoder+mid is independent of the UNet's until the zero-convs, so the two run side by side: the
         latency-bound small kernels and the tails of one branch fill the idle CUs of the other (49.8 -> 44.4 ms/step).
@@ -272,6 +284,9 @@ class DenoiseLoop:
         if self._pack_state(repack=False) != self._packs:
             raise RuntimeError("model weights were re-packed (load_state_dict / .to() / in-place update) after DenoiseLoop.begin(): "
                                "call begin() again -- the per-request FiLM table and context projections belong to the old weights")
+        if ops.AUDIT is not self._audit:
+            raise RuntimeError("a range audit began or ended after DenoiseLoop.begin(): call begin() again -- a captured step holds the "
+                               "statistics launches of the audit it was captured under, or none")
         self.cur.copy_(self.table[self.step_index])
         use_cn = self.controlnet is not None and self.keep[self.step_index] != 0.0
         if self.film_cur_u is not None:
@@ -293,7 +308,8 @@ class DenoiseLoop:
     def _capture(self, use_cn: bool):
         # warm-up on a side stream (allocator + lazily built caches), restoring the latents afterwards
         keep = self.latents.clone()
-        s = torch.cuda.Stream()
+        records = None if ops.AUDIT is None else ops.AUDIT.snapshot()         # the warm-up pass below is not a step of the request: its
+        s = torch.cuda.Stream()                                                # statistics are taken back out of the audit's records
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             self._launch_step(use_cn)
@@ -302,6 +318,8 @@ class DenoiseLoop:
         with torch.cuda.graph(graph):
             self._launch_step(use_cn)
         self.latents.copy_(keep)
+        if ops.AUDIT is not None:
+            ops.AUDIT.restore(records)
         return graph
 
     def run(self, steps: Optional[int] = None) -> torch.Tensor:

@@ -41,14 +41,21 @@ class _SVDPipelineCore(PipelineBase):
     model_cpu_offload_seq = "image_encoder->unet->vae"
     _callback_tensor_inputs = ["latents"]
     native_image_io = False            # class default: also what an instance built without __init__ sees
+    range_audit = False                # True: every call runs under an audit.RangeAudit and leaves its report in last_range_audit
+    last_range_audit = None
 
-    def __init__(self, vae, image_encoder, unet, scheduler, feature_extractor, native_image_io: bool = False):
+    def __init__(self, vae, image_encoder, unet, scheduler, feature_extractor, native_image_io: bool = False, range_audit: bool = False):
         self.register_modules(vae=vae, image_encoder=image_encoder, unet=unet, scheduler=scheduler,
                               feature_extractor=feature_extractor)
         # True: PIL / numpy images reach CLIP through ops.clip_image, the use_text context LayerNorm is ops.layernorm_block and
         # "np" / "pil" frames leave through ops.frames_out (one uint8 / fp32 NHWC copy per decoded chunk).  A plain attribute:
         # it may be switched between calls.
         self.native_image_io = bool(native_image_io)
+        # True: a call runs CLIP encode, VAE encode, the denoise loop and the decode under ONE range audit (audit.py) -- every tensor the
+        # kernels write is followed by a statistics pass, frames and latents stay bit-equal -- and the report (sites of image_encoder.*,
+        # text_encoder.*, vae.*, unet.*, controlnet.*) is left in ``last_range_audit``.  A diagnostic mode; a plain attribute as well.
+        self.range_audit = bool(range_audit)
+        self.last_range_audit = None
         self.vae_scale_factor = 2 ** (len(self.vae.config.block_out_channels) - 1)
         self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, do_convert_rgb=True)
         self.control_image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, do_convert_rgb=True,
@@ -57,7 +64,7 @@ class _SVDPipelineCore(PipelineBase):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path=None, *, vae=None, image_encoder=None, unet=None, scheduler=None,
-                        feature_extractor=None, torch_dtype=None, native_image_io: bool = False, **kwargs):
+                        feature_extractor=None, torch_dtype=None, native_image_io: bool = False, range_audit: bool = False, **kwargs):
         """The reference passes vae / image_encoder / unet explicitly (test_code/inference.py:171-178) and lets diffusers
         load the remaining components from the hub folder.  Same here, from a LOCAL diffusers-format folder (no network):
           feature_extractor/preprocessor_config.json -> CLIP image processor (mean/std used by ``encode_clip``, reference :145-152)
@@ -66,7 +73,8 @@ class _SVDPipelineCore(PipelineBase):
         vae and image_encoder are third-party models (AutoencoderKLTemporalDecoder / CLIPVisionModelWithProjection) and must be
         passed in.  Without a folder the scheduler defaults to SVD's shipped EulerDiscrete configuration and the feature
         extractor to CLIP's published preprocessing constants; nothing is ever silently skipped.
-        ``native_image_io=True`` sets the pipeline attribute of that name (default False: the torch request path)."""
+        ``native_image_io=True`` sets the pipeline attribute of that name (default False: the torch request path), ``range_audit=True``
+        the attribute of that name (default False: no statistics launches)."""
         import os
         path = pretrained_model_name_or_path
         have_dir = isinstance(path, str) and os.path.isdir(path)
@@ -84,7 +92,7 @@ class _SVDPipelineCore(PipelineBase):
             cfg = os.path.join(path, "feature_extractor", "preprocessor_config.json") if have_dir else None
             feature_extractor = CLIPFeatureExtractor.from_json_file(cfg) if cfg and os.path.isfile(cfg) else CLIPFeatureExtractor()
         return cls(vae=vae, image_encoder=image_encoder, unet=unet, scheduler=scheduler, feature_extractor=feature_extractor,
-                   native_image_io=native_image_io)
+                   native_image_io=native_image_io, range_audit=range_audit)
 
     # ---- constants of a request (reference :130-254,305-337)
     def encode_clip(self, image, prompt, use_text, text_encoder, device, num_videos_per_prompt, do_classifier_free_guidance,
@@ -251,8 +259,24 @@ class _SVDPipelineCore(PipelineBase):
         return self._num_timesteps
 
     # ---- the shared generation routine
+    def _generate(self, image, condition_img, controlnet, prompt, use_text, text_encoder, *args, **kwargs):
+        """``range_audit`` off (the default): the request as it is.  On: the same request under one audit.RangeAudit whose report is left
+        in ``last_range_audit`` (also when the request raises: the report then ends where the call did)."""
+        if not getattr(self, "range_audit", False):
+            return self._generate_request(image, condition_img, controlnet, prompt, use_text, text_encoder, *args, **kwargs)
+        from .. import audit
+        with audit.RangeAudit() as a:
+            for root, model in (("image_encoder", self.image_encoder), ("text_encoder", text_encoder), ("vae", self.vae), ("unet", self.unet),
+                                ("controlnet", controlnet)):
+                if isinstance(model, torch.nn.Module):
+                    a.watch(model, root)
+            try:
+                return self._generate_request(image, condition_img, controlnet, prompt, use_text, text_encoder, *args, **kwargs)
+            finally:
+                self.last_range_audit = a.report()
+
     @torch.no_grad()
-    def _generate(self, image, condition_img, controlnet, prompt, use_text, text_encoder, height, width, num_frames,
+    def _generate_request(self, image, condition_img, controlnet, prompt, use_text, text_encoder, height, width, num_frames,
                   num_inference_steps, min_guidance_scale, max_guidance_scale, fps, motion_bucket_id, noise_aug_strength,
                   decode_chunk_size, num_videos_per_prompt, generator, latents, output_type, callback_on_step_end,
                   callback_on_step_end_tensor_inputs, return_dict, controlnet_conditioning_scale=1.0,
