@@ -146,6 +146,19 @@ template <typename Tag> __device__ __forceinline__ float round_store(float v) { 
 template <> __device__ __forceinline__ float round_store<f32_tag>(float v) { return v; }
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
+// GroupNorm statistics of one group from a = sum x and b = sum x^2 over its cnt values (fp64, uncentred): the mean and
+// 1 / sqrt(var + eps), each rounded to fp32 once, with var = E[x^2] - mean^2 clamped at zero.  Returns the conditioning guard's flag,
+// E[x^2] > ratio * var: beyond it the uncentred variance has lost its digits to the cancellation (norm.hip: GN_GUARD_RATIO) and the
+// caller recomputes the group centred.  The ONE place this arithmetic is written: every statistics route of norm.hip and
+// splitk_epilogue_gn_kernel (gemm_kernel.h; it has no centred pass and ignores the flag) call it.
+__device__ __forceinline__ bool gn_group_stat(double a, double b, double cnt, float eps, double ratio, float& mean, float& rstd) {
+  const double m = a / cnt;
+  double var = b / cnt - m * m;
+  if (var < 0.0) var = 0.0;
+  mean = (float)m;
+  rstd = (float)(1.0 / sqrt(var + (double)eps));
+  return b / cnt > ratio * var;
+}
 // exact-erf GELU with erf from Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far below fp16/bf16 output rounding):
 //   gelu(x) = x Phi(x),  Phi(x >= 0) = 1 - u,  Phi(x < 0) = u,  u = 0.5 (a1 t + .. + a5 t^5) exp(-x^2 / 2),  t = 1 / (1 + p |x| / sqrt 2)
 // written for the issue slots it costs -- the GEGLU epilogue of the persistent GEMM is VALU-bound on it (64 per lane and tile):

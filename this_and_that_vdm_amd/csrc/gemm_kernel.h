@@ -1440,7 +1440,8 @@ __global__ __launch_bounds__(256) void splitk_epilogue_stats_kernel(const GemmP 
 // block (segment of p.stat_rows rows = one image or the frames of a video, one of the 32 groups), thread (column quad of the group, row lane)
 // finishes MAXR rows -- slabs summed in order, epilogue, `out` stored --, keeps the STORED values in registers, the block adds them up
 // (fp64, fixed order: lanes by shuffle, waves through LDS), and every thread normalises what it holds.  One launch instead of the reduction
-// and a GroupNorm launch; the normalised tensor is computed from the same rounded values and the same formula as tt_groupnorm_tiles.
+// and a GroupNorm launch; the normalised tensor is computed from the same rounded values and the same formula as tt_groupnorm_tiles
+// (gn_group_stat, common.h -- without its conditioning guard: DESIGN.md 6.P).
 // Row r of the segment belongs to lane r % rl_n, slot r / rl_n; the slab loads of all MAXR slots are issued before the first is used
 // (slots beyond the segment re-read its last row and count for nothing: no branches around the loads).
 template <typename Tag, int MAXR>
@@ -1492,11 +1493,8 @@ __global__ __launch_bounds__(1024) void splitk_epilogue_gn_kernel(const GemmP p,
   if (tid == 0) {
     double a = 0.0, b = 0.0;
     for (int w = 0; w < (((int)blockDim.x + 63) >> 6); ++w) { a += wsum[w][0]; b += wsum[w][1]; }
-    const double cnt = (double)R * cpg, mean = a / cnt;
-    double var = b / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    s_stat[0] = (float)mean;
-    s_stat[1] = (float)(1.0 / sqrt(var + (double)p.gn_eps));
+    // (sums in fp64 from the first addition and no centred pass here: the guard's flag is not used, the ratio is a placeholder)
+    (void)gn_group_stat(a, b, (double)R * cpg, p.gn_eps, 0.0, s_stat[0], s_stat[1]);
   }
   __syncthreads();
   const float mean = s_stat[0], rstd = s_stat[1];

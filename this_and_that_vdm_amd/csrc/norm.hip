@@ -2,6 +2,7 @@
 // All statistics in fp32 with fp64 block/group combination (inputs reach |x| ~ 1e2 after sigma scaling); a group whose mean lies far
 // from zero against its spread is recomputed centred, in fp64 (the conditioning guard: GN_GUARD_RATIO below).
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -30,6 +31,108 @@ __host__ __device__ inline int gn_rows_per_chunk(int C) {
 // factor 16 lower (rho > 1.7): GN_GUARD_RATIO_TILES.  Below the guard nothing changes, bit for bit.
 constexpr double GN_GUARD_RATIO = 64.0, GN_GUARD_RATIO_TILES = 4.0;
 
+// ---- the pieces the GroupNorm kernels are built from (which also names the two sites that keep their own form).  The
+// arithmetic is written once, here or in gn_group_stat (common.h); the kernels differ in who owns which rows and channels and in how the
+// partial sums meet.
+
+// channel `ch` of the token-major tensor (x0 | x1): the address of its element in row `row0` of its source, and that source's row stride in bytes
+struct GnSource { const char* p; long rstride; };
+template <typename Tag>
+__device__ __forceinline__ GnSource gn_source(const char* x0, int c0, const char* x1, int c1, int ch, long row0) {
+  constexpr int ES = Elem<Tag>::ES;
+  const char* base; long ld; int coff;
+  if (ch < c0) { base = x0; ld = c0; coff = ch; } else { base = x1; ld = c1; coff = ch - c0; }
+  return {base + (row0 * ld + coff) * ES, ld * ES};
+}
+
+// a thread's fp32 sums of x and x^2 of one 8-channel vector over the rows r_begin, r_begin + step, .. < r_end, stored to psum[0..8) /
+// psq[0..8).  8 independent row loads per round (the statistics pass streams from HBM / L2), then a tail of single rows: the rows are
+// added in ascending order either way, so the unroll changes the loads in flight and nothing in the result.
+template <typename Tag>
+__device__ __forceinline__ void gn_row_sums(const char* pbase, long rstride, int r_begin, int r_end, int step, float* psum, float* psq) {
+  constexpr int INFLIGHT = 8;
+  float s[8], q[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
+  int r = r_begin;
+  for (; r + (INFLIGHT - 1) * step < r_end; r += INFLIGHT * step) {
+    float f[INFLIGHT][8];
+#pragma unroll
+    for (int k = 0; k < INFLIGHT; ++k) load8<Tag>(pbase + (long)(r + k * step) * rstride, f[k]);
+#pragma unroll
+    for (int k = 0; k < INFLIGHT; ++k) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { s[e] += f[k][e]; q[e] = fmaf(f[k][e], f[k][e], q[e]); }
+    }
+  }
+  for (; r < r_end; r += step) {
+    float f[8];
+    load8<Tag>(pbase + (long)r * rstride, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s[e] += f[e]; q[e] = fmaf(f[e], f[e], q[e]); }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { psum[e] = s[e]; psq[e] = q[e]; }
+}
+
+// group g of a block's LDS partials psum / psq [rows][ld] (its channels: g * cpg ..) is summed in fp64 by the 32 lanes sl = 0 .. 31 of a
+// half wave -- slices of its rows * cpg values --, then combined by a wave-level fixed-order tree (xor shuffles: the same association on
+// every run, bit-reproducible).  Every lane of the half wave returns the group's sums.
+__device__ __forceinline__ void gn_combine_group32(const float* psum, const float* psq, int rows, int ld, int cpg, int g, int sl, double& a, double& b) {
+  a = 0.0; b = 0.0;
+  const int n = rows * cpg;
+  for (int i = sl; i < n; i += 32) {
+    const int r = i / cpg, c = g * cpg + (i - r * cpg);
+    a += (double)psum[r * ld + c]; b += (double)psq[r * ld + c];
+  }
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+}
+
+// y = x * sc + sh with sc = rstd * gamma, sh = beta - mean * sc for the 8 channels ch .. ch + 7 of a thread; channel ch + e belongs to
+// the group (ch_in_block + e) / cpg of the block's shared statistics
+__device__ __forceinline__ void gn_affine8(const float* s_mean, const float* s_rstd, const float* gamma, const float* beta, int ch, int ch_in_block,
+                                           int cpg, float* sc, float* sh) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int gg = (ch_in_block + e) / cpg;
+    sc[e] = s_rstd[gg] * gamma[ch + e];
+    sh[e] = beta[ch + e] - s_mean[gg] * sc[e];
+  }
+}
+
+__device__ __forceinline__ void gn_apply8(float* f, const float* sc, const float* sh, int silu) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float t = fmaf(f[e], sc[e], sh[e]);
+    f[e] = silu ? silu_f(t) : t;
+  }
+}
+// ... over the rows r_begin, r_begin + step, .. < r_end of a thread's 8-channel vector: INFLIGHT rows loaded per round, then single rows
+template <typename Tag, int INFLIGHT>
+__device__ __forceinline__ void gn_apply_rows(const char* pbase, long rstride, char* ybase, long ystride, int r_begin, int r_end, int step,
+                                              const float* sc, const float* sh, int silu) {
+  int r = r_begin;
+  if constexpr (INFLIGHT > 1) {
+    for (; r + (INFLIGHT - 1) * step < r_end; r += INFLIGHT * step) {
+      float f[INFLIGHT][8];
+#pragma unroll
+      for (int k = 0; k < INFLIGHT; ++k) load8<Tag>(pbase + (long)(r + k * step) * rstride, f[k]);
+#pragma unroll
+      for (int k = 0; k < INFLIGHT; ++k) {
+        gn_apply8(f[k], sc, sh, silu);
+        store8<Tag>(ybase + (long)(r + k * step) * ystride, f[k]);
+      }
+    }
+  }
+  for (; r < r_end; r += step) {
+    float f[8];
+    load8<Tag>(pbase + (long)r * rstride, f);
+    gn_apply8(f, sc, sh, silu);
+    store8<Tag>(ybase + (long)r * ystride, f);
+  }
+}
+
 // centred statistics of channels [c_lo, c_lo + cpg) over `rows` rows from row `row0` of the token-major tensor (x0 | x1), by ALL
 // threads of the block (call under block-uniform control flow): sums of x - pivot and (x - pivot)^2 in fp64 -- thread t takes
 // one channel of the group and every (blockDim.x / cpg)-th row, lanes meet by xor shuffles, waves through red[32] in a fixed order
@@ -37,7 +140,6 @@ constexpr double GN_GUARD_RATIO = 64.0, GN_GUARD_RATIO_TILES = 4.0;
 template <typename Tag>
 __device__ __forceinline__ void gn_centred_group(const char* x0, int c0, const char* x1, int c1, long row0, int rows, int c_lo, int cpg,
                                                  float pivot, double* red, double& mean, double& var) {
-  constexpr int ES = Elem<Tag>::ES;
   const int tid = threadIdx.x, nthr = blockDim.x;
   const long n = (long)rows * cpg;
   double a = 0.0, b = 0.0;
@@ -46,10 +148,9 @@ __device__ __forceinline__ void gn_centred_group(const char* x0, int c0, const c
   const double pv = (double)pivot;
   const int rl_n = nthr / cpg, cl = tid % cpg, rl = tid / cpg;       // (cpg <= 256 <= blockDim.x)
   if (rl < rl_n) {
-    const int c = c_lo + cl;
-    const char* src; long ld;
-    if (c < c0) { src = x0 + (long)c * ES; ld = (long)c0 * ES; } else { src = x1 + (long)(c - c0) * ES; ld = (long)c1 * ES; }
-    src += row0 * ld;
+    const GnSource sx = gn_source<Tag>(x0, c0, x1, c1, c_lo + cl, 0);
+    const long ld = sx.rstride;
+    const char* src = sx.p + row0 * ld;
     int r = rl;
     for (; r + 7 * rl_n < rows; r += 8 * rl_n) {
       float v[8];
@@ -100,6 +201,8 @@ __global__ void gn_partial_kernel(const char* x0, int c0, const char* x1, int c1
   const int myv = tid % cv, myr = tid / cv;
   const int rows_per_chunk = gn_rows_per_chunk(C);
   const int r0 = chunk * rows_per_chunk, r1 = min(hw, r0 + rows_per_chunk);
+  // (this kernel keeps its own source selection and row loop, 4 loads in flight: through gn_source / gn_row_sums the fp32 instance needs
+  // 65 to 67 VGPRs instead of 64 and loses a wave -- DESIGN.md 6.P)
   if (myr < rpb) {
     float s[8], q[8];
 #pragma unroll
@@ -180,13 +283,7 @@ __global__ __launch_bounds__(1024) void gn_finalize_kernel(const double* ws, int
     double a = 0.0, b = 0.0;
 #pragma unroll
     for (int s = 0; s < GN_SLICES; ++s) { a += s_a[s][tid]; b += s_b[s][tid]; }
-    const double cnt = (double)fpg * hw * (C / GN_GROUPS);
-    const double mean = a / cnt;
-    double var = b / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    s_mean[tid] = (float)mean;
-    s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
-    s_redo[tid] = b / cnt > GN_GUARD_RATIO * var;
+    s_redo[tid] = gn_group_stat(a, b, (double)fpg * hw * (C / GN_GROUPS), eps, GN_GUARD_RATIO, s_mean[tid], s_rstd[tid]);
   }
   __syncthreads();
   const int cpg = C / GN_GROUPS;
@@ -225,58 +322,18 @@ __global__ __launch_bounds__(1024) void gn_stats_image_kernel(const char* x0, in
   float* psq = psum + rpb * C;           // [rpb][C]
   const int myv = tid % cv, myr = tid / cv;
   if (myr < rpb) {
-    float s[8], q[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
     const int ch = myv * 8;
-    const char* base; long ld; int coff;
-    if (ch < c0) { base = x0; ld = c0; coff = ch; } else { base = x1; ld = c1; coff = ch - c0; }
-    constexpr int ES = Elem<Tag>::ES;
-    const char* pbase = base + (((long)img * hw) * ld + coff) * ES;
-    const long rstride = ld * ES;
-    int r = myr;
-    for (; r + 7 * rpb < hw; r += 8 * rpb) {
-      float f[8][8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) load8<Tag>(pbase + (long)(r + k * rpb) * rstride, f[k]);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { s[e] += f[k][e]; q[e] = fmaf(f[k][e], f[k][e], q[e]); }
-      }
-    }
-    for (; r < hw; r += rpb) {
-      float f[8];
-      load8<Tag>(pbase + (long)r * rstride, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { s[e] += f[e]; q[e] = fmaf(f[e], f[e], q[e]); }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { psum[myr * C + ch + e] = s[e]; psq[myr * C + ch + e] = q[e]; }
+    const GnSource sx = gn_source<Tag>(x0, c0, x1, c1, ch, (long)img * hw);
+    gn_row_sums<Tag>(sx.p, sx.rstride, myr, hw, rpb, psum + myr * C + ch, psq + myr * C + ch);
   }
   __syncthreads();
   const int cpg = C / GN_GROUPS;
   {
-    // group g is summed by the 32 lanes tid = g*32 .. g*32+31 (slices of its rpb*cpg values), then combined by a wave-level
-    // fixed-order tree (xor shuffles: the same association on every run)
+    // group g <- the 32 lanes tid = g*32 .. g*32+31
     const int g = tid >> 5, sl = tid & 31;
-    double a = 0.0, b = 0.0;
-    const int n = rpb * cpg;
-    for (int i = sl; i < n; i += 32) {
-      const int r = i / cpg, c = g * cpg + (i - r * cpg);
-      a += (double)psum[r * C + c]; b += (double)psq[r * C + c];
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
-    if (sl == 0) {
-      const double cnt = (double)hw * cpg;
-      const double mean = a / cnt;
-      double var = b / cnt - mean * mean;
-      if (var < 0.0) var = 0.0;
-      s_mean[g] = (float)mean;
-      s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-      s_redo[g] = b / cnt > GN_GUARD_RATIO * var;
-    }
+    double a, b;
+    gn_combine_group32(psum, psq, rpb, C, cpg, g, sl, a, b);
+    if (sl == 0) s_redo[g] = gn_group_stat(a, b, (double)hw * cpg, eps, GN_GUARD_RATIO, s_mean[g], s_rstd[g]);
   }
   __syncthreads();
   gn_redo_groups<Tag>(x0, c0, x1, c1, (long)img * hw, hw, 0, cpg, GN_GROUPS, eps, s_mean, s_rstd, s_redo, s_red);
@@ -292,29 +349,13 @@ __global__ __launch_bounds__(1024) void gn_stats_image_kernel(const char* x0, in
   if (myr < rpb) {
     const int ch = myv * 8;
     float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int gg = (ch + e) / cpg;
-      sc[e] = s_rstd[gg] * gamma[ch + e];
-      sh[e] = beta[ch + e] - s_mean[gg] * sc[e];
-    }
-    const char* base; long ld; int coff;
-    if (ch < c0) { base = x0; ld = c0; coff = ch; } else { base = x1; ld = c1; coff = ch - c0; }
+    gn_affine8(s_mean, s_rstd, gamma, beta, ch, ch, cpg, sc, sh);
     constexpr int ES = Elem<Tag>::ES;
-    const char* pbase = base + (((long)img * hw) * ld + coff) * ES;
+    const GnSource sx = gn_source<Tag>(x0, c0, x1, c1, ch, (long)img * hw);
     char* ybase = y + (((long)img * hw) * ldy + ch) * ES;
     const int S = gridDim.y, part = blockIdx.y;
     const int r_lo = (int)((long)hw * part / S), r_hi = (int)((long)hw * (part + 1) / S);
-    for (int r = r_lo + myr; r < r_hi; r += rpb) {
-      float f[8];
-      load8<Tag>(pbase + (long)r * ld * ES, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float t = fmaf(f[e], sc[e], sh[e]);
-        f[e] = silu ? silu_f(t) : t;
-      }
-      store8<Tag>(ybase + (long)r * ldy * ES, f);
-    }
+    gn_apply_rows<Tag, 1>(sx.p, sx.rstride, ybase, ldy * ES, r_lo + myr, r_hi, rpb, sc, sh, silu);
   }
 }
 
@@ -327,6 +368,7 @@ __global__ void gn_apply_kernel(const char* x0, int c0, const char* x1, int c1, 
     const int ch = (int)(v - row * cv) * 8;
     const int img = (int)(row / hw);
     constexpr int ES = Elem<Tag>::ES;
+    // (per row, in this form: through gn_source the address set-up differs and the kernel measured 2 % slower at 7168 rows -- DESIGN.md 6.P)
     const char* src = ch < c0 ? x0 + (row * c0 + ch) * ES : x1 + (row * c1 + (ch - c0)) * ES;
     float f[8];
     load8<Tag>(src, f);
@@ -334,11 +376,7 @@ __global__ void gn_apply_kernel(const char* x0, int c0, const char* x1, int c1, 
     const float4 h0 = *(const float4*)(shift + (long)img * C + ch), h1 = *(const float4*)(shift + (long)img * C + ch + 4);
     const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
     const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float t = fmaf(f[e], sc[e], sh[e]);
-      f[e] = silu ? silu_f(t) : t;
-    }
+    gn_apply8(f, sc, sh, silu);
     store8<Tag>(y + (row * ldy + ch) * ES, f);
   }
 }
@@ -423,95 +461,27 @@ __global__ __launch_bounds__(512) void gn_group_kernel(const char* x0, int c0, c
   float* psq = psum + rlanes * nch;
   constexpr int ES = Elem<Tag>::ES;
   const int ch = ch_lo + myv * 8;
-  const char* base; long ld; int coff;
-  if (ch < c0) { base = x0; ld = c0; coff = ch; } else { base = x1; ld = c1; coff = ch - c0; }
-  const char* pbase = base + (((long)img * hw) * ld + coff) * ES;
-  const long rstride = ld * ES;
-  if (myr < rlanes) {
-    float s[8], q[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
-    int r = myr;
-    for (; r + 7 * rlanes < hw; r += 8 * rlanes) {
-      float f[8][8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) load8<Tag>(pbase + (long)(r + k * rlanes) * rstride, f[k]);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { s[e] += f[k][e]; q[e] = fmaf(f[k][e], f[k][e], q[e]); }
-      }
-    }
-    for (; r < hw; r += rlanes) {
-      float f[8];
-      load8<Tag>(pbase + (long)r * rstride, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { s[e] += f[e]; q[e] = fmaf(f[e], f[e], q[e]); }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { psum[myr * nch + myv * 8 + e] = s[e]; psq[myr * nch + myv * 8 + e] = q[e]; }
-  }
+  const GnSource sx = gn_source<Tag>(x0, c0, x1, c1, ch, (long)img * hw);
+  const char* pbase = sx.p;
+  const long rstride = sx.rstride;
+  if (myr < rlanes) gn_row_sums<Tag>(pbase, rstride, myr, hw, rlanes, psum + myr * nch + myv * 8, psq + myr * nch + myv * 8);
   __syncthreads();
   {
-    // group g of the slice <- 32 lanes (slices of its rlanes * cpg partial sums), combined by a fixed-order xor tree
+    // group g of the slice <- the 32 lanes tid = g*32 .. g*32+31
     const int g = tid >> 5, sl = tid & 31;
     if (g < gpb) {
-      double a = 0.0, b = 0.0;
-      const int n = rlanes * cpg;
-      for (int i = sl; i < n; i += 32) {
-        const int r = i / cpg, c = g * cpg + (i - r * cpg);
-        a += (double)psum[r * nch + c]; b += (double)psq[r * nch + c];
-      }
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
-      if (sl == 0) {
-        const double cnt = (double)hw * cpg;
-        const double mean = a / cnt;
-        double var = b / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
-        s_mean[g] = (float)mean;
-        s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-        s_redo[g] = b / cnt > GN_GUARD_RATIO * var;
-      }
+      double a, b;
+      gn_combine_group32(psum, psq, rlanes, nch, cpg, g, sl, a, b);
+      if (sl == 0) s_redo[g] = gn_group_stat(a, b, (double)hw * cpg, eps, GN_GUARD_RATIO, s_mean[g], s_rstd[g]);
     }
   }
   __syncthreads();
   gn_redo_groups<Tag>(x0, c0, x1, c1, (long)img * hw, hw, ch_lo, cpg, gpb, eps, s_mean, s_rstd, s_redo, s_red);
   if (myr < rlanes) {
     float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int gg = (myv * 8 + e) / cpg;
-      sc[e] = s_rstd[gg] * gamma[ch + e];
-      sh[e] = beta[ch + e] - s_mean[gg] * sc[e];
-    }
+    gn_affine8(s_mean, s_rstd, gamma, beta, ch, myv * 8, cpg, sc, sh);
     char* ybase = y + (((long)img * hw) * ldy + ch) * ES;
-    const long ystride = ldy * ES;
-    int r = myr;
-    for (; r + 3 * rlanes < hw; r += 4 * rlanes) {
-      float f[4][8];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) load8<Tag>(pbase + (long)(r + k * rlanes) * rstride, f[k]);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float v = fmaf(f[k][e], sc[e], sh[e]);
-          f[k][e] = silu ? silu_f(v) : v;
-        }
-        store8<Tag>(ybase + (long)(r + k * rlanes) * ystride, f[k]);
-      }
-    }
-    for (; r < hw; r += rlanes) {
-      float f[8];
-      load8<Tag>(pbase + (long)r * rstride, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float v = fmaf(f[e], sc[e], sh[e]);
-        f[e] = silu ? silu_f(v) : v;
-      }
-      store8<Tag>(ybase + (long)r * ystride, f);
-    }
+    gn_apply_rows<Tag, 4>(pbase, rstride, ybase, ldy * ES, myr, hw, rlanes, sc, sh, silu);
   }
 }
 // ---- GroupNorm from the PRODUCER's tile sums (tt_gemm stats_out; round 5): the conv / Linear launch that wrote x also left, per tile
@@ -560,12 +530,7 @@ __global__ __launch_bounds__(512) void gn_tiles_kernel(const char* x, int C, con
   if (tid < gpb) {
     double a = 0.0, b = 0.0;
     for (int c = 0; c < cpg; ++c) { a += pd[(tid * cpg + c) * 2]; b += pd[(tid * cpg + c) * 2 + 1]; }
-    const double cnt = (double)seg_rows * cpg, mean = a / cnt;
-    double var = b / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    s_mean[tid] = (float)mean;
-    s_rstd[tid] = (float)(1.0 / sqrt(var + (double)eps));
-    s_redo[tid] = b / cnt > GN_GUARD_RATIO_TILES * var;
+    s_redo[tid] = gn_group_stat(a, b, (double)seg_rows * cpg, eps, GN_GUARD_RATIO_TILES, s_mean[tid], s_rstd[tid]);
   }
   __syncthreads();
   // (every row part of the segment recomputes a guarded group over the WHOLE segment: the same numbers in each of them; one source:
@@ -576,41 +541,11 @@ __global__ __launch_bounds__(512) void gn_tiles_kernel(const char* x, int C, con
   if (myr >= rlanes) return;
   const int ch = ch_lo + myv * 8;
   float sc[8], sh[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int gg = (myv * 8 + e) / cpg;
-    sc[e] = s_rstd[gg] * gamma[ch + e];
-    sh[e] = beta[ch + e] - s_mean[gg] * sc[e];
-  }
+  gn_affine8(s_mean, s_rstd, gamma, beta, ch, myv * 8, cpg, sc, sh);
   const int per = (seg_rows + parts - 1) / parts, r_lo = part * per, r_hi = min(seg_rows, r_lo + per);
   const char* pbase = x + (((long)seg * seg_rows) * C + ch) * ES;
   char* ybase = y + (((long)seg * seg_rows) * ldy + ch) * ES;
-  const long rstride = (long)C * ES, ystride = ldy * ES;
-  int r = r_lo + myr;
-  for (; r + 3 * rlanes < r_hi; r += 4 * rlanes) {
-    float f[4][8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) load8<Tag>(pbase + (long)(r + k * rlanes) * rstride, f[k]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float v = fmaf(f[k][e], sc[e], sh[e]);
-        f[k][e] = silu ? silu_f(v) : v;
-      }
-      store8<Tag>(ybase + (long)(r + k * rlanes) * ystride, f[k]);
-    }
-  }
-  for (; r < r_hi; r += rlanes) {
-    float f[8];
-    load8<Tag>(pbase + (long)r * rstride, f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float v = fmaf(f[e], sc[e], sh[e]);
-      f[e] = silu ? silu_f(v) : v;
-    }
-    store8<Tag>(ybase + (long)r * ystride, f);
-  }
+  gn_apply_rows<Tag, 4>(pbase, (long)C * ES, ybase, ldy * ES, r_lo + myr, r_hi, rlanes, sc, sh, silu);
 }
 
 // groups per block: the smallest count whose channels fill whole 8-channel vectors, doubled towards 128-byte row slices while an
@@ -646,6 +581,22 @@ template <typename Tag> static void gn_image_opt_in() {
   static unsigned long long done = 0;
   tt_lds_opt_in((const void*)gn_stats_image_kernel<Tag>, GN_IMAGE_LDS_MAX, &done);
 }
+// ... and its row lanes: one per 8-channel vector of 1024 threads, fewer while the partials exceed that LDS, at most the image's rows
+static int gn_small_rpb(int C, int hw) {
+  const int cv = C >> 3;
+  int rpb = 1024 / cv;
+  while (rpb > 1 && (size_t)2 * rpb * C * sizeof(float) > GN_IMAGE_LDS_MAX) --rpb;
+  if (rpb > hw) rpb = hw;
+  return rpb;
+}
+
+// ---- storage types of this file's entry points: validity, element size, and the one dispatch from the run-time code to a kernel's
+// tag -- f(tag) is called with a value of bf16_tag / f16_tag / f32_tag (`dtype` has passed dtype_ok)
+static bool dtype_ok(int dtype) { return dtype == TT_BF16 || dtype == TT_F16 || dtype == TT_F32; }
+static int es(int dtype) { return dtype == TT_F32 ? 4 : 2; }
+template <typename F> static void by_dtype(int dtype, F&& f) {
+  if (dtype == TT_BF16) f(bf16_tag{}); else if (dtype == TT_F16) f(f16_tag{}); else f(f32_tag{});
+}
 
 }  // namespace
 
@@ -665,7 +616,7 @@ extern "C" int tt_groupnorm_stats(const void* x0, int32_t c0, const void* x1, in
   if (nimg <= 0 || hw <= 0 || C <= 0 || (C % GN_GROUPS) || (c0 & 7) || (c1 & 7)) TT_FAIL(TT_EINVAL, "tt_groupnorm_stats: C=%d+%d must be a multiple of 32, sources of 8", c0, c1);
   if (fpg <= 0 || nimg % fpg) TT_FAIL(TT_EINVAL, "tt_groupnorm_stats: frames_per_group %d does not divide %d images", fpg, nimg);
   if (ws_bytes < tt_groupnorm_ws_bytes(nimg, hw, C)) TT_FAIL(TT_EINVAL, "tt_groupnorm_stats: workspace too small");
-  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_groupnorm_stats: bad dtype");
+  if (!dtype_ok(dtype)) TT_FAIL(TT_EINVAL, "tt_groupnorm_stats: bad dtype");
   const int cv = C >> 3;
   if (cv > 1024) TT_FAIL(TT_EUNSUPPORTED, "tt_groupnorm_stats: C=%d too wide", C);
   const int rows_per_chunk = gn_rows_per_chunk(C);
@@ -674,57 +625,43 @@ extern "C" int tt_groupnorm_stats(const void* x0, int32_t c0, const void* x1, in
   int threads = cv * rpb; if (threads < GN_GROUPS) threads = GN_GROUPS;
   threads = (threads + 63) / 64 * 64;
   hipStream_t st = (hipStream_t)stream;
-  const int es = dtype == TT_F32 ? 4 : 2;
-  if (fpg == 1 && gn_one_block_ok(hw, C, es)) {
-    int rpb1 = 1024 / cv;
-    while (rpb1 > 1 && (size_t)2 * rpb1 * C * sizeof(float) > 96 * 1024) --rpb1;     // [rpb][C] x 2 fp32 in LDS
-    if (rpb1 > hw) rpb1 = hw;
-    const size_t lds1 = (size_t)2 * rpb1 * C * sizeof(float);
-#define TT_GN1(TAG, IDX) do { gn_image_opt_in<TAG>(); \
-      hipLaunchKernelGGL(gn_stats_image_kernel<TAG>, dim3(nimg), dim3(1024), lds1, st, (const char*)x0, c0, (const char*)x1, c1, hw, rpb1, gamma, beta, eps, scale, shift, (char*)nullptr, 0L, 0); } while (0)
-    if (dtype == TT_BF16) TT_GN1(bf16_tag, 0); else if (dtype == TT_F16) TT_GN1(f16_tag, 1); else TT_GN1(f32_tag, 2);
-#undef TT_GN1
+  if (fpg == 1 && gn_one_block_ok(hw, C, es(dtype))) {
+    const int rpb1 = gn_small_rpb(C, hw);
+    const size_t lds1 = (size_t)2 * rpb1 * C * sizeof(float);     // [rpb][C] x 2 fp32 in LDS
+    by_dtype(dtype, [&](auto tag) {
+      using Tag = decltype(tag);
+      gn_image_opt_in<Tag>();
+      hipLaunchKernelGGL(gn_stats_image_kernel<Tag>, dim3(nimg), dim3(1024), lds1, st, (const char*)x0, c0, (const char*)x1, c1, hw, rpb1, gamma, beta, eps,
+                         scale, shift, (char*)nullptr, 0L, 0);
+    });
     TT_CHECK_LAUNCH("tt_groupnorm_stats");
     return TT_OK;
   }
   const size_t lds = (size_t)2 * rpb * C * sizeof(float);
-  if (dtype == TT_BF16)
-    hipLaunchKernelGGL(gn_partial_kernel<bf16_tag>, dim3(chunks, nimg), dim3(threads), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, chunks, (double*)ws);
-  else if (dtype == TT_F16)
-    hipLaunchKernelGGL(gn_partial_kernel<f16_tag>, dim3(chunks, nimg), dim3(threads), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, chunks, (double*)ws);
-  else
-    hipLaunchKernelGGL(gn_partial_kernel<f32_tag>, dim3(chunks, nimg), dim3(threads), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, chunks, (double*)ws);
-#define TT_GNF(TAG) hipLaunchKernelGGL(gn_finalize_kernel<TAG>, dim3(nimg / fpg), dim3(32 * GN_SLICES), 0, st, (const double*)ws, chunks, hw, C, fpg, gamma, beta, eps, \
-                                       scale, shift, (const char*)x0, c0, (const char*)x1, c1)
-  if (dtype == TT_BF16) TT_GNF(bf16_tag); else if (dtype == TT_F16) TT_GNF(f16_tag); else TT_GNF(f32_tag);
-#undef TT_GNF
+  by_dtype(dtype, [&](auto tag) {
+    using Tag = decltype(tag);
+    hipLaunchKernelGGL(gn_partial_kernel<Tag>, dim3(chunks, nimg), dim3(threads), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, chunks, (double*)ws);
+    hipLaunchKernelGGL(gn_finalize_kernel<Tag>, dim3(nimg / fpg), dim3(32 * GN_SLICES), 0, st, (const double*)ws, chunks, hw, C, fpg, gamma, beta, eps,
+                       scale, shift, (const char*)x0, c0, (const char*)x1, c1);
+  });
   TT_CHECK_LAUNCH("tt_groupnorm_stats");
   return TT_OK;
 }
 
 // ---- statistics + apply in one launch for small images (see gn_stats_image_kernel)
-static int gn_small_rpb(int C, int hw) {
-  const int cv = C >> 3;
-  int rpb = 1024 / cv;
-  while (rpb > 1 && (size_t)2 * rpb * C * sizeof(float) > 96 * 1024) --rpb;
-  if (rpb > hw) rpb = hw;
-  return rpb;
-}
 extern "C" int tt_groupnorm_small_supported(int32_t hw, int32_t c, int32_t dtype) {
-  const int es = dtype == TT_F32 ? 4 : 2;
   if (hw <= 0 || c <= 0 || (c % GN_GROUPS) || (c & 7)) return 0;
-  if (gn_grouped_gpb(hw, c, es) > 0) return 1;             // one block per (image, group slice)
-  return gn_one_block_ok(hw, c, es);
+  if (gn_grouped_gpb(hw, c, es(dtype)) > 0) return 1;      // one block per (image, group slice)
+  return gn_one_block_ok(hw, c, es(dtype));
 }
 extern "C" int tt_groupnorm_route(int32_t hw, int32_t c, int32_t dtype, int32_t frames_per_group, int32_t one_launch) {
-  const int es = dtype == TT_F32 ? 4 : 2;
   if (hw <= 0 || c <= 0 || frames_per_group <= 0 || (c % GN_GROUPS) || (c & 7)) return 0;
   if (one_launch) {
     if (frames_per_group != 1) return 0;
-    if (gn_grouped_gpb(hw, c, es) > 0) return TT_GN_ROUTE_GROUPED;
-    return gn_one_block_ok(hw, c, es) ? TT_GN_ROUTE_IMAGE : 0;
+    if (gn_grouped_gpb(hw, c, es(dtype)) > 0) return TT_GN_ROUTE_GROUPED;
+    return gn_one_block_ok(hw, c, es(dtype)) ? TT_GN_ROUTE_IMAGE : 0;
   }
-  return frames_per_group == 1 && gn_one_block_ok(hw, c, es) ? TT_GN_ROUTE_IMAGE : TT_GN_ROUTE_PARTIAL;
+  return frames_per_group == 1 && gn_one_block_ok(hw, c, es(dtype)) ? TT_GN_ROUTE_IMAGE : TT_GN_ROUTE_PARTIAL;
 }
 extern "C" int tt_groupnorm_small(const void* x0, int32_t c0, const void* x1, int32_t c1, int32_t nimg, int32_t hw,
                                   const float* gamma, const float* beta, float eps, int32_t silu, void* y, int64_t ldy,
@@ -733,21 +670,20 @@ extern "C" int tt_groupnorm_small(const void* x0, int32_t c0, const void* x1, in
   if (!x0 || !gamma || !beta || !y) TT_FAIL(TT_EINVAL, "tt_groupnorm_small: null operand");
   if (c1 && !x1) TT_FAIL(TT_EINVAL, "tt_groupnorm_small: c1 without x1");
   if (nimg <= 0 || (c0 & 7) || (c1 & 7) || (ldy & 7) || ldy < C) TT_FAIL(TT_EINVAL, "tt_groupnorm_small: channel counts/stride must be multiples of 8");
-  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_groupnorm_small: bad dtype");
+  if (!dtype_ok(dtype)) TT_FAIL(TT_EINVAL, "tt_groupnorm_small: bad dtype");
   if (!tt_groupnorm_small_supported(hw, C, dtype))
     TT_FAIL(TT_EUNSUPPORTED, "tt_groupnorm_small: %d x %d per image is served by tt_groupnorm_stats + tt_groupnorm_apply", hw, C);
   hipStream_t st = (hipStream_t)stream;
-  const int es = dtype == TT_F32 ? 4 : 2;
-  if (const int gpb = gn_grouped_gpb(hw, C, es)) {
+  if (const int gpb = gn_grouped_gpb(hw, C, es(dtype))) {
     const int nslices = GN_GROUPS / gpb, nv = (gpb * (C / GN_GROUPS)) >> 3;
     int rlanes = 512 / nv;
     if (rlanes > hw) rlanes = hw;
     const size_t ldsg = (size_t)2 * rlanes * nv * 8 * sizeof(float);
     const int blocks = ((nimg + 7) / 8) * 8 * nslices;
-#define TT_GNG(TAG) hipLaunchKernelGGL(gn_group_kernel<TAG>, dim3(blocks), dim3(512), ldsg, st, (const char*)x0, c0, (const char*)x1, c1, nimg, hw, gpb, nslices, \
-                                       rlanes, gamma, beta, eps, (int)silu, (char*)y, (long)ldy)
-    if (dtype == TT_BF16) TT_GNG(bf16_tag); else if (dtype == TT_F16) TT_GNG(f16_tag); else TT_GNG(f32_tag);
-#undef TT_GNG
+    by_dtype(dtype, [&](auto tag) {
+      hipLaunchKernelGGL(gn_group_kernel<decltype(tag)>, dim3(blocks), dim3(512), ldsg, st, (const char*)x0, c0, (const char*)x1, c1, nimg, hw, gpb, nslices,
+                         rlanes, gamma, beta, eps, (int)silu, (char*)y, (long)ldy);
+    });
     TT_CHECK_LAUNCH("tt_groupnorm_small");
     return TT_OK;
   }
@@ -756,30 +692,29 @@ extern "C" int tt_groupnorm_small(const void* x0, int32_t c0, const void* x1, in
   // blocks per image: enough to put the apply phase on ~4 x 28..56 CUs without re-reading the image too often
   int parts = 4;
   if (hw < parts * rpb) parts = hw / rpb > 0 ? hw / rpb : 1;
-#define TT_GNS(TAG, IDX) do { gn_image_opt_in<TAG>(); \
-    hipLaunchKernelGGL(gn_stats_image_kernel<TAG>, dim3(nimg, parts), dim3(1024), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, rpb, \
-                       gamma, beta, eps, (float*)nullptr, (float*)nullptr, (char*)y, (long)ldy, (int)silu); } while (0)
-  if (dtype == TT_BF16) TT_GNS(bf16_tag, 0); else if (dtype == TT_F16) TT_GNS(f16_tag, 1); else TT_GNS(f32_tag, 2);
-#undef TT_GNS
+  by_dtype(dtype, [&](auto tag) {
+    using Tag = decltype(tag);
+    gn_image_opt_in<Tag>();
+    hipLaunchKernelGGL(gn_stats_image_kernel<Tag>, dim3(nimg, parts), dim3(1024), lds, st, (const char*)x0, c0, (const char*)x1, c1, hw, rpb,
+                       gamma, beta, eps, (float*)nullptr, (float*)nullptr, (char*)y, (long)ldy, (int)silu);
+  });
   TT_CHECK_LAUNCH("tt_groupnorm_small");
   return TT_OK;
 }
 
 extern "C" int tt_groupnorm_tiles_supported(int32_t seg_rows, int32_t c, int32_t stat_rows, int32_t dtype) {
-  const int es = dtype == TT_F32 ? 4 : 2;
   if (seg_rows <= 0 || c <= 0 || stat_rows <= 0 || (c % GN_GROUPS) || (c & 7) || seg_rows % stat_rows) return 0;
-  return gn_group_gpb(c, es) > 0 ? 1 : 0;
+  return gn_group_gpb(c, es(dtype)) > 0 ? 1 : 0;
 }
 extern "C" int tt_groupnorm_tiles(const void* x, int32_t c, const float* stats, int32_t stat_rows, int32_t nseg, int32_t seg_rows,
                                   const float* gamma, const float* beta, float eps, int32_t silu, void* y, int64_t ldy, int32_t dtype,
                                   tt_stream_t stream) {
   if (!x || !stats || !gamma || !beta || !y) TT_FAIL(TT_EINVAL, "tt_groupnorm_tiles: null operand");
   if (nseg <= 0 || (ldy & 7) || ldy < c) TT_FAIL(TT_EINVAL, "tt_groupnorm_tiles: segments / output stride");
-  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_groupnorm_tiles: bad dtype");
+  if (!dtype_ok(dtype)) TT_FAIL(TT_EINVAL, "tt_groupnorm_tiles: bad dtype");
   if (!tt_groupnorm_tiles_supported(seg_rows, c, stat_rows, dtype))
     TT_FAIL(TT_EUNSUPPORTED, "tt_groupnorm_tiles: %d rows per segment must be a multiple of the %d statistics rows, C = %d a multiple of 32", seg_rows, stat_rows, c);
-  const int es = dtype == TT_F32 ? 4 : 2;
-  const int gpb = gn_group_gpb(c, es), nslices = GN_GROUPS / gpb, nch = gpb * (c / GN_GROUPS), nv = nch >> 3;
+  const int gpb = gn_group_gpb(c, es(dtype)), nslices = GN_GROUPS / gpb, nch = gpb * (c / GN_GROUPS), nv = nch >> 3;
   // row parts per segment: ~2 blocks per CU over the launch, at least 128 rows each
   int parts = (512 + nseg * nslices - 1) / (nseg * nslices);
   if (parts > seg_rows / 128) parts = seg_rows / 128;
@@ -790,10 +725,10 @@ extern "C" int tt_groupnorm_tiles(const void* x, int32_t c, const float* stats, 
   const int nunits = nseg * parts, blocks = ((nunits + 7) / 8) * 8 * nslices;
   const size_t lds = (size_t)(512 / nch) * nch * 2 * sizeof(double);
   hipStream_t st = (hipStream_t)stream;
-#define TT_GNT(TAG) hipLaunchKernelGGL(gn_tiles_kernel<TAG>, dim3(blocks), dim3(512), lds, st, (const char*)x, (int)c, stats, (int)stat_rows, (int)seg_rows, \
-                                       nunits, parts, gpb, nslices, rlanes, gamma, beta, eps, (int)silu, (char*)y, (long)ldy)
-  if (dtype == TT_BF16) TT_GNT(bf16_tag); else if (dtype == TT_F16) TT_GNT(f16_tag); else TT_GNT(f32_tag);
-#undef TT_GNT
+  by_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL(gn_tiles_kernel<decltype(tag)>, dim3(blocks), dim3(512), lds, st, (const char*)x, (int)c, stats, (int)stat_rows, (int)seg_rows,
+                       nunits, parts, gpb, nslices, rlanes, gamma, beta, eps, (int)silu, (char*)y, (long)ldy);
+  });
   TT_CHECK_LAUNCH("tt_groupnorm_tiles");
   return TT_OK;
 }
@@ -805,16 +740,14 @@ extern "C" int tt_groupnorm_apply(const void* x0, int32_t c0, const void* x1, in
   if (!x0 || !scale || !shift || !y) TT_FAIL(TT_EINVAL, "tt_groupnorm_apply: null operand");
   if (c1 && !x1) TT_FAIL(TT_EINVAL, "tt_groupnorm_apply: c1 without x1");
   if ((c0 & 7) || (c1 & 7) || (ldy & 7) || ldy < C) TT_FAIL(TT_EINVAL, "tt_groupnorm_apply: channel counts/stride must be multiples of 8");
-  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_groupnorm_apply: bad dtype");
+  if (!dtype_ok(dtype)) TT_FAIL(TT_EINVAL, "tt_groupnorm_apply: bad dtype");
   const long total = (long)nimg * hw * (C >> 3);
   long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TT_BF16)
-    hipLaunchKernelGGL(gn_apply_kernel<bf16_tag>, dim3((unsigned)blocks), dim3(256), 0, st, (const char*)x0, c0, (const char*)x1, c1, hw, total, scale, shift, silu, (char*)y, (long)ldy);
-  else if (dtype == TT_F16)
-    hipLaunchKernelGGL(gn_apply_kernel<f16_tag>, dim3((unsigned)blocks), dim3(256), 0, st, (const char*)x0, c0, (const char*)x1, c1, hw, total, scale, shift, silu, (char*)y, (long)ldy);
-  else
-    hipLaunchKernelGGL(gn_apply_kernel<f32_tag>, dim3((unsigned)blocks), dim3(256), 0, st, (const char*)x0, c0, (const char*)x1, c1, hw, total, scale, shift, silu, (char*)y, (long)ldy);
+  by_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL(gn_apply_kernel<decltype(tag)>, dim3((unsigned)blocks), dim3(256), 0, st, (const char*)x0, c0, (const char*)x1, c1, hw, total, scale, shift,
+                       silu, (char*)y, (long)ldy);
+  });
   TT_CHECK_LAUNCH("tt_groupnorm_apply");
   return TT_OK;
 }
@@ -826,15 +759,18 @@ extern "C" int tt_layernorm(const void* x, int64_t ldx, int32_t rows, int32_t c,
   if (rows <= 0 || c <= 0 || (c & 7) || (ldx & 7) || (ldy & 7)) TT_FAIL(TT_EINVAL, "tt_layernorm: c and strides must be multiples of 8");
   if (rowvec && (!xsum_out || rows_per_vec <= 0 || nvec <= 0)) TT_FAIL(TT_EINVAL, "tt_layernorm: rowvec needs xsum_out, rows_per_vec, nvec");
   if (c > 64 * 8 * 4) TT_FAIL(TT_EUNSUPPORTED, "tt_layernorm: c=%d > 2048", c);
-  if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_layernorm: bad dtype");
+  if (!dtype_ok(dtype)) TT_FAIL(TT_EINVAL, "tt_layernorm: bad dtype");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((rows + 3) / 4), block(256);
-#define TT_LN(TAG, MV) hipLaunchKernelGGL((ln_kernel<TAG, MV>), grid, block, 0, st, (const char*)x, (long)ldx, rows, c, gamma, beta, eps, rowvec, rows_per_vec, nvec, (char*)xsum_out, (char*)y, (long)ldy)
   const int mv = (c / 8 + 63) / 64;
-  if (dtype == TT_BF16) { if (mv <= 1) TT_LN(bf16_tag, 1); else if (mv <= 2) TT_LN(bf16_tag, 2); else TT_LN(bf16_tag, 4); }
-  else if (dtype == TT_F16) { if (mv <= 1) TT_LN(f16_tag, 1); else if (mv <= 2) TT_LN(f16_tag, 2); else TT_LN(f16_tag, 4); }
-  else { if (mv <= 1) TT_LN(f32_tag, 1); else if (mv <= 2) TT_LN(f32_tag, 2); else TT_LN(f32_tag, 4); }
-#undef TT_LN
+  by_dtype(dtype, [&](auto tag) {
+    using Tag = decltype(tag);
+    auto launch = [&](auto maxv) {
+      hipLaunchKernelGGL((ln_kernel<Tag, decltype(maxv)::value>), grid, block, 0, st, (const char*)x, (long)ldx, rows, c, gamma, beta, eps, rowvec, rows_per_vec,
+                         nvec, (char*)xsum_out, (char*)y, (long)ldy);
+    };
+    if (mv <= 1) launch(std::integral_constant<int, 1>{}); else if (mv <= 2) launch(std::integral_constant<int, 2>{}); else launch(std::integral_constant<int, 4>{});
+  });
   TT_CHECK_LAUNCH("tt_layernorm");
   return TT_OK;
 }

@@ -23,7 +23,8 @@ def main():
             old = graph_time(lambda: ops.groupnorm(x, None, nimg, hw, fpg, g, b, 1e-5, True))
             line = f"hw {hw:5d} C {c:4d} {'per image ' if fpg == 1 else 'cross-frame'}: statistics pass {old:6.1f} us"
             if sb is not None and lib.tt_groupnorm_tiles_supported(seg, c, r, ops._code(dt)):
-                x._tt_stats = (sb, r)
+                # (sums, tile rows) and the hand-off record groupnorm() validates: x as it was last written
+                x._tt_stats = (sb, r, ops._LAST_WRITE.get(x.untyped_storage().data_ptr()), x.data_ptr(), tuple(x.shape))
                 new = graph_time(lambda: ops.groupnorm(x, None, nimg, hw, fpg, g, b, 1e-5, True))
                 del x._tt_stats
                 line += f" | from tile sums {new:6.1f} us ({rows * c * 4 / new / 1e6:5.2f} TB/s in+out)"
