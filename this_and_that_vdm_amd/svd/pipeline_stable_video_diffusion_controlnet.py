@@ -226,13 +226,14 @@ class _SVDPipelineCore(PipelineBase):
         if height % 8 != 0 or width % 8 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
 
-    def prepare_latents(self, batch_size, num_frames, num_channels_latents, height, width, dtype, device, generator, latents=None):
+    def prepare_latents(self, batch_size, num_frames, num_channels_latents, height, width, dtype, device, generator, latents=None,
+                        scheduler=None):
         shape = (batch_size, num_frames, num_channels_latents // 2, height // self.vae_scale_factor, width // self.vae_scale_factor)
         if isinstance(generator, list) and len(generator) != batch_size:
             raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective "
                              f"batch size of {batch_size}. Make sure the batch size matches the length of the generators.")
         latents = randn_tensor(shape, generator=generator, device=device, dtype=dtype) if latents is None else latents.to(device)
-        return latents * self.scheduler.init_noise_sigma
+        return latents * (self.scheduler if scheduler is None else scheduler).init_noise_sigma
 
     def prepare_condition_image(self, condition_img, device):
         """[0,1] float gesture frames [F,3,H,W] -> fp16 on device (reference :363-364, quirk Q7).  A list of such arrays, or one
@@ -282,10 +283,64 @@ class _SVDPipelineCore(PipelineBase):
                   callback_on_step_end_tensor_inputs, return_dict, controlnet_conditioning_scale=1.0,
                   control_guidance_start=0.0, control_guidance_end=1.0, use_instructpix2pix=False, image_guidance_scale=7.5,
                   guess_mode=False):
+        rq = self._request_setup(image, condition_img, controlnet, prompt, use_text, text_encoder, height, width, num_frames,
+                                 num_inference_steps, min_guidance_scale, max_guidance_scale, fps, motion_bucket_id, noise_aug_strength,
+                                 num_videos_per_prompt, generator, latents, use_instructpix2pix, self.scheduler)
+        num_frames, do_cfg, ip2p, ehs, latents, timesteps = rq.num_frames, rq.do_cfg, rq.ip2p, rq.ehs, rq.latents, rq.timesteps
+        decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else num_frames
+        self._guidance_scale = rq.guidance
+        self._num_timesteps = len(timesteps)
+        scale = controlnet_conditioning_scale[0] if isinstance(controlnet_conditioning_scale, list) else controlnet_conditioning_scale
+
+        # which steps keep the ControlNet (reference :611-617): 0.0 outside [start, end], else 1.0
+        n = len(timesteps)
+        keep = [1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end) for i in range(n)]
+
+        key = controlnet is not None
+        loop = self._loops.get(key)
+        if loop is None or loop.controlnet is not controlnet or loop.unet is not self.unet:
+            loop = self._loops[key] = DenoiseLoop(self.unet, controlnet, use_graph=True)
+        loop.begin(latents=latents, image_latents=rq.image_latents, encoder_hidden_states=ehs, added_time_ids=rq.added_time_ids,
+                   guidance_scale=rq.guidance if do_cfg else None, sigmas=self.scheduler.sigmas, timesteps=timesteps,
+                   controlnet_cond=rq.gesture_latents, conditioning_scale=float(scale),
+                   controlnet_keep=keep if controlnet is not None else None,
+                   image_guidance_scale=float(image_guidance_scale) if ip2p else None,
+                   guess_mode=bool(guess_mode) and controlnet is not None)
+        with self.progress_bar(total=num_inference_steps) as bar:
+            for i, t in enumerate(timesteps):
+                loop.step()
+                if callback_on_step_end is not None:
+                    cur = loop.result().to(latents.dtype)
+                    outs = callback_on_step_end(self, i, t, {k: cur for k in callback_on_step_end_tensor_inputs if k == "latents"})
+                    new = (outs or {}).pop("latents", None)
+                    if new is not None and new is not cur:
+                        loop.latents.copy_(new.reshape(loop.latents.shape))
+                bar.update()
+        frames = self._request_finish(loop.result().to(ehs.dtype), num_frames, decode_chunk_size, output_type)
+        self.maybe_free_model_hooks()
+        if not return_dict:
+            return frames
+        return StableVideoDiffusionPipelineOutput(frames=frames)
+
+    def _request_finish(self, latents, num_frames, decode_chunk_size, output_type):
+        """final latents [R,F,4,h,w] -> what the caller receives: decode + frame export, or the latents themselves (output_type "latent")"""
+        if self.native_image_io and output_type in ("np", "pil"):
+            return self._frames_native(latents.to(self.vae.dtype), num_frames, decode_chunk_size, output_type)
+        if output_type != "latent":
+            return tensor2vid(self.decode_latents(latents.to(self.vae.dtype), num_frames, decode_chunk_size),
+                              self.image_processor, output_type=output_type)
+        return latents
+
+    def _request_setup(self, image, condition_img, controlnet, prompt, use_text, text_encoder, height, width, num_frames,
+                       num_inference_steps, min_guidance_scale, max_guidance_scale, fps, motion_bucket_id, noise_aug_strength,
+                       num_videos_per_prompt, generator, latents, use_instructpix2pix, scheduler):
+        """Everything step-invariant of a call's requests (reference :520-605): CLIP context, VAE image latents, gesture latents, time
+        ids, the schedule of ``scheduler`` (set here), initial latents, the guidance ramp.  Shared by __call__ (the pipeline's
+        scheduler) and by callers that serve a request on a scheduler instance of its own."""
+        from types import SimpleNamespace
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         num_frames = num_frames if num_frames is not None else self.unet.config.num_frames
-        decode_chunk_size = decode_chunk_size if decode_chunk_size is not None else num_frames
         self.check_inputs(image, height, width)
         batch_size = 1 if isinstance(image, PIL.Image.Image) else (len(image) if isinstance(image, list) else image.shape[0])
         nvid = 1 if num_videos_per_prompt is None else int(num_videos_per_prompt)
@@ -350,52 +405,15 @@ class _SVDPipelineCore(PipelineBase):
             gesture_latents = self._encode_gesture_maps(cond, nvid)
         added_time_ids = self._get_add_time_ids(fps, motion_bucket_id, noise_aug_strength, ehs.dtype, batch_size,
                                                 nvid, do_cfg, use_instructpix2pix=ip2p).to(device)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        timesteps = self.scheduler.timesteps
+        scheduler.set_timesteps(num_inference_steps, device=device)
+        timesteps = scheduler.timesteps
         latents = self.prepare_latents(nreq, num_frames, self.unet.config.in_channels, height,
-                                       width, ehs.dtype, device, generator, latents)
+                                       width, ehs.dtype, device, generator, latents, scheduler=scheduler)
         guidance = torch.linspace(min_guidance_scale, max_guidance_scale, num_frames).unsqueeze(0).to(device, latents.dtype)
         guidance = append_dims(guidance.repeat(nreq, 1), latents.ndim)
-        self._guidance_scale = guidance
-        self._num_timesteps = len(timesteps)
-        scale = controlnet_conditioning_scale[0] if isinstance(controlnet_conditioning_scale, list) else controlnet_conditioning_scale
-
-        # which steps keep the ControlNet (reference :611-617): 0.0 outside [start, end], else 1.0
-        n = len(timesteps)
-        keep = [1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end) for i in range(n)]
-
-        key = controlnet is not None
-        loop = self._loops.get(key)
-        if loop is None or loop.controlnet is not controlnet or loop.unet is not self.unet:
-            loop = self._loops[key] = DenoiseLoop(self.unet, controlnet, use_graph=True)
-        loop.begin(latents=latents, image_latents=image_latents, encoder_hidden_states=ehs, added_time_ids=added_time_ids,
-                   guidance_scale=guidance if do_cfg else None, sigmas=self.scheduler.sigmas, timesteps=timesteps,
-                   controlnet_cond=gesture_latents, conditioning_scale=float(scale),
-                   controlnet_keep=keep if controlnet is not None else None,
-                   image_guidance_scale=float(image_guidance_scale) if ip2p else None,
-                   guess_mode=bool(guess_mode) and controlnet is not None)
-        with self.progress_bar(total=num_inference_steps) as bar:
-            for i, t in enumerate(timesteps):
-                loop.step()
-                if callback_on_step_end is not None:
-                    cur = loop.result().to(latents.dtype)
-                    outs = callback_on_step_end(self, i, t, {k: cur for k in callback_on_step_end_tensor_inputs if k == "latents"})
-                    new = (outs or {}).pop("latents", None)
-                    if new is not None and new is not cur:
-                        loop.latents.copy_(new.reshape(loop.latents.shape))
-                bar.update()
-        latents = loop.result().to(ehs.dtype)
-        if self.native_image_io and output_type in ("np", "pil"):
-            frames = self._frames_native(latents.to(self.vae.dtype), num_frames, decode_chunk_size, output_type)
-        elif output_type != "latent":
-            frames = tensor2vid(self.decode_latents(latents.to(self.vae.dtype), num_frames, decode_chunk_size),
-                                self.image_processor, output_type=output_type)
-        else:
-            frames = latents
-        self.maybe_free_model_hooks()
-        if not return_dict:
-            return frames
-        return StableVideoDiffusionPipelineOutput(frames=frames)
+        return SimpleNamespace(nreq=nreq, num_frames=num_frames, height=height, width=width, do_cfg=do_cfg, ip2p=ip2p, ehs=ehs,
+                               image_latents=image_latents, gesture_latents=gesture_latents, added_time_ids=added_time_ids,
+                               timesteps=timesteps, sigmas=scheduler.sigmas, latents=latents, guidance=guidance)
 
 
 class StableVideoDiffusionControlNetPipeline(_SVDPipelineCore):
