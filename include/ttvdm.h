@@ -173,9 +173,22 @@ int32_t tt_gemm_gn_fused(const TtGemmArgs* args);
  * call with ws / ws_bytes set as for tt_gemm (the plan depends on them). */
 int32_t tt_gemm_stats_rows(const TtGemmArgs* args);
 /* which tile configuration tt_gemm will use for this problem: cfg[0..6] = BM, BN, BK, ring stages, waves along M,
- * waves along N, split-K factor.  Lets a profiler name the kernel instance
- * (gemm_kernel<dtype, BM, BN, BK, stages, wavesM, wavesN, mode>) a launch maps to.  Host-only, no launch. */
+ * waves along N, split-K factor (stages = 0: not the tiled template).  Host-only, no launch. */
 int tt_gemm_plan(const TtGemmArgs* args, int32_t cfg[7]);
+/* The kernel instance tt_gemm launches for this problem (additive entry points, like tt_conv3x3_kernel and tt_attention_kernel below; the
+ * ABI version is unchanged): its name is written to name[0..cap), NUL-terminated.  The name is the kernel's demangled symbol without return
+ * type, parameter list and namespace qualifiers, EVERY template argument written out -- the form a kernel trace prints:
+ *   gemm_kernel<bf16_tag, 128, 128, 64, 2, 4, 2, 0>    the tiled template: tag, the tile (cfg[0..5] of tt_gemm_plan) and the variant --
+ *                                                      0..5 (gather modes 0 / 1 / 2, LayerNorm folded over the rows of A / of W, mode 3)
+ *                                                      + 8 split16 + 16 / + 32 pre-split W / A + 64 the wide route
+ *   gemm_pp_kernel<f16_tag, 1, 0>                      the persistent kernel: tag, LayerNorm fold, GEGLU
+ *   gemm_w320_kernel / gemm_w320h_kernel<tag, 0, 1>    the big-tile kernels: tag, gather mode, LayerNorm fold
+ *   sq320_kernel<bf16_tag, true, true>                 the streaming kernel: tag, residual, row vector
+ * It comes from the selector the launch itself dispatches on, so it names what runs.  A problem launched in two parts (persistent kernel +
+ * tail) gives the head's kernel, as tt_gemm_plan gives the head's tile; a split-K plan gives the main kernel, not the reduction pass.
+ * Host-only, no launch, no device: set ws / ws_bytes as for tt_gemm (the plan depends on them).  Returns what tt_gemm_plan returns for a
+ * problem it refuses, and TT_EINVAL when the name does not fit `cap` bytes (64 hold every name). */
+int tt_gemm_kernel(const TtGemmArgs* args, char* name, int32_t cap);
 /* bytes of fp32 scratch tt_gemm would like for this problem (0 = no split-K planned).  Problems with few output
  * tiles and a long K (convs at the coarsest UNet levels) are split over K; the slabs are summed in a fixed order,
  * so results stay bit-reproducible.  Without (enough) workspace the un-split plan runs instead. */
@@ -210,6 +223,8 @@ int tt_gemm_set_big_tile(int32_t on);
  *      tt_attention on fp32 storage (head_dim 64) follows the same switch; few-tile long-K problems take a split-K plan in this mode
  *      (fp32 slabs in the tt_gemm_ws_bytes workspace, summed in a fixed order). */
 int tt_gemm_set_f32_split(int32_t on);
+/* the mode in force: 0 or 1, from TT_F32_SPLIT (any value atoi reads as non-zero) or the last tt_gemm_set_f32_split.  Host-only (additive). */
+int32_t tt_gemm_get_f32_split(void);
 /* The wide route (see "Operand sizes" above; additive entry points, the ABI version is unchanged).
  * tt_gemm_is_wide: 1 if tt_gemm would run `args` on the wide route, else 0 (also for problems it refuses).  Host-only. */
 int32_t tt_gemm_is_wide(const TtGemmArgs* args);
@@ -245,6 +260,9 @@ typedef struct TtConvArgs {
 } TtConvArgs;
 int tt_conv3x3_supported(int32_t h, int32_t w, int32_t c0, int32_t c1, int32_t n, int32_t dtype);
 int tt_conv3x3(const TtConvArgs* args, tt_stream_t stream);
+/* the instance tt_conv3x3 launches, conv_patch_kernel<tag, TH, TW, BN> (pixel tile, output columns per block), in the form and with the
+ * return codes of tt_gemm_kernel: what tt_conv3x3 itself returns for arguments it refuses (the operand pointers are checked, not read). */
+int tt_conv3x3_kernel(const TtConvArgs* args, char* name, int32_t cap);
 
 /* ------------------------------------------------------------------------------------------------
  * tt_attention: softmax(Q K^T / sqrt(d)) V with online softmax on MFMA tiles; replaces
@@ -295,6 +313,10 @@ typedef struct TtAttnArgs {
   int32_t v_rows;
 } TtAttnArgs;
 int tt_attention(const TtAttnArgs* args, tt_stream_t stream);
+/* the instance tt_attention launches, in the form and with the return codes of tt_gemm_kernel (tt_attention's own for arguments it refuses;
+ * the operand pointers are checked, not read): attn_kernel<tag, head_dim, mask, fused query projection, v_rows, split16>,
+ * attn_pipe_kernel<tag> (v_rows with two or more whole tiles of 64 keys) or attn8_kernel<tag, head_dim> (fp8). */
+int tt_attention_kernel(const TtAttnArgs* args, char* name, int32_t cap);
 
 /* temporal self-attention over the frame axis (seq = frames <= 32), one 16/32-lane group per
  * (batch, pixel, head); replaces TemporalBasicTransformerBlock.attn1 incl. its two

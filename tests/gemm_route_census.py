@@ -231,9 +231,9 @@ def sha_of(rows):
     return hashlib.sha256(json.dumps([[s[0], s[1], p, w] for s, p, w in rows], sort_keys=True).encode()).hexdigest()
 
 
-def take(lib):
-    rows = rows_of()
-    table, index, state = {}, [], None
+def walk(lib, rows):
+    """The TtGemmArgs of every row, in order, with the row's knob state in force while the caller looks at it."""
+    state = None
     for st, p, with_ws in rows:
         if st is not state:
             if state is not None and state[1] is not None:
@@ -245,10 +245,17 @@ def take(lib):
         if with_ws:                                   # exactly the workspace tt_gemm_ws_bytes asks for
             need = lib.tt_gemm_ws_bytes(C.byref(g))
             g.ws, g.ws_bytes = (PTR["ws"], need) if need else (None, 0)
-        a = tuple(answers(lib, g))
-        index.append(table.setdefault(a, len(table)))
+        yield g
     if state[1] is not None:
         getattr(lib, state[0])(state[2])
+
+
+def take(lib, answers=answers):
+    rows = rows_of()
+    table, index = {}, []
+    for g in walk(lib, rows):
+        a = tuple(answers(lib, g))
+        index.append(table.setdefault(a, len(table)))
     return dict(sha=sha_of(rows), answers=[list(a) for a in table], rows=index)
 
 

@@ -107,6 +107,11 @@ SIGNATURES = {
     # the wide route for operands of 2 GiB and more (additive; the ABI version is unchanged)
     "tt_gemm_is_wide": (C.c_int32, [C.POINTER(TtGemmArgs)]),
     "tt_gemm_set_wide": (C.c_int, [C.c_int32]),
+    # the kernel instance a launch runs, by name, and the split16 mode in force (host-only, additive; the ABI version is unchanged)
+    "tt_gemm_kernel": (C.c_int, [C.POINTER(TtGemmArgs), C.c_char_p, _i32]),
+    "tt_conv3x3_kernel": (C.c_int, [C.POINTER(TtConvArgs), C.c_char_p, _i32]),
+    "tt_attention_kernel": (C.c_int, [C.POINTER(TtAttnArgs), C.c_char_p, _i32]),
+    "tt_gemm_get_f32_split": (C.c_int32, []),
     "tt_attention": (C.c_int, [C.POINTER(TtAttnArgs), _vp]),
     "tt_conv3x3_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "tt_conv3x3": (C.c_int, [C.POINTER(TtConvArgs), _vp]),

@@ -1406,6 +1406,21 @@ AttnRoute resolve_attention(const TtAttnArgs& a) {
   if (a.dtype == TT_F32 && a.head_dim == 64 && tt_internal_f32_split()) return AttnRoute::SPLIT16;
   return AttnRoute::PLAIN;
 }
+// The kernel instance of a problem: launch_attention switches on it and tt_attention_kernel prints it.  d, mask: the template arguments
+// as the route's instances take them (QPROJ is built for masks 1 / 2, VROWS for mask 0).
+struct AttnInst { AttnRoute route; int d, mask; };
+AttnInst attn_inst(const TtAttnArgs& a) {
+  const AttnRoute route = resolve_attention(a);
+  return AttnInst{route, a.head_dim, route == AttnRoute::QPROJ ? (a.mask == 1 ? 1 : 2) : (route == AttnRoute::VROWS ? 0 : a.mask)};
+}
+int attn_inst_name(const AttnInst& i, int dtype, char* name, int32_t cap) {
+  const char* who = "tt_attention_kernel", *tag = tt_tag_name(dtype);
+  if (i.route == AttnRoute::FP8) return tt_put_name(who, name, cap, "attn8_kernel<%s, %d>", tag, i.d);
+  if (i.route == AttnRoute::PIPE) return tt_put_name(who, name, cap, "attn_pipe_kernel<%s>", tag);
+  const auto tf = [](bool b) { return b ? "true" : "false"; };
+  return tt_put_name(who, name, cap, "attn_kernel<%s, %d, %d, %s, %s, %s>", tag, i.d, i.mask, tf(i.route == AttnRoute::QPROJ),
+                     tf(i.route == AttnRoute::VROWS), tf(i.route == AttnRoute::SPLIT16));
+}
 struct TattnRoute { bool mfma; int lpu; };                   // tattn_mfma_kernel or tattn_kernel<.., LPU lanes per unit>
 TattnRoute resolve_temporal(int dtype, int head_dim, int frames) {
   // (one 16 x 16 MFMA tile of keys x queries per unit: tattn_mfma_kernel's own precondition)
@@ -1434,7 +1449,7 @@ void for_mask(int mask, F&& f) {
 
 // false: the route has no instance for this tag / head dimension (validation keeps such problems out)
 template <typename Tag, int D>
-bool launch_attention(AttnRoute route, const AttnP& p, hipStream_t st) {
+bool launch_attention(const AttnInst& inst, const AttnP& p, hipStream_t st) {
   constexpr int ES = Elem<Tag>::ES;
   constexpr bool H64 = D == 64 && ES == 2;                   // QPROJ, PIPE, VROWS: head dimension 64, 16-bit storage
   constexpr size_t ring = 2 * (KB * D * ES + D * KB * ES);   // the K / V^T ring; it doubles as the output strips
@@ -1442,7 +1457,7 @@ bool launch_attention(AttnRoute route, const AttnP& p, hipStream_t st) {
   // mask 2: one block per (query residue class, QB queries of that class)
   const int cls = p.mask == 2 ? p.ctx_batches : 1;
   const dim3 grid(cls * ((((p.lq + cls - 1) / cls) + QB - 1) / QB), p.heads, p.nseq), block(256);
-  switch (route) {
+  switch (inst.route) {
     case AttnRoute::FP8:
       if constexpr (ES == 2) {
         // the K/V ring (2 x 2 x 64 x D bytes) doubles as the 4 x 32 x D*ES-byte output strips
@@ -1454,7 +1469,7 @@ bool launch_attention(AttnRoute route, const AttnP& p, hipStream_t st) {
     case AttnRoute::QPROJ:
       if constexpr (H64) {
         constexpr size_t lds = 3 * (QB * 128 + 64 * 128);    // the 3 x 24 KiB projection ring (the K / V^T ring reuses it)
-        if (p.mask == 1) launch<attn_kernel<Tag, 64, 1, true>>(grid, block, lds, st, p);
+        if (inst.mask == 1) launch<attn_kernel<Tag, 64, 1, true>>(grid, block, lds, st, p);
         else launch<attn_kernel<Tag, 64, 2, true>>(grid, block, lds, st, p);
         return true;
       }
@@ -1467,12 +1482,12 @@ bool launch_attention(AttnRoute route, const AttnP& p, hipStream_t st) {
       break;
     case AttnRoute::SPLIT16:
       if constexpr (ES == 4 && D == 64) {
-        for_mask(p.mask, [&](auto m) { launch<attn_kernel<Tag, D, decltype(m)::value, false, false, true>>(grid, block, ring, st, p); });
+        for_mask(inst.mask, [&](auto m) { launch<attn_kernel<Tag, D, decltype(m)::value, false, false, true>>(grid, block, ring, st, p); });
         return true;
       }
       break;
     case AttnRoute::PLAIN:
-      for_mask(p.mask, [&](auto m) { launch<attn_kernel<Tag, D, decltype(m)::value>>(grid, block, ring, st, p); });
+      for_mask(inst.mask, [&](auto m) { launch<attn_kernel<Tag, D, decltype(m)::value>>(grid, block, ring, st, p); });
       return true;
   }
   return false;
@@ -1501,9 +1516,8 @@ void launch_tattn_mfma(const void* qkv, long ldqkv, void* out, long ldo, int bat
                                  1.4426950408889634f / sqrtf(64.0f), units);
 }
 
-}  // namespace
-
-extern "C" int tt_attention(const TtAttnArgs* a, tt_stream_t stream) {
+// what tt_attention checks of a problem, and its launch parameters
+int attn_params(const TtAttnArgs* a, AttnP& p) {
   if (!a || (!a->q && !a->qx) || !a->k || !a->vt || !a->out) TT_FAIL(TT_EINVAL, "tt_attention: null operand");
   if (a->qx) {
     if (a->mask == 0 || a->head_dim != 64 || a->dtype == TT_F32 || a->fp8)
@@ -1531,7 +1545,6 @@ extern "C" int tt_attention(const TtAttnArgs* a, tt_stream_t stream) {
   // slice of a fused Q | K | V buffer offset by a non-multiple of 8 elements would otherwise be read misaligned instead of refused)
   if ((((size_t)a->q | (size_t)a->k | (size_t)a->vt | (size_t)a->out) & 15))
     TT_FAIL(TT_EINVAL, "tt_attention: q, k, vt and out must start on 16-byte boundaries");
-  AttnP p;
   p.q = (const char*)a->q; p.ldq = a->ldq; p.k = (const char*)a->k; p.ldk = a->ldk;
   p.vt = (const char*)a->vt; p.ldvt = a->ldvt; p.out = (char*)a->out; p.ldo = a->ldo;
   p.nseq = a->nseq; p.lq = a->lq; p.heads = a->heads; p.mask = a->mask; p.lk = a->lk;
@@ -1559,12 +1572,25 @@ extern "C" int tt_attention(const TtAttnArgs* a, tt_stream_t stream) {
     if (xb >= (1L << 31) || wb >= (1L << 31)) TT_FAIL(TT_EUNSUPPORTED, "tt_attention: x or Wq larger than 2 GiB");
     p.qx_bytes = (unsigned)xb; p.wq_bytes = (unsigned)wb;
   }
-  const AttnRoute route = resolve_attention(*a);
+  return TT_OK;
+}
+}  // namespace
+
+extern "C" int tt_attention(const TtAttnArgs* a, tt_stream_t stream) {
+  AttnP p;
+  if (const int rc = attn_params(a, p)) return rc;
+  const AttnInst inst = attn_inst(*a);
   bool launched = false;
-  for_tag_dim(a->dtype, a->head_dim, [&](auto tag, auto dim) { launched = launch_attention<decltype(tag), decltype(dim)::value>(route, p, (hipStream_t)stream); });
+  for_tag_dim(a->dtype, a->head_dim, [&](auto tag, auto dim) { launched = launch_attention<decltype(tag), decltype(dim)::value>(inst, p, (hipStream_t)stream); });
   if (!launched) TT_FAIL(TT_EUNSUPPORTED, "tt_attention: no kernel instance for this route, dtype and head_dim");
   TT_CHECK_LAUNCH("tt_attention");
   return TT_OK;
+}
+
+extern "C" int tt_attention_kernel(const TtAttnArgs* a, char* name, int32_t cap) {
+  AttnP p;
+  if (const int rc = attn_params(a, p)) return rc;
+  return attn_inst_name(attn_inst(*a), a->dtype, name, cap);
 }
 
 extern "C" int tt_temporal_attention(const void* qkv, int64_t ldqkv, void* out, int64_t ldo, int32_t batch, int32_t frames,

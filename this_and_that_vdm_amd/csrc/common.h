@@ -26,6 +26,10 @@ static __device__ __attribute__((aligned(64))) unsigned int tt_zero_page[64] = {
 
 void tt_set_error(const char* fmt, ...);
 #define TT_FAIL(code, ...) do { tt_set_error(__VA_ARGS__); return (code); } while (0)
+// the tt_*_kernel queries (host only): a kernel instance's name -- the demangled symbol without return type, parameters and namespaces,
+// every template argument written out, as a kernel trace prints it -- formatted into the caller's buffer (TT_EINVAL: it does not fit)
+int tt_put_name(const char* who, char* name, int32_t cap, const char* fmt, ...);
+inline const char* tt_tag_name(int dtype) { return dtype == TT_BF16 ? "bf16_tag" : (dtype == TT_F16 ? "f16_tag" : "f32_tag"); }
 // Kernels that need more than the default 64 KiB of dynamic LDS opt in with hipFuncSetAttribute.  The attribute is per
 // DEVICE, so the "done" flag is a per-device bit mask (one mask per kernel instance), and a failure is kept in
 // tt_attr_err until the entry point's TT_CHECK_LAUNCH reports it (a launch without the opt-in would fail anyway).

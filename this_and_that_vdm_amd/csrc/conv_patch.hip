@@ -282,6 +282,20 @@ int pick_tile(int h, int w) {
   if (h % 8 == 0 && w % 14 == 0) return 2;                    //  8 x 14  (16x28, 8x14)
   return 0;
 }
+// the instance of a supported problem: the pixel tile of its image, and N = 320 / 960 without column waste (TT_CONV_BN: tuning aid)
+struct ConvInst { int th, tw, bn; };
+ConvInst conv_inst(int h, int w, int n) {
+  const int tile = pick_tile(h, w);
+  int bn = (n % 160 == 0 && n % 128 != 0) ? 160 : 128;
+  if (const char* e = getenv("TT_CONV_BN")) bn = atoi(e) == 160 ? 160 : 128;
+  return tile == 1 ? ConvInst{16, 8, bn} : (tile == 2 ? ConvInst{8, 14, bn} : ConvInst{8, 16, bn});
+}
+template <typename Tag>
+void launch_conv_inst(ConvP& p, ConvInst i, hipStream_t st) {
+  if (i.th == 16) launch_conv_bn<Tag, 16, 8>(p, i.bn, st);
+  else if (i.tw == 14) launch_conv_bn<Tag, 8, 14>(p, i.bn, st);
+  else launch_conv_bn<Tag, 8, 16>(p, i.bn, st);
+}
 
 }  // namespace
 
@@ -289,7 +303,9 @@ extern "C" int tt_conv3x3_supported(int32_t h, int32_t w, int32_t c0, int32_t c1
   return (dtype == TT_BF16 || dtype == TT_F16) && pick_tile(h, w) != 0 && c0 > 0 && (c0 & 63) == 0 && (c1 & 63) == 0 && n > 0 && (n & 3) == 0;
 }
 
-extern "C" int tt_conv3x3(const TtConvArgs* a, tt_stream_t stream) {
+namespace {
+// what tt_conv3x3 checks of a problem, and its launch parameters
+int conv_params(const TtConvArgs* a, ConvP& p) {
   if (!a || !a->x0 || !a->w || !a->out) TT_FAIL(TT_EINVAL, "tt_conv3x3: null operand");
   if (!tt_conv3x3_supported(a->h, a->w_img, a->c0, a->c1, a->n, a->dtype))
     TT_FAIL(TT_EUNSUPPORTED, "tt_conv3x3: %dx%d images with %d+%d -> %d channels are served by tt_gemm mode 1 (+ tt_groupnorm_apply)", a->h, a->w_img, a->c0, a->c1, a->n);
@@ -298,7 +314,6 @@ extern "C" int tt_conv3x3(const TtConvArgs* a, tt_stream_t stream) {
   if (a->rowvec && a->rowvec_rows <= 0) TT_FAIL(TT_EINVAL, "tt_conv3x3: rowvec_rows");
   if ((a->ld0 & 7) || (a->c1 && (a->ld1 & 7)) || (a->ldw & 7) || (a->ldo & 3) || (a->residual && (a->ld_res & 3)))
     TT_FAIL(TT_EINVAL, "tt_conv3x3: strides");
-  ConvP p;
   p.x0 = (const char*)a->x0; p.x1 = (const char*)a->x1; p.c0 = a->c0; p.c1 = a->c1; p.ld0 = a->ld0; p.ld1 = a->c1 ? a->ld1 : a->ld0;
   p.w = (const char*)a->w; p.ldw = a->ldw;
   p.gn_scale = a->gn_scale; p.gn_shift = a->gn_shift; p.silu = a->silu;
@@ -315,14 +330,22 @@ extern "C" int tt_conv3x3(const TtConvArgs* a, tt_stream_t stream) {
     TT_FAIL(TT_EUNSUPPORTED, "tt_conv3x3: operand larger than 2 GiB (32-bit buffer offsets)");
   p.x0_bytes = (unsigned)x0b; p.x1_bytes = (unsigned)x1b; p.w_bytes = (unsigned)wb; p.out_bytes = (unsigned)outb;
   p.res_bytes = (unsigned)resb; p.bias_bytes = p.bias ? (unsigned)p.n * 4u : 0u; p.rowvec_bytes = (unsigned)rvb;
-  int bn = (p.n % 160 == 0 && p.n % 128 != 0) ? 160 : 128;
-  if (const char* e = getenv("TT_CONV_BN")) bn = atoi(e) == 160 ? 160 : 128;      // tuning aid
-  hipStream_t st = (hipStream_t)stream;
-  const int tile = pick_tile(p.h, p.w_);
-#define TT_CV(TAG) do { if (tile == 1) launch_conv_bn<TAG, 16, 8>(p, bn, st); else if (tile == 2) launch_conv_bn<TAG, 8, 14>(p, bn, st); \
-                        else launch_conv_bn<TAG, 8, 16>(p, bn, st); } while (0)
-  if (a->dtype == TT_BF16) TT_CV(bf16_tag); else TT_CV(f16_tag);
-#undef TT_CV
+  return TT_OK;
+}
+}  // namespace
+
+extern "C" int tt_conv3x3(const TtConvArgs* a, tt_stream_t stream) {
+  ConvP p;
+  if (const int rc = conv_params(a, p)) return rc;
+  const ConvInst i = conv_inst(p.h, p.w_, p.n);
+  if (a->dtype == TT_BF16) launch_conv_inst<bf16_tag>(p, i, (hipStream_t)stream); else launch_conv_inst<f16_tag>(p, i, (hipStream_t)stream);
   TT_CHECK_LAUNCH("tt_conv3x3");
   return TT_OK;
+}
+
+extern "C" int tt_conv3x3_kernel(const TtConvArgs* a, char* name, int32_t cap) {
+  ConvP p;
+  if (const int rc = conv_params(a, p)) return rc;
+  const ConvInst i = conv_inst(p.h, p.w_, p.n);
+  return tt_put_name("tt_conv3x3_kernel", name, cap, "conv_patch_kernel<%s, %d, %d, %d>", tt_tag_name(a->dtype), i.th, i.tw, i.bn);
 }

@@ -297,6 +297,8 @@ Plan mode3_plan(const TtGemmArgs* a, Plan pl) {
   const long b128 = (long)ceil_div(a->m, 128) * ceil_div(a->n, 128), b12864 = (long)ceil_div(a->m, 128) * ceil_div(a->n, 64);
   return Plan{b128 >= 384 ? 11 : (b12864 >= 384 ? 1 : 2), 1};   // (the wide / N = 160 t shapes: make_plan's choice for the other sizes)
 }
+// do the products of `a` run split (GemmP.f32_split)?
+int f32_split_of(const TtGemmArgs* a) { return a->dtype == TT_F32 ? knobs().f32_split : 0; }
 bool mode3_served(const TtGemmArgs* a, const Plan& pl) { return a->mode != 3 || tile_of(a->dtype, pl.cfg).m3; }
 // TT_F32 products: 0 = exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, 157 TFLOP/s peak), 1 = "split16": every fp32 operand split on the fly into
 // fp16 hi + lo, three 16-bit MFMAs per product block (gemm_kernel.h, `mma`): ~2^-21 relative per product at 3 / 16 of the issue time.
@@ -569,6 +571,7 @@ int32_t gn_fused_on(const TtGemmArgs* a, const Route& r) {
 }  // namespace
 
 int tt_internal_f32_split() { return knobs().f32_split; }
+extern "C" int32_t tt_gemm_get_f32_split(void) { return knobs().f32_split; }
 
 extern "C" int tt_gemm_set_tile_override(int32_t cfg) {
   if (cfg < -1 || cfg >= kNumCfgs) TT_FAIL(TT_EINVAL, "tt_gemm_set_tile_override: cfg %d (valid -1..%d)", cfg, kNumCfgs - 1);
@@ -591,15 +594,51 @@ extern "C" int32_t tt_gemm_is_wide(const TtGemmArgs* a) {
   return resolve(a).wide ? 1 : 0;
 }
 
+namespace {
+// what the two host-only queries below refuse, and the route of everything else
+int queried_route(const char* who, const TtGemmArgs* a, const void* result, Route* r) {
+  if (!a || !result || a->m <= 0 || a->n <= 0) TT_FAIL(TT_EINVAL, "%s: bad arguments", who);
+  if (is_up2(a)) if (const char* why = up2_refusal(a)) TT_FAIL(TT_EINVAL, "%s: upsample = 2 needs %s", who, why);
+  *r = resolve(a);
+  if (r->kind == Kind::UNSUPPORTED)
+    TT_FAIL(TT_EUNSUPPORTED, "%s: forced tile configuration %d has no mode-3 variant (mode 3 is built for 1, 2, 11, 16)", who, r->cfg);
+  return TT_OK;
+}
+}  // namespace
+
 extern "C" int tt_gemm_plan(const TtGemmArgs* a, int32_t cfg[7]) {
-  if (!a || !cfg || a->m <= 0 || a->n <= 0) TT_FAIL(TT_EINVAL, "tt_gemm_plan: bad arguments");
-  if (is_up2(a)) if (const char* why = up2_refusal(a)) TT_FAIL(TT_EINVAL, "tt_gemm_plan: upsample = 2 needs %s", why);
-  const Route r = resolve(a);
-  if (r.kind == Kind::UNSUPPORTED)
-    TT_FAIL(TT_EUNSUPPORTED, "tt_gemm_plan: forced tile configuration %d has no mode-3 variant (mode 3 is built for 1, 2, 11, 16)", r.cfg);
-  const TileCfg t = route_tile(a, r);              // (stages = 0: not the tiled template -- ops.py tells the kernels apart by it and the tile)
+  Route r;
+  if (const int rc = queried_route("tt_gemm_plan", a, cfg, &r)) return rc;
+  const TileCfg t = route_tile(a, r);              // (stages = 0: not the tiled template)
   cfg[0] = t.bm; cfg[1] = t.bn; cfg[2] = t.bk; cfg[3] = t.nst; cfg[4] = t.wgm; cfg[5] = t.wgn; cfg[6] = r.splitk;
   return TT_OK;
+}
+
+// The instance of the route's kernel: each family's selector (gemm_kernel.h) is asked what its launcher asks it, with the fields
+// fill_params copies into GemmP unchanged.  A two-part problem: the head's kernel; a split plan: the main kernel (not the reduction pass).
+extern "C" int tt_gemm_kernel(const TtGemmArgs* a, char* name, int32_t cap) {
+  Route r;
+  if (const int rc = queried_route("tt_gemm_kernel", a, name, &r)) return rc;
+  const char* who = "tt_gemm_kernel", *tag = tt_tag_name(a->dtype);
+  switch (r.kind) {
+    case Kind::PP: case Kind::PP_TWO_PART: {
+      const PpInst i = pp_inst(a->ln_fold, a->geglu);
+      return tt_put_name(who, name, cap, "gemm_pp_kernel<%s, %d, %d>", tag, i.lnrows, i.geglu);
+    }
+    case Kind::SQ320: {
+      const Sq320Inst i = sq320_inst(a->residual, a->rowvec);
+      return tt_put_name(who, name, cap, "sq320_kernel<%s, %s, %s>", tag, i.has_res ? "true" : "false", i.has_rv ? "true" : "false");
+    }
+    case Kind::W320: case Kind::W320H: case Kind::W320H_SPLIT: {
+      const W320Inst i = w320_inst(a->mode, a->ln_fold);
+      return tt_put_name(who, name, cap, "gemm_w320%s_kernel<%s, %d, %d>", r.kind == Kind::W320 ? "" : "h", tag, i.mode, i.lnrows);
+    }
+    default: {
+      const TileCfg t = tile_of(a->dtype, r.cfg);
+      const int kmode = tile_kmode(a->mode, a->ln_fold, a->presplit, f32_split_of(a), r.wide, t.ln, t.m3);
+      return tt_put_name(who, name, cap, "gemm_kernel<%s, %d, %d, %d, %d, %d, %d, %d>", tag, t.bm, t.bn, t.bk, t.nst, t.wgm, t.wgn, kmode);
+    }
+  }
 }
 
 // rows per statistics tile of the route tt_gemm takes (0: no statistics epilogue on it); see include/ttvdm.h
@@ -655,7 +694,7 @@ int fill_params(const TtGemmArgs* a, const Route& r, GemmP& p) {
   p.out = (char*)a->out; p.ldo = a->ldo; p.out_f32 = a->dtype == TT_F32 ? 0 : a->out_f32;   // TT_F32 stores fp32 anyway
   p.out_col_hw = a->out_col_hw; p.out_col_hwp = a->out_col_hwp;
   p.ln_fold = a->ln_fold; p.ln_eps = a->ln_eps; p.out_fp8 = a->out_fp8; p.stats = a->stats_out; p.stat_rows = a->gn_out ? a->stats_seg : (a->stats_out ? stats_rows_on(a, r) : 0);
-  p.f32_split = a->dtype == TT_F32 ? knobs().f32_split : 0;
+  p.f32_split = f32_split_of(a);
   p.presplit = a->presplit;
   if (a->presplit) {
     if ((a->presplit & ~3) || a->dtype != TT_F32 || !p.f32_split)

@@ -301,7 +301,7 @@ void gemm_kernel(const GemmP p) {
   // tile in 64-bit scalar arithmetic -- onto the first row the tile can touch -- and the lanes' offsets count from that row.  num_records
   // is the rest of the operand capped below 2^31, so an offset of 0x80000000 still reads zeros / drops the store; tt_gemm refuses a
   // problem in which one tile's window itself reaches 2 GiB.  Same tile, ring, K order and epilogue arithmetic as KMODE_ - 64: the same
-  // bits.  Built for modes 0 / 1 / 2 with the bias / scale / residual / blend / fp32-out epilogues and stats_out (launch_cfg_wide).
+  // bits.  Built for modes 0 / 1 / 2 with the bias / scale / residual / blend / fp32-out epilogues and stats_out (tile_kmode).
   constexpr bool WIDE = (KMODE_ & 64) != 0;
   constexpr int KMODE = KMODE_ & 7;
   static_assert(SPLIT || (!PRE_A && !PRE_B), "pre-split operands belong to the split variants");
@@ -1603,79 +1603,52 @@ void tile_params(GemmP& p) {
   fill_fastdivs(p);
 }
 
-// the wide variant (KMODE + 64, see gemm_kernel) of a tile shape: modes 0 / 1 / 2, un-split, operands not pre-split (tt_gemm refuses the rest)
-template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN>
-void launch_cfg_wide(GemmP& p, hipStream_t st) {
-  tile_params<Tag, BM, BN, BK, NST, WGM, WGN>(p);
-  if constexpr (std::is_same<Tag, f32_tag>::value) {
-    if (p.f32_split) {
-      switch (p.mode) {
-        case 0: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 8>(p, st); break;
-        case 1: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 9>(p, st); break;
-        default: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 10>(p, st); break;
-      }
-      return;
-    }
-  }
-  switch (p.mode) {
-    case 0: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64>(p, st); break;
-    case 1: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 1>(p, st); break;
-    default: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 64 + 2>(p, st); break;
-  }
+// ---- which instance of gemm_kernel a launch on a tile runs: the ONE place that says so.  launch_cfg dispatches on the answer and
+// tt_gemm_kernel (gemm.hip) prints it.  KMODE_ = the base mode 0..5 (0 / 1 / 2: the gather of p.mode; 3 / 4: LayerNorm folded over the rows of
+// A / of W; 5: the mode-3 gather) + 8 split-fp16 products (TT_F32) + 16 / + 32 W / A arrives pre-split + 64 the wide (windowed) variant.
+// lnok / m3ok: the tile's LNOK / M3OK columns.  -1: mode 3 on a tile without the gather (tt_gemm refuses it before it gets here).
+// Wide: modes 0 / 1 / 2, operands not pre-split, no fold (tt_gemm refuses the rest).  Pre-split: W wherever its rows are not the
+// LayerNorm's, A only as a Linear operand whose rows are not (convs: only the weight is ever pre-split).
+constexpr int tile_kmode(int mode, int ln_fold, int presplit, bool f32_split, bool wide, bool lnok, bool m3ok) {
+  const int gather = mode == 0 ? 0 : (mode == 1 ? 1 : 2), split = f32_split ? 8 : 0;
+  const int w_pre = f32_split && (presplit & 2) ? 16 : 0, a_pre = f32_split && (presplit & 1) ? 32 : 0;
+  if (wide) return 64 + split + gather;
+  if (mode == 3) return m3ok ? 5 + split + w_pre : -1;
+  if (lnok && ln_fold == 1) return 3 + split + w_pre;
+  if (lnok && ln_fold == 2) return 4 + split + a_pre;
+  return gather + split + w_pre + (mode == 0 ? a_pre : 0);
 }
+// Every KMODE_ that is built, with the tiles it is built on: X(KMODE_, condition) over F32 (the TT_F32 tiles), LNOK / M3OK (the tile's
+// columns) and WIDE (the units of TT_GEMM_WIDE_TILES).  A row more is a kernel more per tile: compile time and library size.
+#define TT_GEMM_KMODES(X) \
+  X(0, !WIDE) X(1, !WIDE) X(2, !WIDE) X(3, !WIDE && LNOK) X(4, !WIDE && LNOK) X(5, !WIDE && M3OK) \
+  X(8, !WIDE && F32) X(8 + 16, !WIDE && F32) X(8 + 32, !WIDE && F32) X(8 + 48, !WIDE && F32) \
+  X(9, !WIDE && F32) X(9 + 16, !WIDE && F32) X(10, !WIDE && F32) X(10 + 16, !WIDE && F32) \
+  X(11, !WIDE && F32 && LNOK) X(11 + 16, !WIDE && F32 && LNOK) X(12, !WIDE && F32 && LNOK) X(12 + 32, !WIDE && F32 && LNOK) \
+  X(13, !WIDE && F32 && M3OK) X(13 + 16, !WIDE && F32 && M3OK) \
+  X(64, WIDE) X(64 + 1, WIDE) X(64 + 2, WIDE) X(64 + 8, WIDE && F32) X(64 + 9, WIDE && F32) X(64 + 10, WIDE && F32)
 
-template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN, bool LNOK = false, bool M3OK = false>
+template <typename Tag, int BM, int BN, int BK, int NST, int WGM, int WGN, bool LNOK = false, bool M3OK = false, bool WIDE = false>
 void launch_cfg(GemmP& p, hipStream_t st) {
+  constexpr bool F32 = std::is_same<Tag, f32_tag>::value;
   tile_params<Tag, BM, BN, BK, NST, WGM, WGN>(p);
-  if (p.mode == 3) {                         // routed explicitly: the switches below send unknown modes elsewhere
-    if constexpr (M3OK) {
-      if constexpr (std::is_same<Tag, f32_tag>::value) {
-        if (p.f32_split) {                   // split-fp16 products (convs: only the weight is ever pre-split)
-          if (p.presplit & 2) launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 13 + 16>(p, st); else launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 13>(p, st);
-          return;
-        }
-      }
-      launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 5>(p, st);
-    }
-    return;                                  // (tt_gemm refuses mode 3 on tile shapes without the variant before it gets here)
-  }
-  if constexpr (std::is_same<Tag, f32_tag>::value) {
-    if (p.f32_split) {                       // tt_gemm_set_f32_split(1): the split-fp16 product variants (KMODE + 8)
-      // KMODE + 8 (split products) + 16 (W pre-split: packed weights) / + 32 (A pre-split: the swapped V^T projection's weights)
-      const int pre = p.presplit & 3;
-      if (LNOK && p.ln_fold == 1) {          // statistics of the A rows: A is never pre-split here (tt_gemm refuses it)
-        if (pre & 2) launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 11 + 16>(p, st); else launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 11>(p, st);
-        return;
-      }
-      if (LNOK && p.ln_fold == 2) {          // statistics of the W rows: W is never pre-split here
-        if (pre & 1) launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 12 + 32>(p, st); else launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 12>(p, st);
-        return;
-      }
-      switch (p.mode * 4 + pre) {
-        case 0: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 8>(p, st); break;
-        case 1: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 8 + 32>(p, st); break;
-        case 2: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 8 + 16>(p, st); break;
-        case 3: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 8 + 48>(p, st); break;
-        case 4: case 5: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 9>(p, st); break;            // (convs: only the weight is ever pre-split)
-        case 6: case 7: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 9 + 16>(p, st); break;
-        case 8: case 9: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 10>(p, st); break;
-        default: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 10 + 16>(p, st); break;
-      }
-      return;
-    }
-  }
-  if constexpr (LNOK) {
-    if (p.ln_fold == 1) { launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 3>(p, st); return; }
-    if (p.ln_fold == 2) { launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 4>(p, st); return; }
-  }
-  switch (p.mode) {
-    case 0: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 0>(p, st); break;
-    case 1: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 1>(p, st); break;
-    default: launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, 2>(p, st); break;
+  switch (tile_kmode(p.mode, p.ln_fold, p.presplit, p.f32_split, WIDE, LNOK, M3OK)) {
+#define TT_KMODE_CASE(km, built) case km: if constexpr (built) launch_mode<Tag, BM, BN, BK, NST, WGM, WGN, km>(p, st); break;
+    TT_GEMM_KMODES(TT_KMODE_CASE)
+#undef TT_KMODE_CASE
   }
 }
 
-template <typename Tag, bool HAS_RES, bool HAS_RV = false>
+// the instances of the streaming 320 x 320 kernel: a row vector only rides on the residual form (the output projections)
+struct Sq320Inst { bool has_res, has_rv; };
+inline Sq320Inst sq320_inst(const void* residual, const void* rowvec) { return Sq320Inst{residual || rowvec, rowvec != nullptr}; }
+// ... of the persistent kernel (gemm_pp.hip) and of the two big-tile kernels (gemm_w320.hip: the fold only rides on the Linear gather)
+struct PpInst { int lnrows, geglu; };
+inline PpInst pp_inst(int ln_fold, int geglu) { return PpInst{ln_fold ? 1 : 0, geglu ? 1 : 0}; }
+struct W320Inst { int mode, lnrows; };
+inline W320Inst w320_inst(int mode, int ln_fold) { return mode == 1 || mode == 2 ? W320Inst{mode, 0} : W320Inst{0, ln_fold ? 1 : 0}; }
+
+template <typename Tag, bool HAS_RES, bool HAS_RV>
 void launch_sq320(const GemmP& p, hipStream_t st) {
   constexpr size_t lds = (size_t)(HAS_RES ? 3 * 2 * SQ_TILE_BYTES : 5 * SQ_TILE_BYTES) + SQ_WAVES * 4096;
   static_assert(lds <= 160 * 1024, "sq320 LDS");
@@ -1683,6 +1656,13 @@ void launch_sq320(const GemmP& p, hipStream_t st) {
   tt_lds_opt_in((const void*)sq320_kernel<Tag, HAS_RES, HAS_RV>, (int)lds, &attr_done);
   const int ntiles = (p.m + SQ_ROWS - 1) / SQ_ROWS;
   hipLaunchKernelGGL((sq320_kernel<Tag, HAS_RES, HAS_RV>), dim3(ntiles < 256 ? ntiles : 256), dim3(SQ_NT), lds, st, p);
+}
+template <typename Tag>
+void launch_sq320_tag(const GemmP& p, hipStream_t st) {
+  const Sq320Inst i = sq320_inst(p.residual, p.rowvec);
+  if (i.has_rv) launch_sq320<Tag, true, true>(p, st);
+  else if (i.has_res) launch_sq320<Tag, true, false>(p, st);
+  else launch_sq320<Tag, false, false>(p, st);
 }
 
 // ---- the tile table: every tile shape of gemm_kernel is written down here, once.  X(index, BM, BN, BK, NST, WGM, WGN, LNOK, M3OK);
@@ -1745,7 +1725,7 @@ static_assert(wide_tiles_match16(kCfgs) && wide_tiles_match32(kCfgsF32), "a wide
 #define TT_WIDE_IS(i, bm, bn, bk, nst, wgm, wgn) || cfg == i
 constexpr bool wide_capable(bool f32, int cfg) { return f32 ? (false TT_GEMM_WIDE_TILES_F32(TT_WIDE_IS)) : (false TT_GEMM_WIDE_TILES(TT_WIDE_IS)); }
 #undef TT_WIDE_IS
-#define TT_WIDE_CASE(i, bm, bn, bk, nst, wgm, wgn) case i: launch_cfg_wide<Tag, bm, bn, bk, nst, wgm, wgn>(p, st); break;
+#define TT_WIDE_CASE(i, bm, bn, bk, nst, wgm, wgn) case i: launch_cfg<Tag, bm, bn, bk, nst, wgm, wgn, false, false, true>(p, st); break;
 
 // cfg = index into the table of Tag's storage type; an index outside it launches nothing (the planner hands out none)
 #define TT_TILE_CASE(i, bm, bn, bk, nst, wgm, wgn, ln, m3) case i: launch_cfg<Tag, bm, bn, bk, nst, wgm, wgn, ln, m3>(p, st); break;

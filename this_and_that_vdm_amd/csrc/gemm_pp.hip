@@ -465,8 +465,13 @@ static void launch_pp_inst(GemmP& p, hipStream_t st) {
 }
 template <typename Tag>
 static void launch_pp_tag(GemmP& p, hipStream_t st) {
-  if (p.ln_fold) { if (p.geglu) launch_pp_inst<Tag, 1, 1>(p, st); else launch_pp_inst<Tag, 1, 0>(p, st); }
-  else { if (p.geglu) launch_pp_inst<Tag, 0, 1>(p, st); else launch_pp_inst<Tag, 0, 0>(p, st); }
+  const PpInst i = pp_inst(p.ln_fold, p.geglu);
+  switch (i.lnrows * 2 + i.geglu) {
+    case 3: launch_pp_inst<Tag, 1, 1>(p, st); break;
+    case 2: launch_pp_inst<Tag, 1, 0>(p, st); break;
+    case 1: launch_pp_inst<Tag, 0, 1>(p, st); break;
+    default: launch_pp_inst<Tag, 0, 0>(p, st); break;
+  }
 }
 void launch_pp_bf16(GemmP& p, hipStream_t st) { launch_pp_tag<bf16_tag>(p, st); }
 void launch_pp_f16(GemmP& p, hipStream_t st) { launch_pp_tag<f16_tag>(p, st); }

@@ -724,10 +724,13 @@ static void launch_w320_tile(GemmP& p, hipStream_t st) {
   p.tiles_n = p.n / 320;
   p.nk0 = p.k0 / 64; p.nk1 = p.k1 / 64;
   p.kt_total = p.taps * (p.nk0 + p.nk1);
-  if (p.mode == 1) launch_w320_inst<Tag, BM, 1, 0>(p, st);
-  else if (p.mode == 2) launch_w320_inst<Tag, BM, 2, 0>(p, st);
-  else if (p.ln_fold) launch_w320_inst<Tag, BM, 0, 1>(p, st);
-  else launch_w320_inst<Tag, BM, 0, 0>(p, st);
+  const W320Inst i = w320_inst(p.mode, p.ln_fold);
+  switch (i.mode * 2 + i.lnrows) {
+    case 2: launch_w320_inst<Tag, BM, 1, 0>(p, st); break;
+    case 4: launch_w320_inst<Tag, BM, 2, 0>(p, st); break;
+    case 1: launch_w320_inst<Tag, BM, 0, 1>(p, st); break;
+    default: launch_w320_inst<Tag, BM, 0, 0>(p, st); break;
+  }
 }
 void launch_w320(GemmP& p, hipStream_t st, int bm, bool bf16) {
   if (bm == 256) { if (bf16) launch_w320_tile<bf16_tag, 256>(p, st); else launch_w320_tile<f16_tag, 256>(p, st); }

@@ -2,6 +2,7 @@
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 #include <vector>
 #include "ttvdm.h"
 
@@ -12,6 +13,20 @@ void tt_set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof g_err, fmt, ap);
   va_end(ap);
+}
+
+int tt_put_name(const char* who, char* name, int32_t cap, const char* fmt, ...) {
+  char buf[128];
+  va_list ap;
+  va_start(ap, fmt);
+  const int len = vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (!name || len < 0 || len >= (int)sizeof buf || len >= cap) {
+    tt_set_error("%s: the name takes %d bytes with its terminator, the buffer holds %d", who, len + 1, name ? cap : 0);
+    return TT_EINVAL;
+  }
+  memcpy(name, buf, (size_t)len + 1);
+  return TT_OK;
 }
 
 extern "C" int tt_abi_version(void) { return 11; }   // 2: TtGemmArgs.ln_fold / ln_eps, TT_F32; 3: out_fp8, TtAttnArgs.fp8, tt_add_rowvec, tt_conv3x3; 4: tt_groupnorm_small; 5: tt_softmax_rows; 6: TtAttnArgs fused query projection (qx, wq, bq, qc, ln_eps), tt_gemm_set_big_tile; 7: TtGemmArgs.rowvec_mod; 8: TtGemmArgs.stats_out / stats_seg, tt_gemm_stats_rows, tt_groupnorm_tiles; 9: TtGemmArgs.gn_out (GroupNorm in the split-K reduction), tt_gemm_gn_fused; 10: TtAttnArgs.v_rows (row-major V); 11: tt_gemm_set_f32_split (split-fp16 products in TT_F32)
