@@ -283,6 +283,9 @@ typedef struct TtAttnArgs {
   int32_t mask;                        /* 0,1,2 as above */
   int32_t lk;                          /* valid keys per sequence/context */
   int32_t k_seq_stride, v_seq_stride;  /* rows of k / columns of vt per sequence (mask 0) or per context (1,2) */
+  /* Finite values between lk and the stride never contribute: the rows of k and the columns of vt (v_rows: the rows of V) in
+   * [lk, stride) of a sequence / context may hold anything finite -- their probability is an exact zero, on every route (fp8, v_rows and
+   * the fused query projection included).  tests/test_attention_closed_forms_gpu.py runs every route with that padding poisoned. */
   int32_t frames, ctx_batches;         /* masks 1,2 */
   int32_t dtype;
   int32_t batch0;                      /* masks 1,2: batch index of sequence 0 (a launch may cover a sub-range of the batch) */
@@ -321,7 +324,7 @@ int tt_attention_kernel(const TtAttnArgs* args, char* name, int32_t cap);
 /* temporal self-attention over the frame axis (seq = frames <= 32), one 16/32-lane group per
  * (batch, pixel, head); replaces TemporalBasicTransformerBlock.attn1 incl. its two
  * [(B F),hw,C] <-> [(B hw),F,C] permute copies (diffusers; reached from transformer_temporal.py:361).
- * qkv [batch*frames*hw, ldqkv] holds Q | K | V at column offsets 0, C, 2C. */
+ * qkv [batch*frames*hw, ldqkv] holds Q | K | V at column offsets 0, C, 2C; columns from 3C up to ldqkv are never read. */
 int tt_temporal_attention(const void* qkv, int64_t ldqkv, void* out, int64_t ldo, int32_t batch, int32_t frames,
                           int32_t hw, int32_t heads, int32_t head_dim, int32_t dtype, tt_stream_t stream);
 
