@@ -445,6 +445,33 @@ int tt_cfg_euler_step_requests(const float* eps, int64_t ld_eps, float* latents,
                                float image_guidance_scale, const float* sigmas, int32_t step, int32_t requests, int32_t cfg,
                                int32_t frames, int32_t h, int32_t w, tt_stream_t stream);
 
+/* A second sampler on the same glue (additive: the ABI version is unchanged): DPM-Solver++ multistep, second order ("2M"; Lu, Zhou,
+ * Bao, Chen, Li, Zhu, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models", 2022, the multistep
+ * second-order data-prediction update) in the sigma parametrisation alpha = 1, lambda = -ln sigma.  One network evaluation per step,
+ * like Euler; the only state is the previous step's data prediction x0.
+ * Schedule and coefficients (host; svd/scheduling_dpmsolver_multistep.py): the schedule is EulerDiscreteScheduler.set_timesteps' --
+ *   the same fp32 sigmas (N values and a final 0), timesteps 0.25 ln sigma, init_noise_sigma, scale_model_input.  For step i with
+ *   1 <= i <= N-2:  h_i = ln(sigma_i / sigma_{i+1}),  c_i = h_i / (2 h_{i-1}),  computed in fp64 from the fp32 sigmas and rounded to
+ *   fp32.  c_0 = 0 (no history yet); c_{N-1} = 0 (sigma_N = 0, h infinite: diffusers' final_sigmas_type "zero" makes the last step
+ *   first order).  solver_order 1: every c_i = 0.  N = 1 and N = 2 run first order throughout.
+ * Per latent element, fp32, every product and sum rounded on its own (contraction off), in the statement order of
+ * tt_cfg_euler_step_requests:
+ *     v    = CFG combination of eps                       the three cases and statements of tt_cfg_euler_step_requests
+ *     x0   = v * c_out + x * c_skip                       c_out = -s / sqrtf(s*s + 1), c_skip = 1 / (s*s + 1), s = sigmas[step]
+ *     D    = (c != 0) ? x0 + c * (x0 - hist) : x0         a branch, not a multiply: hist is NOT read when c == 0
+ *     hist = x0                                           always stored
+ *     x    = x + (x - D) / s * (s_next - s)               s_next = sigmas[step + 1]
+ * which is  x' = (s'/s) x + (1 - s'/s) [(1 + 1/(2r)) x0 - (1/(2r)) x0_prev],  r = h_{i-1} / h_i:  diffusers' "dpmsolver++" /
+ * "midpoint" second-order update.  With c == 0 it is tt_cfg_euler_step_requests statement for statement, bit for bit.
+ * tt_cfg_multistep_step_requests: eps, latents, guidance, the batch order and cfg 1 / 2 / 3 as tt_cfg_euler_step_requests (requests >=
+ *   1); x0_hist fp32 [R,F,4,h,w], laid out like latents; coef: device, one fp32, the c of this step.  coef and sigmas are read on the
+ *   device, so one captured graph serves every step.  Element indices are 64-bit.  TT_EINVAL (tt_last_error has the text; nothing is
+ *   launched): a null eps / latents / x0_hist / sigmas / coef, and every refusal of tt_cfg_euler_step_requests. */
+int tt_cfg_multistep_step_requests(const float* eps, int64_t ld_eps, float* latents, float* x0_hist, const float* guidance,
+                                   int32_t guidance_per_request, float image_guidance_scale, const float* sigmas, int32_t step,
+                                   const float* coef /* device, one fp32: c of this step */, int32_t requests, int32_t cfg,
+                                   int32_t frames, int32_t h, int32_t w, tt_stream_t stream);
+
 /* layout plumbing at the drop-in boundary: NCHW (any float dtype code below) <-> token-major.
  * src_kind/dst_kind: 0 = dtype (bf16/f16), 1 = fp32. */
 int tt_nchw_to_tokens(const void* src, int32_t src_f32, int32_t nimg, int32_t c, int32_t hw, void* dst, int64_t ld_dst,

@@ -136,6 +136,8 @@ SIGNATURES = {
     # the R-request forms of the loop glue (additive; the ABI version is unchanged)
     "tt_prep_model_input_requests": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "tt_cfg_euler_step_requests": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _f32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    # the DPM-Solver++ 2M step on the same glue (additive; the ABI version is unchanged)
+    "tt_cfg_multistep_step_requests": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _f32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "tt_nchw_to_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
     "tt_tokens_to_nchw": (C.c_int, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "tt_add_scaled": (C.c_int, [_vp, _vp, _f32, _vp, _i64, _i32, _vp]),

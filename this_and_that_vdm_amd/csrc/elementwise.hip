@@ -282,6 +282,52 @@ __global__ void cfg_euler_requests_kernel(const float* eps, long ld_eps, float* 
   }
 }
 
+// DPM-Solver++ 2M step (tt_cfg_multistep_step_requests, arithmetic in include/ttvdm.h): cfg_euler_requests_kernel with the data
+// prediction extrapolated from the previous step's, D = x0 + c (x0 - hist), before the same update statement.  c is read on the device
+// (one captured graph serves every step) and is uniform over the launch, so the branch on it does not diverge; with c == 0 the history
+// is written and never read, and the latents are the Euler kernel's bit for bit.
+__global__ void cfg_multistep_requests_kernel(const float* eps, long ld_eps, float* lat, float* hist, const float* guidance,
+                                              int guidance_per_request, const float* sigmas, int step, const float* coef, int requests,
+                                              int cfg, int frames, long hw, float image_guidance) {
+#pragma clang fp contract(off)
+  const long total = (long)requests * frames * hw;
+  const float sg = sigmas[step], sn = sigmas[step + 1];
+  const float c_out = -sg / sqrtf(sg * sg + 1.0f), c_skip = 1.0f / (sg * sg + 1.0f);
+  const float cm = coef[0];
+  const long cls = (long)requests * frames * hw;            // token rows between two CFG classes of one request
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long p = i % hw;
+    const long rf = i / hw;                     // r * frames + f
+    const long f = rf % frames;
+    const long r = rf / frames;
+    const float g = guidance ? guidance[(guidance_per_request ? r * frames : 0) + f] : 1.0f;
+    const float* e = eps + (rf * hw + p) * ld_eps;          // class 0 of request r
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float v;
+      if (cfg == 3) {             // InstructPix2Pix order (reference :698-702): first-frame, cond, uncond
+        const float e1 = e[c];
+        const float cd = e[cls * ld_eps + c];
+        const float u = e[2 * cls * ld_eps + c];
+        v = u + g * (cd - u) + image_guidance * (cd - e1);
+      } else if (cfg == 2) {
+        const float u = e[c];
+        const float cd = e[cls * ld_eps + c];
+        v = u + g * (cd - u);
+      } else {
+        v = e[c];
+      }
+      const long j = (rf * 4 + c) * hw + p;
+      const float xv = lat[j];
+      const float x0 = v * c_out + xv * c_skip;
+      float d = x0;
+      if (cm != 0.0f) d = x0 + cm * (x0 - hist[j]);
+      hist[j] = x0;
+      lat[j] = xv + (xv - d) / sg * (sn - sg);
+    }
+  }
+}
+
 // NCHW -> tokens through a 32x32 LDS transpose (coalesced both sides)
 template <typename Tag, bool SRC_F32>
 __global__ void nchw_to_tokens_kernel(const char* src, int c, int hw, char* dst, long ld_dst) {
@@ -623,6 +669,24 @@ extern "C" int tt_cfg_euler_step_requests(const float* eps, int64_t ld_eps, floa
   hipLaunchKernelGGL(cfg_euler_requests_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, eps, (long)ld_eps, latents, guidance,
                      guidance_per_request, sigmas, step, requests, cfg, frames, hw, image_guidance_scale);
   TT_CHECK_LAUNCH("tt_cfg_euler_step_requests");
+  return TT_OK;
+}
+
+extern "C" int tt_cfg_multistep_step_requests(const float* eps, int64_t ld_eps, float* latents, float* x0_hist, const float* guidance,
+                                              int32_t guidance_per_request, float image_guidance_scale, const float* sigmas, int32_t step,
+                                              const float* coef, int32_t requests, int32_t cfg, int32_t frames, int32_t h, int32_t w,
+                                              tt_stream_t stream) {
+  if (!eps || !latents || !x0_hist || !sigmas || !coef) TT_FAIL(TT_EINVAL, "tt_cfg_multistep_step_requests: null operand");
+  if (requests <= 0 || cfg < 1 || cfg > 3 || frames <= 0 || h <= 0 || w <= 0 || ld_eps < 4 || step < 0)
+    TT_FAIL(TT_EINVAL, "tt_cfg_multistep_step_requests: requests/cfg/frames/h/w/ld_eps (cfg is 1, 2 or 3)");
+  if (cfg == 3 && !guidance) TT_FAIL(TT_EINVAL, "tt_cfg_multistep_step_requests: cfg 3 (use_instructpix2pix) needs guidance");
+  if (guidance_per_request != 0 && guidance_per_request != 1) TT_FAIL(TT_EINVAL, "tt_cfg_multistep_step_requests: guidance_per_request is 0 or 1");
+  const long hw = (long)h * w;
+  const long total = (long)requests * frames * hw;
+  long blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(cfg_multistep_requests_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, eps, (long)ld_eps, latents, x0_hist,
+                     guidance, guidance_per_request, sigmas, step, coef, requests, cfg, frames, hw, image_guidance_scale);
+  TT_CHECK_LAUNCH("tt_cfg_multistep_step_requests");
   return TT_OK;
 }
 

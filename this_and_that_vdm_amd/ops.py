@@ -595,6 +595,33 @@ def cfg_euler_step_requests(eps, latents, guidance, sigmas, step, requests, cfg,
     return latents
 
 
+def cfg_multistep_step_requests(eps, latents, x0_hist, guidance, sigmas, step, coef, requests, cfg, frames, h, w,
+                                image_guidance_scale=None):
+    """The DPM-Solver++ 2M step (include/ttvdm.h) for R >= 1 requests in one launch: cfg_euler_step_requests' operands plus x0_hist
+    fp32 [R,F,4,h,w] (the previous step's data prediction: read when this step's coefficient is not 0, always rewritten) and coef, one
+    fp32 on the device.  Updates latents and x0_hist in place."""
+    lib = _lib.load()
+    if cfg == 3 and (image_guidance_scale is None or guidance is None):
+        raise ValueError("a CFG batch of 3 needs guidance and image_guidance_scale")
+    if x0_hist.numel() != latents.numel() or x0_hist.dtype != torch.float32 or latents.numel() != requests * frames * 4 * h * w:
+        raise ValueError(f"cfg_multistep_step_requests: latents hold {latents.numel()} and x0_hist {x0_hist.numel()} ({x0_hist.dtype}) "
+                         f"elements, expected fp32 [R,F,4,h,w] each with R = {requests}, F = {frames}, h = {h}, w = {w}")
+    if coef.numel() != 1 or coef.dtype != torch.float32:
+        raise ValueError(f"cfg_multistep_step_requests: coef holds {coef.numel()} values ({coef.dtype}), expected one fp32 (this step's c)")
+    per_request = 0
+    if guidance is not None:
+        if guidance.numel() not in (frames, requests * frames):
+            raise ValueError(f"cfg_multistep_step_requests: guidance holds {guidance.numel()} values, expected [1,F] or [R,F] with "
+                             f"R = {requests}, F = {frames}")
+        per_request = int(requests > 1 and guidance.numel() == requests * frames)
+    check(lib.tt_cfg_multistep_step_requests(_p(eps), eps.stride(0), _p(latents), _p(x0_hist), _p(guidance), per_request,
+                                             float(image_guidance_scale) if cfg == 3 else 0.0, _p(sigmas), step, _p(coef), requests, cfg,
+                                             frames, h, w, _stream()), "tt_cfg_multistep_step_requests")
+    _wrote(latents, "cfg_multistep_step")
+    _wrote(x0_hist, "cfg_multistep_x0")
+    return latents
+
+
 def nchw_to_tokens(src, dtype, ld=None, out=None):
     """[N,C,H,W] contiguous (fp32 or `dtype`) -> token-major `dtype` [N*H*W, ld>=C] (extra columns zero), or into
     ``out`` (a [N*H*W, C] column window of a wider token buffer)."""

@@ -4,7 +4,8 @@ as ONE hipGraph replayed per step.
 
 Per step, on device:   prep (CFG duplicate, x/sqrt(sigma^2+1), channel concat, NCHW->tokens)  ->  time/FiLM rows
   ->  UNet encoder+mid  ->  GestureNet encoder+mid, zero-convs with the UNet skips added in the epilogue
-  ->  UNet decoder  ->  per-frame CFG + v-prediction Euler update of the fp32 latents (in place).
+  ->  UNet decoder  ->  per-frame CFG + v-prediction Euler update of the fp32 latents (in place), or with begin(multistep=...) the
+  DPM-Solver++ 2M update (same schedule, one more latent-sized buffer: the previous step's data prediction).
 Hoisted out of the loop (step-invariant; the reference recomputes them every step):
 context K/V of all 46 cross-attention layers, frame-position embeddings, and the gesture-map latents (the
 pipeline VAE-encodes them once instead of 25 times, reference :652).  The time embedding + FiLM rows of all ResBlocks depend
@@ -52,7 +53,7 @@ class DenoiseLoop:
               added_time_ids: torch.Tensor, guidance_scale: Optional[torch.Tensor], sigmas: torch.Tensor,
               timesteps: torch.Tensor, controlnet_cond: Optional[torch.Tensor] = None, conditioning_scale: float = 1.0,
               controlnet_keep: Optional[Sequence[float]] = None, image_guidance_scale: Optional[float] = None,
-              guess_mode: bool = False):
+              guess_mode: bool = False, multistep: Optional[torch.Tensor] = None):
         """latents [R,F,4,h,w] (already scaled by init_noise_sigma), R independent requests; image_latents [B,F,4,h,w], B = R*C;
         encoder_hidden_states [B,S,D]; added_time_ids [B,3]; guidance_scale [R,F,1,1,1] or [1,F,1,1,1] (all requests), None = no
         CFG (C == 1); sigmas [steps+1], timesteps [steps] (shared by the requests); controlnet_cond gesture latents [F,4,h,w] (all
@@ -63,7 +64,13 @@ class DenoiseLoop:
         Every request is computed as a begin() of its own would (never the reference's cross-request context pairing).
         guess_mode: the 13 residual scales become
         logspace(-1, 0, 13) * conditioning_scale (temporal_controlnet.py:626-630); only without CFG -- the reference's
-        guess-mode + CFG branch (:676-681) concatenates zeros onto an already CFG-sized residual batch and cannot run."""
+        guess-mode + CFG branch (:676-681) concatenates zeros onto an already CFG-sized residual batch and cannot run.
+        multistep: None = the Euler update; a [steps] fp32 tensor (DPMSolverMultistepScheduler.multistep_coefficients) = the
+        DPM-Solver++ 2M update, every step ending in tt_cfg_multistep_step_requests with that step's coefficient (include/ttvdm.h).
+        The previous step's data prediction lives in a static buffer ``x0_hist`` that is never cleared between requests: a step whose
+        coefficient is 0 -- the first of every request -- does not read it.  Latents replaced between steps (a pipeline's
+        callback_on_step_end) leave the history as it is, as diffusers' multistep schedulers do: the next step extrapolates from the
+        data prediction of the latents the loop itself produced."""
         dev = self.unet.device
         b = image_latents.shape[0]
         nr, f, _, h, w = latents.shape
@@ -99,6 +106,12 @@ class DenoiseLoop:
                guidance_scale is not None, self.image_guidance_scale, packs,   # the image scale is baked into the graph
                ops.f32_split(),                                                # ... and so is the TT_F32 product mode (kernel variants)
                None if ops.AUDIT is None else ops.AUDIT.generation)           # ... and the range audit whose statistics launches a captured step holds
+        if multistep is not None:
+            if multistep.numel() != len(timesteps):
+                raise ValueError(f"multistep holds {multistep.numel()} coefficients for {len(timesteps)} steps: expected one per step")
+            if float(multistep.reshape(-1)[0]) != 0.0:
+                raise ValueError("multistep[0] must be 0: the first step of a request has no history to extrapolate from")
+            key += ("multistep",)               # which step kernel a graph ends in; the coefficient values are data, not structure
         if key != self._key:                    # new shapes or new weights: new static buffers, new graph
             self._graph, self._graph_off, self._key, self._static = None, None, key, {}
         self._packs = packs                     # what the FiLM table, the context projections and the graphs below were built from
@@ -116,6 +129,14 @@ class DenoiseLoop:
         self.table = self._static_set("table", torch.stack([sig[:-1], sig[1:], f32(timesteps)], 1))       # [steps, 3]
         self.cur = self._static_set("cur", torch.zeros(3, dtype=torch.float32, device=dev))           # sigma, sigma_next, t
         self.num_steps = self.table.shape[0]
+        self.x0_hist = self.coef_tab = self.coef_cur = None
+        if multistep is not None:
+            # the previous step's data prediction: allocated once per key and left as it is between requests (step 0's coefficient is 0)
+            self.x0_hist = self._static.get("x0_hist")
+            if self.x0_hist is None:
+                self.x0_hist = self._static["x0_hist"] = torch.zeros_like(self.latents)
+            self.coef_tab = self._static_set("coef_tab", f32(multistep).reshape(-1))                      # [steps]
+            self.coef_cur = self._static_set("coef_cur", torch.zeros(1, dtype=torch.float32, device=dev))   # this step's (copied in by step())
         self.film_tab_u = self.film_tab_c = self.film_cur_u = self.film_cur_c = None
         if FILM_TABLE:
             self.film_tab_u = self._static_set("film_tab_u", self.unet.film_table(self.table[:, 2], self.added_time_ids, b))
@@ -260,7 +281,10 @@ class DenoiseLoop:
                     tails.append(done)
         for ev in tails:
             main.wait_event(ev)
-        if g.requests == 1:
+        if self.x0_hist is not None:            # DPM-Solver++ 2M: one kernel for every R (the request form serves R = 1 too)
+            ops.cfg_multistep_step_requests(eps, self.latents, self.x0_hist, self.guidance, self.cur, 0, self.coef_cur, g.requests, g.cfg,
+                                            g.frames, g.h, g.w, self.image_guidance_scale)
+        elif g.requests == 1:
             ops.cfg_euler_step(eps, self.latents, self.guidance, self.cur, 0, g.batch, g.frames, g.h, g.w,
                                self.image_guidance_scale)
         else:
@@ -276,7 +300,7 @@ class DenoiseLoop:
         return st
 
     def step(self):
-        """Advance the latents by one Euler step (asynchronous; call torch.cuda.synchronize() to wait)."""
+        """Advance the latents by one step, Euler or (begin(multistep=...)) DPM-Solver++ 2M (asynchronous; call torch.cuda.synchronize() to wait)."""
         if self.step_index >= self.num_steps:
             raise RuntimeError("denoise loop already finished; call begin() for a new request")
         # begin() evaluated the FiLM rows of ALL steps and the context K/V from the weights of that moment, and the captured graph
@@ -288,6 +312,8 @@ class DenoiseLoop:
             raise RuntimeError("a range audit began or ended after DenoiseLoop.begin(): call begin() again -- a captured step holds the "
                                "statistics launches of the audit it was captured under, or none")
         self.cur.copy_(self.table[self.step_index])
+        if self.coef_cur is not None:
+            self.coef_cur.copy_(self.coef_tab[self.step_index:self.step_index + 1])
         use_cn = self.controlnet is not None and self.keep[self.step_index] != 0.0
         if self.film_cur_u is not None:
             self.film_cur_u.copy_(self.film_tab_u[self.step_index])
@@ -306,8 +332,11 @@ class DenoiseLoop:
         self.step_index += 1
 
     def _capture(self, use_cn: bool):
-        # warm-up on a side stream (allocator + lazily built caches), restoring the latents afterwards
+        # warm-up on a side stream (allocator + lazily built caches), restoring the latents afterwards -- and the multistep history: the
+        # UNet-only graph of a control-guidance window is first captured in the middle of a request, where the replay that follows reads
+        # the data prediction of the step before, not the warm-up's
         keep = self.latents.clone()
+        keep_hist = None if self.x0_hist is None else self.x0_hist.clone()
         records = None if ops.AUDIT is None else ops.AUDIT.snapshot()         # the warm-up pass below is not a step of the request: its
         s = torch.cuda.Stream()                                                # statistics are taken back out of the audit's records
         s.wait_stream(torch.cuda.current_stream())
@@ -318,6 +347,8 @@ class DenoiseLoop:
         with torch.cuda.graph(graph):
             self._launch_step(use_cn)
         self.latents.copy_(keep)
+        if keep_hist is not None:
+            self.x0_hist.copy_(keep_hist)
         if ops.AUDIT is not None:
             ops.AUDIT.restore(records)
         return graph

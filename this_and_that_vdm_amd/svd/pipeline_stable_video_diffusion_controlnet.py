@@ -305,7 +305,7 @@ class _SVDPipelineCore(PipelineBase):
                    controlnet_cond=rq.gesture_latents, conditioning_scale=float(scale),
                    controlnet_keep=keep if controlnet is not None else None,
                    image_guidance_scale=float(image_guidance_scale) if ip2p else None,
-                   guess_mode=bool(guess_mode) and controlnet is not None)
+                   guess_mode=bool(guess_mode) and controlnet is not None, **rq.sampler)
         with self.progress_bar(total=num_inference_steps) as bar:
             for i, t in enumerate(timesteps):
                 loop.step()
@@ -411,7 +411,10 @@ class _SVDPipelineCore(PipelineBase):
                                        width, ehs.dtype, device, generator, latents, scheduler=scheduler)
         guidance = torch.linspace(min_guidance_scale, max_guidance_scale, num_frames).unsqueeze(0).to(device, latents.dtype)
         guidance = append_dims(guidance.repeat(nreq, 1), latents.ndim)
-        return SimpleNamespace(nreq=nreq, num_frames=num_frames, height=height, width=width, do_cfg=do_cfg, ip2p=ip2p, ehs=ehs,
+        # which update the fused loop runs is the scheduler's to say: one with ``multistep_coefficients`` (DPMSolverMultistepScheduler) gets
+        # the DPM-Solver++ 2M step kernel with those coefficients, any other the Euler step -- the loop never calls scheduler.step
+        coefs = getattr(scheduler, "multistep_coefficients", None)
+        return SimpleNamespace(sampler={} if coefs is None else {"multistep": coefs},nreq=nreq, num_frames=num_frames, height=height, width=width, do_cfg=do_cfg, ip2p=ip2p, ehs=ehs,
                                image_latents=image_latents, gesture_latents=gesture_latents, added_time_ids=added_time_ids,
                                timesteps=timesteps, sigmas=scheduler.sigmas, latents=latents, guidance=guidance)
 

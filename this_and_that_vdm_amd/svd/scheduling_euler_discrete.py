@@ -1,7 +1,8 @@
 """EulerDiscreteScheduler as the SVD pipelines use it (diffusers==0.25.1 class, call sites
 svd/pipeline_stable_video_diffusion_controlnet.py:336,583-584,632,709): Karras sigmas, continuous
 timesteps 0.25*ln(sigma), v-prediction Euler step.  Host-side schedule logic; the per-step tensor math
-used by the fused loop lives in tt_prep_model_input / tt_cfg_euler_step."""
+used by the fused loop lives in tt_prep_model_input / tt_cfg_euler_step.  The second sampler, DPM-Solver++ 2M
+(svd/scheduling_dpmsolver_multistep.py), shares this schedule; its step kernel is tt_cfg_multistep_step_requests."""
 from __future__ import annotations
 
 from dataclasses import dataclass
