@@ -154,7 +154,7 @@ __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)
 // 1 / sqrt(var + eps), each rounded to fp32 once, with var = E[x^2] - mean^2 clamped at zero.  Returns the conditioning guard's flag,
 // E[x^2] > ratio * var: beyond it the uncentred variance has lost its digits to the cancellation (norm.hip: GN_GUARD_RATIO) and the
 // caller recomputes the group centred.  The ONE place this arithmetic is written: every statistics route of norm.hip and
-// splitk_epilogue_gn_kernel (gemm_kernel.h; it has no centred pass and ignores the flag) call it.
+// splitk_epilogue_gn_kernel (gemm_splitk.h; it has no centred pass and ignores the flag) call it.
 __device__ __forceinline__ bool gn_group_stat(double a, double b, double cnt, float eps, double ratio, float& mean, float& rstd) {
   const double m = a / cnt;
   double var = b / cnt - m * m;

@@ -21,7 +21,7 @@
 //     columns per lane, 8-byte stores covering 128 contiguous bytes per pixel.
 // LDS-fill traffic per 64 channels of K: one 23..26 KiB patch + 9 W tiles, against 9 x (16 KiB A tile + W tile) before.
 #include <type_traits>
-#include "gemm_kernel.h"
+#include "gemm_params.h"
 
 using namespace ttg;
 

@@ -22,9 +22,12 @@
 //
 // Host side of this file: the per-route predicates (pp_ok, sq320_ok, w320_route, ... -- each with the measurements behind its thresholds),
 // ONE resolver that sequences them (wanted_route / granted_route -> Route), and five short entry points that read its answer.
-// The tile shapes live in one table (TT_GEMM_TILES in gemm_kernel.h); the tuning knobs in one struct read once (knobs()).
+// The tile shapes live in one table (TT_GEMM_TILES in gemm_tiles.h); the tuning knobs in one struct read once (knobs()).
 #include <stdlib.h>
-#include "gemm_kernel.h"
+#include "gemm_params.h"
+#include "gemm_splitk.h"
+#include "gemm_sq320.h"
+#include "gemm_tiles.h"
 
 namespace ttg {
 // per-dtype instantiation units (gemm_inst_*.hip)
@@ -69,7 +72,7 @@ int env_int(const char* name, int dflt) { const char* e = getenv(name); return e
 int big_tile_bits(int on) { return on == 0 ? 0 : (on == 2 ? 1 : (on == 3 ? 11 : (on == 4 ? 7 : 15))); }
 struct Knobs {
   int forced_cfg = env_int("TT_GEMM_CFG", -1);                    // tt_gemm_set_tile_override
-  int group_m = env_int("TT_GEMM_GROUP_M", 0);                    // tuning switch: <rows> overrides the group height of the tile order (gemm_kernel.h: launch_cfg picks it otherwise)
+  int group_m = env_int("TT_GEMM_GROUP_M", 0);                    // tuning switch: <rows> overrides the group height of the tile order (gemm_launch.h: tile_params picks it otherwise)
   int forced_split = env_int("TT_GEMM_SPLITK", -1);
   int deep = env_int("TT_GEMM_DEEP", 1);
   int small64 = env_int("TT_GEMM_SMALL64", 2);
@@ -323,7 +326,8 @@ Plan plan_for(const TtGemmArgs* a) {
     // (three / two tiles in flight instead of one) 112.7 / 112.0; x 32 with a 3-deep ring (96 KiB: one workgroup per CU) 135.5; 8 waves
     // as 4 x 2 / 2 x 4 (wave tiles 32 x 64 / 64 x 32 at a 128-register budget) 123.4 / 234.2; 128 x 64 x 32, 3-deep 127.7.
     // (4 waves as 4 x 1 -- every A fragment converted by one wave instead of two -- 105.1 -> 104.0 ms, within the noise; as 1 x 4 149.6.)
-    // Where the time goes (ablation builds `make variant DEFS=-DTT_SPLIT_ABL=1|2|3`, wrong numbers, one call): 105.4 ms as built; without
+    // Where the time goes (ablation builds `make variant DEFS=-DTT_SPLIT_ABL=1|2|3`, wrong numbers, one call; the flag ended with commit 83d2c66,
+    // the last that builds it): 105.4 ms as built; without
     // any conversion 74.8; with one MFMA per product block instead of three 75.1; with neither 65.9 -- conversions and the two extra MFMAs
     // cost ~9 ms each on their own and ~40 ms together: inside one wave they run back to back (the fragment consumers are pinned by
     // sched_barrier: the raw-read hazard of gemm_kernel.h), so the matrix pipe idles while a wave converts.
@@ -614,7 +618,7 @@ extern "C" int tt_gemm_plan(const TtGemmArgs* a, int32_t cfg[7]) {
   return TT_OK;
 }
 
-// The instance of the route's kernel: each family's selector (gemm_kernel.h) is asked what its launcher asks it, with the fields
+// The instance of the route's kernel: each family's selector (gemm_params.h, gemm_tiles.h) is asked what its launcher asks it, with the fields
 // fill_params copies into GemmP unchanged.  A two-part problem: the head's kernel; a split plan: the main kernel (not the reduction pass).
 extern "C" int tt_gemm_kernel(const TtGemmArgs* a, char* name, int32_t cap) {
   Route r;

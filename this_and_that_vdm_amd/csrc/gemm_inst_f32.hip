@@ -1,5 +1,5 @@
-// instantiation unit: the TT_F32 tile configurations (TT_GEMM_TILES_F32 in gemm_kernel.h)
-#include "gemm_kernel.h"
+// instantiation unit: the TT_F32 tile configurations (TT_GEMM_TILES_F32 in gemm_tiles.h)
+#include "gemm_launch.h"
 namespace ttg {
 template <>
 void launch<f32_tag>(GemmP& p, int cfg, hipStream_t st) {

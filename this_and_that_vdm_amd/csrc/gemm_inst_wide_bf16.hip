@@ -1,5 +1,5 @@
-// instantiation unit: the wide (windowed) variants of tt_gemm's tiled template for one storage type (TT_GEMM_WIDE_TILES in gemm_kernel.h)
-#include "gemm_kernel.h"
+// instantiation unit: the wide (windowed) variants of tt_gemm's tiled template for one storage type (TT_GEMM_WIDE_TILES in gemm_tiles.h)
+#include "gemm_launch.h"
 namespace ttg {
 void launch_wide_bf16(GemmP& p, int cfg, hipStream_t st) {
   using Tag = bf16_tag;

@@ -25,7 +25,7 @@
 //     through a wave-private 4 KiB strip and stored as 16 bytes per lane (plain: full 128-byte lines).
 #include <stdlib.h>
 #include <type_traits>
-#include "gemm_kernel.h"
+#include "gemm_params.h"
 
 #ifndef TT_PP_GEGLU_STORE_AUX
 #define TT_PP_GEGLU_STORE_AUX 0      // cache policy of the GEGLU output stores (aux: 2 = nt); measured, see DESIGN.md 6.R4

@@ -30,7 +30,8 @@
 // issues its MFMAs while the other reads fragments and issues DMA.
 #include <stdlib.h>
 #include <type_traits>
-#include "gemm_kernel.h"
+#include "gemm_params.h"
+#include "gemm_splitk.h"
 
 #ifndef TT_W320_A_AUX
 #define TT_W320_A_AUX 0      // cache policy of the A stream's LDS-DMA (aux: 2 = nt); measured: see DESIGN.md 6.R4
@@ -223,7 +224,7 @@ __device__ __forceinline__ void w3_epilogue_rows(const GemmP& p, const f32x16_t 
   const __amdgpu_buffer_rsrc_t r_bl = make_rsrc(p.blend, BLEND ? p.blend_bytes : 0);
   const float one_m_alpha = 1.0f - alpha;
   const int rv_rows = FILM ? p.rowvec_rows : 1;
-  // STATS (GemmP.stats): column sums of the stored values (gemm_kernel.h, colstat_strip).  Compile-time like the operand variants: a
+  // STATS (GemmP.stats): column sums of the stored values (gemm_params.h, colstat_strip).  Compile-time like the operand variants: a
   // uniform run-time `if` inside the pass loops turns the straight-line epilogue into basic blocks, and hipcc then drains vmcnt
   // between them (measured: +4 us on a 23 us launch with the run-time form)
   const bool parity = FILM && p.rowvec_mod == 2 && rv_rows == 1;             // even / odd rows: two vectors, the row's parity selects
@@ -363,7 +364,7 @@ template <typename T> __device__ __forceinline__ void w3_stats_tile(const GemmP&
 
 // ---- split-K form of the above for ONE fragment row of gemm_w320h_kernel (p.splitk > 1): the fp32 partial sums of K slice `split`
 // (after the exchange of the two in-slab K halves) go to the workspace slab ws[split][m][n] through the same strip transposition,
-// 16 bytes per lane and 4 rows x 256 contiguous bytes per store instruction; splitk_epilogue_kernel (gemm_kernel.h) adds the slabs
+// 16 bytes per lane and 4 rows x 256 contiguous bytes per store instruction; splitk_epilogue_kernel (gemm_splitk.h) adds the slabs
 // in a fixed order and runs the full epilogue.  The slab's descriptor ends at row m: rows beyond it are dropped by the bounds check.
 __device__ __forceinline__ void w3_partial_row(const GemmP& p, const f32x16_t (&acc)[5], char* ebuf, int mb, int ncol0, int lane, int split,
                                                const f32x16_t (&give)[5], char* xbuf, const char* pbuf) {
