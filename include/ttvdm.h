@@ -744,6 +744,71 @@ int tt_tensor_stats_launch(int32_t dtype, int32_t* max_grid /* host */, int32_t*
 int tt_tensor_stats(const void* x, int64_t ldx, int64_t rows, int32_t cols, int32_t dtype, const float* thr /* host [4] */,
                     TtTensorStats* rec, void* ws, int64_t ws_bytes, int32_t accumulate, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * tt_frame_metrics: how far two videos are from each other, frame by frame -- the sums behind MSE / PSNR and SSIM (Wang, Bovik,
+ * Sheikh, Simoncelli 2004, as skimage, torchmetrics and pytorch-msssim compute it) of frames a and b that are on the device
+ * already, e.g. from tt_frames_out.  Additive: the ABI version is unchanged.
+ *
+ *   a, b   [n, h, w, ch] contiguous NHWC, 1 <= ch <= 4, both of `kind`: 1 uint8, 0 fp32 (tt_frames_out's codes); aligned to their
+ *          element, nothing more: a pointer offset by whole frames is served like any other
+ *   rec    n records on the DEVICE, one per frame, 8-byte aligned.  TtFrameMetricsRecord -- 104 bytes, no padding:
+ *            [ 0] double sse[4]       per channel c:  sum over the frame of (a - b)^2
+ *            [32] double ssim_sum[4]  per channel:  sum over the windows of ssim
+ *            [64] double cs_sum[4]    per channel:  sum over the windows of cs
+ *            [96] int64  count        windows per channel, (h - 10) (w - 10); 0 with TT_METRICS_SSE_ONLY
+ *          SUMS, not means: the host divides.  Channels ch .. 3 hold 0.
+ *   sse    uint8: integer differences, squares and sums; the record holds the exact integer (below 2^53 for any frame of fewer than
+ *          2^37 pixels, so the fp64 is exact).  fp32: d = (double)a - (double)b, d d and the sums in fp64.
+ *   window g[k] = exp(-(k - 5)^2 / 4.5) / S for k = 0 .. 10, S their sum in index order: the 11-tap Gaussian of sigma 1.5, normalised,
+ *          separable, in fp64 (tt_frame_metrics_window copies the 11 doubles the kernel uses to the caller).
+ *          G*x at window (y, x), "valid" windows only (0 <= y < h - 10, 0 <= x < w - 10), no padding:
+ *            row[r][x] = g[0] v[r][x] + g[1] v[r][x + 1] + .. + g[10] v[r][x + 10]         (left to right, starting from the first product)
+ *            (G*v)[y][x] = g[0] row[y][x] + .. + g[10] row[y + 10][x]                       (likewise)
+ *          for v = a, b, a a, a b, b b (the products formed in fp64 per pixel).
+ *   ssim   C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range (255 for uint8 frames, 1 for fp32 frames in [0, 1]: always passed)
+ *            mu_a = G*a, mu_b = G*b;  maa = mu_a mu_a, mbb = mu_b mu_b, mab = mu_a mu_b
+ *            s_aa = G*(a a) - maa,  s_bb = G*(b b) - mbb,  s_ab = G*(a b) - mab
+ *            cs   = (2 s_ab + C2) / ((s_aa + s_bb) + C2)
+ *            ssim = ((2 mab + C1) / ((maa + mbb) + C1)) cs
+ *          ALL of it in fp64, every operation rounded on its own (no contraction): with fp32 moments the cancellation in
+ *          G*(x x) - mu^2 costs up to 5.5e-4 per window on a bright flat region (x x reaches 65 025, C2 is 58.5).  Identical frames
+ *          give cs == ssim == 1.0 in every window, hence ssim_sum == count exactly.
+ *   flags  TT_METRICS_SSE_ONLY: sse only -- no window work, ssim_sum = cs_sum = 0, count = 0, and frames smaller than 11 x 11 are served.
+ *
+ * Launches: TWO.  One workgroup of TT_METRICS_BLOCK lanes per (frame, tile of TT_METRICS_TILE x TT_METRICS_TILE windows), all
+ * channels of the tile: the tile's pixels with their 10-pixel halo of both operands go to LDS (16-byte loads along the contiguous
+ * w ch axis wherever an aligned 16 bytes lies inside the tile's row, single elements at its ends), then per channel a horizontal and
+ * a vertical pass in fp64.  A pixel's squared difference is counted by the tile that holds it among its first TT_METRICS_TILE rows and
+ * columns (the last tile of an axis: to the frame's edge).  Each workgroup sums in a fixed shape and writes 12 doubles to ws; the
+ * second launch (one workgroup per frame) adds the tiles' partial sums IN TILE ORDER.  No atomics, no flags between workgroups:
+ * the same call on the same inputs gives the same bits every time, and a frame's record does not depend on the other frames of the
+ * call.  Element indices are 64-bit.  No allocation, no synchronisation: capturable.
+ * ws: tt_frame_metrics_ws_bytes(n, h, w, flags) bytes, 8-byte aligned (0 for arguments tt_frame_metrics refuses).
+ * tt_frame_metrics_launch reports (TT_METRICS_TILE, TT_METRICS_BLOCK, elements per 16-byte load of `kind`) for tests and tools.
+ * Refused before the first HIP call.  TT_EINVAL: null a / b / rec; n <= 0; h or w <= 0; ch outside 1 .. 4; an unknown kind; unknown
+ * flag bits; h < 11 or w < 11 without TT_METRICS_SSE_ONLY; data_range <= 0 or not finite; a / b off their element size, rec or ws off
+ * an 8-byte boundary; a workspace that is missing or too small.  TT_EUNSUPPORTED: more than 2^31 - 1 tiles in one call.
+ *
+ * tt_frames_pool2: one level of the MS-SSIM pyramid (Wang, Simoncelli, Bovik 2003), the 2 x 2 mean:
+ *   src [n, h, w, ch] (kind 1 uint8 / 0 fp32) -> dst fp32 [n, h / 2, w / 2, ch],
+ *   dst[f][y][x][c] = 0.25f * ((x00 + x01) + (x10 + x11)) in fp32, in that order (xij = src[f][2 y + i][2 x + j][c]).
+ * For frames that began as uint8, four levels are exact: every value stays a multiple of 2^-8 below 2^8.  One launch.
+ * TT_EINVAL: null src / dst; n, h or w <= 0; h or w odd; ch outside 1 .. 4; an unknown kind; fp32 src or dst off a 4-byte boundary. */
+#define TT_METRICS_WIN 11
+#define TT_METRICS_TILE 16
+#define TT_METRICS_BLOCK 256
+#define TT_METRICS_SSE_ONLY 1
+typedef struct TtFrameMetricsRecord {
+  double sse[4], ssim_sum[4], cs_sum[4];
+  int64_t count;
+} TtFrameMetricsRecord;
+int tt_frame_metrics_window(double* g /* host [TT_METRICS_WIN] */);
+int tt_frame_metrics_launch(int32_t kind, int32_t* tile /* host */, int32_t* block /* host */, int32_t* elems_per_load /* host */);
+int64_t tt_frame_metrics_ws_bytes(int32_t n, int32_t h, int32_t w, int32_t flags);
+int tt_frame_metrics(const void* a, const void* b, int32_t kind, int32_t n, int32_t h, int32_t w, int32_t ch, double data_range,
+                     int32_t flags, TtFrameMetricsRecord* rec, void* ws, int64_t ws_bytes, tt_stream_t stream);
+int tt_frames_pool2(const void* src, int32_t kind, int32_t n, int32_t h, int32_t w, int32_t ch, float* dst, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,13 @@ class TtTensorStats(C.Structure):
     ]
 
 
+class TtFrameMetricsRecord(C.Structure):
+    """The device record of tt_frame_metrics, one per frame: 104 bytes, the field order and offsets of include/ttvdm.h."""
+    _fields_ = [("sse", C.c_double * 4), ("ssim_sum", C.c_double * 4), ("cs_sum", C.c_double * 4), ("count", C.c_int64)]
+
+
+TT_METRICS_SSE_ONLY = 1
+
 _i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
 # name -> (restype, argtypes): every symbol include/ttvdm.h declares
@@ -166,6 +173,12 @@ SIGNATURES = {
     "tt_tensor_stats_ws_bytes": (_i64, [_i64, _i32, _i32]),
     "tt_tensor_stats_launch": (C.c_int, [_i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tt_tensor_stats": (C.c_int, [_vp, _i64, _i64, _i32, _i32, C.POINTER(C.c_float), _vp, _vp, _i64, _i32, _vp]),
+    # two videos compared on the device: the sums behind PSNR / SSIM per frame, and the MS-SSIM pyramid's 2 x 2 mean (additive as well)
+    "tt_frame_metrics_window": (C.c_int, [C.POINTER(C.c_double)]),
+    "tt_frame_metrics_launch": (C.c_int, [_i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tt_frame_metrics_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "tt_frame_metrics": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _i32, _vp, _vp, _i64, _vp]),
+    "tt_frames_pool2": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -1030,3 +1030,75 @@ def tensor_stats(x: torch.Tensor, *, thresholds=None, out: Optional[torch.Tensor
     check(lib.tt_tensor_stats(x.data_ptr() if rows else None, ld, rows, cols, code, thr, out.data_ptr() + slot * STATS_BYTES, _p(ws), need,
                               int(bool(accumulate)), _stream()), "tt_tensor_stats")
     return out[slot * STATS_BYTES:(slot + 1) * STATS_BYTES]
+
+
+# ---- two videos compared on the device (tt_frame_metrics / tt_frames_pool2; metrics.py turns the records into PSNR / SSIM / MS-SSIM)
+METRICS_BYTES = C.sizeof(_lib.TtFrameMetricsRecord)
+
+
+def _frames_kind(x: torch.Tensor, what: str) -> int:
+    if x.dtype == torch.uint8:
+        return 1
+    if x.dtype == torch.float32:
+        return 0
+    raise RuntimeError(f"{what}: uint8 or float32 NHWC frames, got {x.dtype}")
+
+
+def frame_metrics_window():
+    """the 11 fp64 weights of the SSIM window as the kernel uses them (Gaussian, sigma 1.5, normalised)"""
+    g = (C.c_double * 11)()
+    check(_lib.load().tt_frame_metrics_window(g), "tt_frame_metrics_window")
+    return list(g)
+
+
+def frame_metrics_launch(dtype: torch.dtype):
+    """(windows per tile edge, lanes per workgroup, elements per 16-byte load of `dtype`): the constants tt_frame_metrics launches with"""
+    kind = 1 if dtype == torch.uint8 else 0
+    t, b, e = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(_lib.load().tt_frame_metrics_launch(kind, C.byref(t), C.byref(b), C.byref(e)), "tt_frame_metrics_launch")
+    return t.value, b.value, e.value
+
+
+def frame_metrics(a: torch.Tensor, b: torch.Tensor, data_range=None, sse_only: bool = False, out: Optional[torch.Tensor] = None):
+    """Frames a and b, [N, H, W, C] contiguous NHWC (C <= 4), both uint8 or both float32 (what ``frames_out`` writes) -> N
+    TtFrameMetricsRecord records (include/ttvdm.h) as a uint8 device tensor [N, METRICS_BYTES]: per frame and channel the sum of squared
+    differences and the sums of ssim and cs over the (H - 10) (W - 10) windows of the 11-tap Gaussian, all in fp64.  data_range: the L of
+    C1 = (0.01 L)^2, C2 = (0.03 L)^2 (default 255 for uint8, 1 for float32).  sse_only: no window work (frames below 11 x 11 are
+    served).  ``out``: a contiguous uint8 tensor of N records to write instead of a new one.  Asynchronous on the current stream and
+    capturable; ``metrics.compare_frames`` reads the records after one device-to-host copy."""
+    lib = _lib.load()
+    _p(a), _p(b)
+    kind = _frames_kind(a, "frame_metrics")
+    if a.dim() != 4 or a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
+        raise RuntimeError(f"frame_metrics: two [N, H, W, C] tensors of one shape, dtype and device, got {tuple(a.shape)} {a.dtype} and "
+                           f"{tuple(b.shape)} {b.dtype}")
+    if not (a.is_contiguous() and b.is_contiguous()):
+        raise RuntimeError("frame_metrics: contiguous NHWC frames")
+    n, h, w, ch = a.shape
+    if data_range is None:
+        data_range = 255.0 if kind else 1.0
+    flags = _lib.TT_METRICS_SSE_ONLY if sse_only else 0
+    if out is None:
+        out = torch.empty((n, METRICS_BYTES), dtype=torch.uint8, device=a.device)
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != a.device or out.numel() != n * METRICS_BYTES:
+        raise RuntimeError(f"frame_metrics: out must be a contiguous uint8 tensor on {a.device} of {n} records ({METRICS_BYTES} bytes each)")
+    need = lib.tt_frame_metrics_ws_bytes(n, h, w, flags)
+    ws = _workspace(need, a.device) if need else None
+    check(lib.tt_frame_metrics(_p(a), _p(b), kind, n, h, w, ch, float(data_range), flags, _p(out), _p(ws), need, _stream()), "tt_frame_metrics")
+    _wrote(out, "frame_metrics")
+    return out.view(n, METRICS_BYTES)
+
+
+def frames_pool2(x: torch.Tensor):
+    """[N, H, W, C] uint8 or float32 NHWC frames (H, W even) -> float32 [N, H / 2, W / 2, C], the 2 x 2 mean
+    ``0.25f * ((x00 + x01) + (x10 + x11))`` in fp32: one level of the MS-SSIM pyramid (tt_frames_pool2)."""
+    lib = _lib.load()
+    _p(x)
+    kind = _frames_kind(x, "frames_pool2")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise RuntimeError(f"frames_pool2: contiguous [N, H, W, C] frames, got {tuple(x.shape)}")
+    n, h, w, ch = x.shape
+    out = torch.empty((n, h // 2, w // 2, ch), dtype=torch.float32, device=x.device)
+    check(lib.tt_frames_pool2(_p(x), kind, n, h, w, ch, _p(out), _stream()), "tt_frames_pool2")
+    _wrote(out, "frames_pool2")
+    return out

@@ -7,10 +7,14 @@
       on the loop's shapes (median of --iters launches between events).  Prints one JSON line; --out writes it to a file as well.
   (b) Solver accuracy (--accuracy tiny | full, or --checkpoint DIR).  In a reference-precision mode (--dtype f32: TT_F32, or split16),
       one request from one noise tensor: Euler at 25 steps and 2M at 12, 15, 20 and 25 steps, each against a 2M run of 200 steps.
-      Reports the relative L2 distance of every candidate's final latents to that fine-step run.  A report, not an assertion.
+      Reports the relative L2 distance of every candidate's final latents to that fine-step run, and next to it the distance in
+      PICTURE space: every candidate's final latents and the fine-step solve's are decoded by the native AutoencoderKLTemporalDecoder
+      (synthetic fill, or the checkpoint's vae/), exported with ops.frames_out(kind=1), and compared with metrics.compare_frames: psnr,
+      ssim and ms_ssim (null where the frames are smaller than MS-SSIM's 176 pixels) to the fine-step video.  A report, not an assertion.
 
 What (b) measures on synthetic (hash-filled) weights is how fast each solver converges on THAT network's ODE: solver accuracy only.  It
-says nothing about pictures.  Nobody has evaluated picture quality at fewer steps on trained This&That weights; the output of (b) says
+says nothing about pictures -- the picture-space columns included: a hash-filled decoder maps latents to noise-like frames, so they
+restate the solver's error through another synthetic network.  Nobody has evaluated picture quality at fewer steps on trained This&That weights; the output of (b) says
 so unless it ran on a checkpoint.  Needs a GPU: there is no CPU fallback."""
 import argparse
 import json
@@ -105,8 +109,17 @@ def cost(a, dev):
                 finite_output=bool(torch.isfinite(loops["2m"].result()).all().item()), kernel_source_sha16=bench.csrc_hash())
 
 
-def accuracy(a, dev):
+def decoded_frames(vae, latents, chunk=7):
+    """final latents [1, F, 4, h, w] -> uint8 NHWC frames [F, 8h, 8w, 3] on the device, as the pipelines' "pil" output holds them"""
     from this_and_that_vdm_amd import ops
+    lat = latents[0].to(torch.float32) / vae.config.scaling_factor
+    return torch.cat([ops.frames_out(vae.decode(lat[i:i + chunk], num_frames=min(chunk, lat.shape[0] - i)).sample, 1)
+                      for i in range(0, lat.shape[0], chunk)], 0)
+
+
+def accuracy(a, dev):
+    from this_and_that_vdm_amd import metrics, ops
+    from this_and_that_vdm_amd.svd.autoencoder_kl_temporal_decoder import AutoencoderKLTemporalDecoder
     from this_and_that_vdm_amd.svd.denoise import DenoiseLoop
     from this_and_that_vdm_amd.svd.temporal_controlnet import ControlNetModel
     from this_and_that_vdm_amd.svd.unet_spatio_temporal_condition import UNetSpatioTemporalConditionModel
@@ -115,14 +128,17 @@ def accuracy(a, dev):
     if a.checkpoint:
         unet = UNetSpatioTemporalConditionModel.from_pretrained(a.checkpoint, subfolder="unet", torch_dtype=torch.float32)
         cn = ControlNetModel.from_pretrained(a.checkpoint, subfolder="controlnet", torch_dtype=torch.float32)
+        vae = AutoencoderKLTemporalDecoder.from_pretrained(a.checkpoint, subfolder="vae", torch_dtype=torch.float32)
     else:
         with torch.device(dev):
             kw = dict(TINY) if a.accuracy == "tiny" else dict(num_attention_heads=(5, 10, 20, 20))
             unet = UNetSpatioTemporalConditionModel(num_frames=size["frames"], **kw)
             cn = ControlNetModel(**(kw if a.accuracy == "tiny" else {}))
+            vae = AutoencoderKLTemporalDecoder()
         fill_parameters_(unet, "unet.")
         fill_parameters_(cn, "controlnet.")
-    for m in (unet, cn):
+        fill_parameters_(vae, "vae.")
+    for m in (unet, cn, vae):
         m.to(device=dev, dtype=torch.float32).eval()
         m.compute_dtype = torch.float32                           # TT_F32: exact-fp32 products, or split16 below
     was = ops.f32_split()
@@ -132,19 +148,27 @@ def accuracy(a, dev):
                                                          seed=a.seed).items()}
         run = lambda name, steps: DenoiseLoop(unet, cn, use_graph=True).begin(**begin_args(inp, name, steps, True)).run().double().clone()
         fine = run("2m", FINE_STEPS)
+        fine_frames = decoded_frames(vae, fine)
+        ms_ok = all(v % 16 == 0 and v >= metrics.MS_SSIM_MIN_SIZE for v in fine_frames.shape[1:3])
         rows = []
         for name, steps in CANDIDATES:
             got = run(name, steps)
+            pic = metrics.compare_frames(decoded_frames(vae, got), fine_frames, ms_ssim=ms_ok)
             rows.append(dict(sampler=name, steps=steps, rel_l2_to_fine=float((got - fine).norm() / fine.norm()),
+                             psnr_to_fine=pic.to_dict()["psnr"], ssim_to_fine=pic.ssim, ms_ssim_to_fine=pic.to_dict()["ms_ssim"],
                              finite=bool(torch.isfinite(got).all().item())))
     finally:
         ops.set_f32_split(was)
     weights = f"checkpoint {a.checkpoint}" if a.checkpoint else f"synthetic ({a.accuracy})"
     return dict(tool="sampler_bench", part="accuracy", weights=weights, mode="TT_F32 " + ("split16" if a.dtype == "split16" else "exact fp32"),
-                latents=[1, size["frames"], 4, size["h"], size["w"]], reference=f"2M at {FINE_STEPS} steps on the same noise", rows=rows,
-                says="distance of the final latents to a fine-step solve of the same ODE" + (
-                    "" if a.checkpoint else ": synthetic weights, solver accuracy only -- nothing about picture quality, which nobody has "
-                                            "evaluated at fewer steps on trained weights"))
+                latents=[1, size["frames"], 4, size["h"], size["w"]], frames=list(fine_frames.shape),
+                reference=f"2M at {FINE_STEPS} steps on the same noise", rows=rows,
+                picture_columns="psnr / ssim / ms_ssim of the decoded uint8 frames (native temporal VAE decoder in the same TT_F32 mode, "
+                                "ops.frames_out(kind=1), metrics.compare_frames) to the fine-step solve's decoded frames" + (
+                                    "" if ms_ok else "; ms_ssim null: the frames are smaller than its 176 pixels"),
+                says="distance of the final latents, and of the frames decoded from them, to a fine-step solve of the same ODE" + (
+                    "" if a.checkpoint else ": synthetic weights (UNet, ControlNet and decoder), solver accuracy only -- nothing about picture "
+                                            "quality, which nobody has evaluated at fewer steps on trained weights"))
 
 
 def main():
