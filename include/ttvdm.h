@@ -809,6 +809,84 @@ int tt_frame_metrics(const void* a, const void* b, int32_t kind, int32_t n, int3
                      int32_t flags, TtFrameMetricsRecord* rec, void* ws, int64_t ws_bytes, tt_stream_t stream);
 int tt_frames_pool2(const void* src, int32_t kind, int32_t n, int32_t h, int32_t w, int32_t ch, float* dst, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GIF export: a video's frames quantised to 256-colour palettes with the per-pixel work on the device (this_and_that_vdm_amd/export.py
+ * drives it).  Two kernels (tt_color_hist, tt_palette_map) and two host routines (tt_palette_median_cut, tt_gif_lzw; plain C++, they
+ * touch no device).  Integers only, everywhere: every call gives the same bits.  Additive: the ABI version is unchanged.
+ *
+ * TtColorBin -- 16 bytes: uint32 count, sum_r, sum_g, sum_b: how many pixels a bin (or a palette entry) holds and the sums of their
+ * FULL 8-bit channel values.  A sum is at most 255 count, so all four fit while count <= TT_GIF_MAX_PIXELS = (2^32 - 1) / 255 =
+ * 16 843 009 pixels per histogram (14 frames of 576 x 1024 are 8.3 M); more than that is refused, never wrapped.
+ *
+ * tt_color_hist: frames [n, h, w, 3] uint8 NHWC on the device -> nhist histograms of TT_GIF_BINS = 32 768 TtColorBin each on the
+ * device, nhist == n (one per frame) or nhist == 1 (one over all frames).  A pixel (r, g, b) belongs to
+ *   bin = (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3)
+ * and adds (1, r, g, b) to it.  The call zeroes hist first (a memset on the stream), then ONE launch: a workgroup of TT_GIF_BLOCK lanes
+ * walks a contiguous run of one histogram's pixels, 16 pixels (three aligned 16-byte loads) per lane and trip with single pixels at the
+ * run's two ends, and adds into a PRIVATE table in LDS of TT_GIF_HIST_SLOTS slots {bin, count, sum_r, sum_g, sum_b}: a pixel's slot is a
+ * hash of its bin, claimed by compare-and-swap on the slot's bin word; a pixel whose slot another bin holds adds to hist directly.  At
+ * the end of its run the workgroup adds its occupied slots to hist.  All adds are integer atomics (LDS, then global): they commute, so
+ * which pixels took which way changes no bit.  (All 32 768 bins private would take 512 KB of LDS against the CU's 160 KB; counts alone
+ * 128 KB.  A natural frame fills a few hundred bins; a frame of ONE colour sends every pixel of a workgroup to one LDS word -- 64 adds
+ * of one wave instruction serialise in the LDS, not in the L2 -- and the workgroup's whole run reaches hist as four global adds.)
+ * TT_EINVAL: null frames / hist; n, h or w <= 0; ch != 3; nhist neither n nor 1; hist off a 16-byte boundary.  TT_EUNSUPPORTED: more
+ * than TT_GIF_MAX_PIXELS pixels per histogram; more than 65 535 histograms.
+ *
+ * tt_palette_map: frames as above, palettes [npal, 256, 3] uint8 on the device (npal == n: frame f uses palette f; npal == 1: all
+ * frames use the one), ncolors [npal] on the HOST, each 1 .. 256 -> indices [n, h, w] uint8 on the device,
+ *   index = the k in 0 .. ncolors - 1 that minimises (r - R_k)^2 + (g - G_k)^2 + (b - B_k)^2, the LOWEST such k on a tie
+ * (entries ncolors .. 255 are never read as candidates); sse [n] uint64 on the device, per frame the sum of that minimum over its
+ * pixels; and, when stats is not NULL, stats [npal, 256] TtColorBin on the device: per palette and entry (count, sum_r, sum_g, sum_b) of
+ * the pixels assigned to it (entries >= ncolors hold zeros) -- the input of a Lloyd step.  The call zeroes sse and stats, then ONE launch
+ * for all frames: grid (runs of a frame, n); every lane keeps 4 pixels in registers and walks the palette ONCE for them; the palette
+ * is the same for every lane of a workgroup, so its dwords are read through uniform (scalar) loads, four entries per three dwords, and
+ * unpacked on the scalar unit; ncolors travel as kernel arguments (hence at most TT_GIF_MAX_PALETTES palettes).  Per-entry sums go to a
+ * 4 KB table in LDS and from there to stats, the squared error through a wave and workgroup reduction to one global add per workgroup;
+ * integer atomics throughout.
+ * TT_EINVAL: null frames / palettes / ncolors / indices / sse; n, h or w <= 0; ch != 3; npal neither n nor 1; an ncolors outside
+ * 1 .. 256; palettes off a 4-byte, sse off an 8-byte, stats off a 16-byte boundary.  TT_EUNSUPPORTED: more than TT_GIF_MAX_PALETTES
+ * palettes, more than 65 535 frames, or (with stats) more than TT_GIF_MAX_PIXELS pixels per palette.
+ * Both are refused before the first HIP call; no allocation, no synchronisation.
+ *
+ * tt_palette_median_cut (host): one histogram (TT_GIF_BINS TtColorBin, host memory) -> at most `colors` (1 .. 256) palette entries.
+ * A bin's coordinates are (r5, g5, b5) = (bin >> 10, (bin >> 5) & 31, bin & 31); a bin is occupied when its count is not 0.
+ *   A box is a set of occupied bins; its count is the sum of theirs.  Box 0 holds all occupied bins.
+ *   While there are fewer than `colors` boxes and some box holds more than one occupied bin:
+ *     1. take the box with the largest count among those that hold more than one bin; on a tie the one created first (lowest index);
+ *     2. the axis: the largest extent, max - min coordinate over the box's bins; ties go to R, then G, then B;
+ *     3. t = the smallest coordinate on that axis for which 2 * (count of the box's pixels at coordinates <= t) >= the box's count;
+ *     4. if t is the box's maximum coordinate on the axis, t = the next lower coordinate that one of the box's bins has;
+ *     5. bins with coordinate <= t stay in the box (it keeps its index), the others become a new box with the next index.
+ *   Entry k, per channel: (2 sum + count) / (2 count), integer division, over box k -- the mean of the box's PIXELS rounded half up,
+ *   not a bin centre.  Hence a frame whose colours fall one per bin into at most `colors` bins is reproduced exactly.
+ * palette: host [256][3], entries ncolors_out .. 255 are written as zeros.  bin_box (may be NULL): host [TT_GIF_BINS], the box index
+ * of every occupied bin, -1 for the others.  TT_EINVAL: a null pointer, colors outside 1 .. 256, a histogram without a pixel.
+ *
+ * tt_gif_lzw (host): indices [npix] (each below 2^min_code_size; min_code_size 2 .. 8) -> the image data of one GIF frame (GIF89a,
+ * appendix F): the min-code-size byte, data sub-blocks of at most 255 bytes, the block terminator 0.  Codes are packed from the least
+ * significant bit.  The stream starts with a clear code; the width starts at min_code_size + 1 and grows to 12 as the table does (one
+ * bit more from the code after the entry 2^width was made); when the table is full (entry 4095 made) the next code is followed by a
+ * clear code and the table and width start over; the end-of-information code closes the stream.  out holds cap bytes:
+ * tt_gif_lzw_bound is enough for any input of npix indices (12 bits per index and per clear code, at most one clear code per 2048
+ * indices, plus the sub-block framing); nbytes_out receives the bytes written.  TT_EINVAL: a null pointer, npix <= 0, min_code_size
+ * outside 2 .. 8, an index that does not fit it, cap too small (nothing beyond out[cap - 1] is ever written). */
+#define TT_GIF_BINS 32768
+#define TT_GIF_MAX_PIXELS 16843009
+#define TT_GIF_MAX_PALETTES 1024
+#define TT_GIF_BLOCK 256
+#define TT_GIF_HIST_SLOTS 2048
+typedef struct TtColorBin {
+  uint32_t count, sum_r, sum_g, sum_b;
+} TtColorBin;
+int tt_color_hist(const void* frames, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t nhist, TtColorBin* hist, tt_stream_t stream);
+int tt_palette_map(const void* frames, int32_t n, int32_t h, int32_t w, int32_t ch, const void* palettes, int32_t npal,
+                   const int32_t* ncolors /* host [npal] */, uint8_t* indices, uint64_t* sse, TtColorBin* stats, tt_stream_t stream);
+int tt_palette_median_cut(const TtColorBin* hist /* host */, int32_t colors, uint8_t* palette /* host [256][3] */,
+                          int32_t* ncolors_out /* host */, int32_t* bin_box /* host [TT_GIF_BINS] or NULL */);
+int64_t tt_gif_lzw_bound(int64_t npix);
+int tt_gif_lzw(const uint8_t* indices /* host */, int64_t npix, int32_t min_code_size, uint8_t* out /* host */, int64_t cap,
+               int64_t* nbytes_out /* host */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,14 @@ class TtFrameMetricsRecord(C.Structure):
 
 TT_METRICS_SSE_ONLY = 1
 
+
+class TtColorBin(C.Structure):
+    """One histogram bin or palette entry of the GIF export (tt_color_hist / tt_palette_map): 16 bytes, pixels and channel sums."""
+    _fields_ = [("count", C.c_uint32), ("sum_r", C.c_uint32), ("sum_g", C.c_uint32), ("sum_b", C.c_uint32)]
+
+
+TT_GIF_BINS = 32768
+
 _i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
 # name -> (restype, argtypes): every symbol include/ttvdm.h declares
@@ -179,6 +187,12 @@ SIGNATURES = {
     "tt_frame_metrics_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "tt_frame_metrics": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _i32, _vp, _vp, _i64, _vp]),
     "tt_frames_pool2": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # the GIF export: colour histograms and the palette map on the device, median cut and LZW on the host (additive as well)
+    "tt_color_hist": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "tt_palette_map": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp]),
+    "tt_palette_median_cut": (C.c_int, [_vp, _i32, _vp, C.POINTER(C.c_int32), _vp]),
+    "tt_gif_lzw_bound": (_i64, [_i64]),
+    "tt_gif_lzw": (C.c_int, [_vp, _i64, _i32, _vp, _i64, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

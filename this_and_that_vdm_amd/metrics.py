@@ -65,22 +65,23 @@ class VideoMetrics:
         return out
 
 
-def _host_array(x):
+def _host_array(x, who="compare_frames"):
     """lists (of lists) of PIL images or arrays -> one numpy array; numpy arrays as they are"""
     if isinstance(x, np.ndarray):
         return x
     if isinstance(x, (list, tuple)):
         if not x:
-            raise ValueError("compare_frames: an empty list of frames")
-        return np.stack([_host_array(e) for e in x], 0)
+            raise ValueError(f"{who}: an empty list of frames")
+        return np.stack([_host_array(e, who) for e in x], 0)
     arr = np.asarray(x)                               # a PIL image
     if arr.dtype == object:
-        raise ValueError(f"compare_frames: cannot read frames from {type(x).__name__}")
+        raise ValueError(f"{who}: cannot read frames from {type(x).__name__}")
     return arr[..., None] if arr.ndim == 2 else arr
 
 
-def _describe(x):
-    """-> (source, shape, kind): source is a device tensor or a numpy array, not yet uploaded or converted"""
+def _describe(x, who="compare_frames"):
+    """-> (source, shape, kind): source is a device tensor or a numpy array, not yet uploaded or converted.  `who` names the public
+    function in the messages (export.py reads its frames through this too)"""
     from .svd.pipeline_utils import DevicePixels
     if isinstance(x, DevicePixels):
         x = x.pixels
@@ -88,16 +89,16 @@ def _describe(x):
         x = x.numpy()
     if torch.is_tensor(x):
         if x.dtype not in (torch.uint8, torch.float32):
-            raise ValueError(f"compare_frames: uint8 or float32 frames on the device, got {x.dtype}")
+            raise ValueError(f"{who}: uint8 or float32 frames on the device, got {x.dtype}")
         kind = "uint8" if x.dtype == torch.uint8 else "float32"
     else:
-        x = _host_array(x)
+        x = _host_array(x, who)
         if x.dtype != np.uint8 and not np.issubdtype(x.dtype, np.floating):
-            raise ValueError(f"compare_frames: uint8 or floating-point frames, got {x.dtype}")
+            raise ValueError(f"{who}: uint8 or floating-point frames, got {x.dtype}")
         kind = "uint8" if x.dtype == np.uint8 else "float32"
     shape = tuple(x.shape)
     if len(shape) not in (4, 5) or not 1 <= shape[-1] <= 4 or 0 in shape:
-        raise ValueError(f"compare_frames: frames are [F, H, W, C] or [B, F, H, W, C] with 1 to 4 channels, got {shape}")
+        raise ValueError(f"{who}: frames are [F, H, W, C] or [B, F, H, W, C] with 1 to 4 channels, got {shape}")
     return x, shape, kind
 
 

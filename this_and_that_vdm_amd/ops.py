@@ -1102,3 +1102,55 @@ def frames_pool2(x: torch.Tensor):
     check(lib.tt_frames_pool2(_p(x), kind, n, h, w, ch, _p(out), _stream()), "tt_frames_pool2")
     _wrote(out, "frames_pool2")
     return out
+
+
+# ---- the GIF export's device half (tt_color_hist / tt_palette_map; export.py drives them and holds the host half)
+COLOR_BINS = _lib.TT_GIF_BINS
+
+
+def _rgb_frames(x: torch.Tensor, what: str):
+    _p(x)
+    if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous():
+        raise RuntimeError(f"{what}: contiguous uint8 [N, H, W, 3] frames, got {tuple(x.shape)} {x.dtype}")
+    return x.shape
+
+
+def color_hist(frames: torch.Tensor, per_frame: bool = True, out: Optional[torch.Tensor] = None):
+    """uint8 NHWC frames [N, H, W, 3] -> int32 device tensor [N or 1, 32768, 4]: per bin ``r5 << 10 | g5 << 5 | b5`` (the top five bits
+    of each channel) the pixels it holds and the sums of their full 8-bit R, G and B (the bits are uint32: TtColorBin, include/ttvdm.h).
+    ``per_frame=False``: one histogram over all frames.  Exact integers; the same bits every call.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    n, h, w, ch = _rgb_frames(frames, "color_hist")
+    nhist = n if per_frame else 1
+    if out is None:
+        out = torch.empty((nhist, COLOR_BINS, 4), dtype=torch.int32, device=frames.device)
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.device != frames.device or tuple(out.shape) != (nhist, COLOR_BINS, 4):
+        raise RuntimeError(f"color_hist: out must be a contiguous int32 tensor [{nhist}, {COLOR_BINS}, 4] on {frames.device}")
+    check(lib.tt_color_hist(_p(frames), n, h, w, ch, nhist, _p(out), _stream()), "tt_color_hist")
+    _wrote(out, "color_hist")
+    return out
+
+
+def palette_map(frames: torch.Tensor, palettes: torch.Tensor, ncolors, stats: bool = False):
+    """uint8 NHWC frames [N, H, W, 3], device palettes uint8 [N or 1, 256, 3] and ``ncolors`` (host integers, one per palette, 1 .. 256)
+    -> (indices uint8 [N, H, W], sse int64 [N], stats): every pixel's nearest entry among the first ``ncolors`` of its frame's palette
+    (squared RGB distance, the lowest index on a tie), per frame the exact sum of those squared distances, and with ``stats=True`` an
+    int32 tensor [N or 1, 256, 4] of (pixels, sum R, sum G, sum B) per entry (uint32 bits), else None -- all on the device (tt_palette_map)."""
+    lib = _lib.load()
+    n, h, w, ch = _rgb_frames(frames, "palette_map")
+    _p(palettes)
+    if palettes.dtype != torch.uint8 or palettes.dim() != 3 or tuple(palettes.shape[1:]) != (256, 3) or not palettes.is_contiguous() \
+            or palettes.device != frames.device:
+        raise RuntimeError(f"palette_map: palettes must be a contiguous uint8 tensor [N or 1, 256, 3] on {frames.device}, got "
+                           f"{tuple(palettes.shape)} {palettes.dtype}")
+    npal = palettes.shape[0]
+    counts = [int(c) for c in ncolors]
+    if len(counts) != npal:
+        raise RuntimeError(f"palette_map: {len(counts)} ncolors for {npal} palettes")
+    nc = (C.c_int32 * npal)(*counts)
+    indices = torch.empty((n, h, w), dtype=torch.uint8, device=frames.device)
+    sse = torch.empty((n,), dtype=torch.int64, device=frames.device)
+    rec = torch.empty((npal, 256, 4), dtype=torch.int32, device=frames.device) if stats else None
+    check(lib.tt_palette_map(_p(frames), n, h, w, ch, _p(palettes), npal, nc, _p(indices), _p(sse), _p(rec), _stream()), "tt_palette_map")
+    _wrote(indices, "palette_map")
+    return indices, sse, rec

@@ -10,7 +10,8 @@ R = images x videos-per-image independent requests, image-major; every video is 
 Opt-in (``native_image_io=True``, default off): the CLIP image preprocessing, the use_text context LayerNorm and the export of decoded
 frames run on the library's kernels (ops.clip_image / layernorm_block / frames_out) instead of stock torch ops; RGB PIL / uint8 images
 are uploaded once, as uint8, and the VAE input (PIL's LANCZOS resize, 2 x - 1, the noise augmentation) is ops.vae_image on that upload;
-``image=DevicePixels(...)`` takes pixels that are on the device already.
+``image=DevicePixels(...)`` takes pixels that are on the device already, and ``output_type="device"`` returns the uint8 frames
+[R, F, H, W, C] as a device tensor (what "pil" holds, never copied to the host: export.write_gif / metrics.compare_frames take it).
 ``use_instructpix2pix`` (CFG batch of 3, reference :182-184,208-210,698-702) and ``guess_mode`` without CFG are built;
 ``guess_mode`` with CFG raises, as the reference's branch (:676-681) cannot run either.
 Changed on purpose: the gesture map is VAE-encoded ONCE per request instead of inside every step (reference :652 --
@@ -219,6 +220,12 @@ class _SVDPipelineCore(PipelineBase):
             return arr
         return [[PIL.Image.fromarray(im.squeeze(-1) if im.shape[-1] == 1 else im) for im in video] for video in arr]
 
+    def _frames_device(self, latents, num_frames, decode_chunk_size):
+        """output_type "device": the uint8 chunks ops.frames_out(sample, 1) writes for "pil", concatenated ON the device -> uint8
+        [R, F, H, W, C]; no host copy.  export.write_gif and metrics.compare_frames take it as it is."""
+        frames = torch.cat([ops.frames_out(sample, 1) for sample in self._decode_chunks(latents, decode_chunk_size)], 0)
+        return frames.reshape(-1, num_frames, *frames.shape[1:])
+
     def check_inputs(self, image, height, width):
         if not isinstance(image, (torch.Tensor, PIL.Image.Image, list, DevicePixels)):
             raise ValueError("`image` has to be of type `torch.FloatTensor` or `PIL.Image.Image` or `List[PIL.Image.Image]` "
@@ -324,6 +331,11 @@ class _SVDPipelineCore(PipelineBase):
 
     def _request_finish(self, latents, num_frames, decode_chunk_size, output_type):
         """final latents [R,F,4,h,w] -> what the caller receives: decode + frame export, or the latents themselves (output_type "latent")"""
+        if output_type == "device":
+            if not self.native_image_io:
+                raise ValueError('output_type="device" needs a pipeline with native_image_io=True: the frames stay on the device as '
+                                 "ops.frames_out writes them, and the torch request path has no such export")
+            return self._frames_device(latents.to(self.vae.dtype), num_frames, decode_chunk_size)
         if self.native_image_io and output_type in ("np", "pil"):
             return self._frames_native(latents.to(self.vae.dtype), num_frames, decode_chunk_size, output_type)
         if output_type != "latent":
