@@ -887,6 +887,110 @@ int64_t tt_gif_lzw_bound(int64_t npix);
 int tt_gif_lzw(const uint8_t* indices /* host */, int64_t npix, int32_t min_code_size, uint8_t* out /* host */, int64_t cap,
                int64_t* nbytes_out /* host */);
 
+/* ------------------------------------------------------------------------------------------------
+ * PNG export: frames written as standard 8-bit PNG files whose row filter, tokens and Huffman-coded bits are made on the device
+ * (this_and_that_vdm_amd/export.py drives it).  Three kernels (tt_png_filter, tt_png_tokens, tt_png_emit) and three host routines
+ * (tt_png_code_lengths, tt_png_block_header, tt_png_plan; plain C++, they touch no device).  Integers only: the same frames give the
+ * same bytes every time.  Additive: the ABI version is unchanged.  The filtered bytes never leave the device; the host sees 1152 bytes
+ * of counts per stripe and the finished compressed stream.
+ *
+ * 1. Filter -- tt_png_filter: frames [n, h, w, ch] uint8 NHWC on the device, ch 1 .. 4 (PNG colour types 0, 4, 2, 6; bpp = ch) ->
+ *    per frame the FILTERED STREAM of tt_png_stream_bytes = h (1 + w ch) bytes: every row is its filter-type byte followed by its
+ *    w ch filtered bytes.  With x the byte, a the byte bpp to its left, b the byte above, c the byte above a (zeros left of the first
+ *    pixel and above the first row), all mod 256:  type 0: x;  1: x - a;  2: x - b;  3: x - ((a + b) >> 1);  4: x - paeth(a, b, c),
+ *    paeth: p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c|; a if pa <= pb and pa <= pc, else b if pb <= pc, else c.
+ *    filter = 0 .. 4: that type on every row.  filter = 5 (TT_PNG_ADAPTIVE): per row the type with the smallest sum over the row's
+ *    filtered bytes v of (v < 128 ? v : 256 - v); the LOWEST type on a tie.  A row needs the raw row above it only: one workgroup of
+ *    TT_PNG_FILTER_BLOCK lanes per row, ONE launch for all frames.  Frame f's stream starts at byte f tt_png_frame_stride (the stream
+ *    bytes rounded up to 16) of `filtered`; the padding is never read as data.
+ *    TT_EINVAL: null frames / filtered; n, h or w <= 0; ch outside 1 .. 4; filter outside 0 .. 5; filtered off a 16-byte boundary.
+ *    TT_EUNSUPPORTED: a stream of 2^31 bytes or more; more rows than one grid covers (n h > 2^31 - 1).
+ *
+ * 2. Stripes: a frame's filtered stream is cut into stripes of TT_PNG_STRIPE = 32 768 bytes (the last may be shorter), by bytes and
+ *    not by rows; tt_png_stripes = ceil(stream bytes / TT_PNG_STRIPE) per frame.  No token crosses a stripe boundary, and every
+ *    stripe is one DEFLATE block with its own codes that starts and ends on a byte, so stripes are coded independently.
+ *
+ * 3. Tokens -- tt_png_tokens (zlib's Z_RLE idea as a closed rule): inside a stripe, a maximal run of L equal bytes becomes one
+ *    literal, then (L - 1) / 258 matches of (length 258, distance 1); with r = (L - 1) mod 258, one match (length r, distance 1)
+ *    follows if r >= 3, else r literals.  No other match is made.  One workgroup of TT_PNG_BLOCK lanes per stripe, every lane holding
+ *    32 consecutive bytes in registers; where the run through a lane's first byte starts and where the run through its last byte ends
+ *    come from two workgroup scans (a running maximum of run starts forward, a running minimum backward); with them every byte
+ *    position knows its run and so whether a token starts at it.  Per stripe one RECORD of TT_PNG_RECORD_WORDS = 288 uint32 (1152
+ *    bytes): the counts of the 286 literal/length symbols (symbol 256, end of block, counts 1; length m is symbol 254 + m for m <= 10,
+ *    285 for 258, else 265 + 4 (k - 1) + (((m - 3) >> k) & 3) with k = floor(log2(m - 3)) - 2 extra bits holding (m - 3) mod 2^k), then
+ *    the stripe's Adler-32 pair s1, s2 mod 65 521 started from (1, 0): s1 = 1 + sum b_i, s2 = len + sum (len - i) b_i.  A lane's
+ *    32 terms are below 2^29; it reduces mod 65 521 before the workgroup sum (1024 x 65 521), so nothing wraps.  ONE launch for all frames.
+ *    TT_EINVAL: null filtered / records; n, h or w <= 0; ch outside 1 .. 4; filtered or records off a 16-byte boundary.
+ *
+ * 4. Code lengths -- tt_png_code_lengths (host): counts[nsym] -> lengths[nsym] (0 for a count of 0) that minimise sum count length
+ *    subject to length <= limit and Kraft sum <= 1 -- package-merge.  Leaves are the used symbols in ascending (count, symbol).
+ *    List 1 is the leaves; list l + 1 is the leaves merged with the packages of list l (items 2k and 2k + 1 added, an odd last item
+ *    dropped), by ascending weight, a LEAF BEFORE A PACKAGE of equal weight, cut to 2 u - 2 items (u used symbols).  The first
+ *    2 u - 2 items of list `limit` are taken; taking a package takes its two items of the list before.  A symbol's length is the
+ *    number of lists in which its leaf is taken (in each list the taken leaves are a prefix of the leaf order, so of two symbols with
+ *    equal counts the lower one never gets the shorter code).  One used symbol gets length 1; with two or more the Kraft sum is
+ *    exactly 1.  limit is 15 for the literal/length code, 7 for the code-length code.  The distance code is not computed: it is
+ *    always symbol 0 alone with length 1 (RFC 1951 3.2.7: "one distance code of one bit"), every match's distance is the bit 0.
+ *    Codes are canonical (RFC 1951 3.2.2) and go into the stream from their most significant bit.
+ *    TT_EINVAL: null pointer; nsym outside 1 .. 286; limit outside 1 .. 15 or 2^limit below the used symbols; no used symbol.
+ *
+ * 5. Block header -- tt_png_block_header (host): counts[286] and lengths[286] -> the dynamic-block header of the stripe, LSB first:
+ *    BFINAL 0, BTYPE 2, HLIT = max(257, last used symbol + 1) - 257, HDIST - 1 = 0, HCLEN - 4, the code-length code's lengths (3 bits
+ *    each, in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, up to the last used one, at least 4), then the HLIT + 257
+ *    literal/length lengths followed by the one distance length 1, as ONE sequence coded greedily from the left: a maximal run of R
+ *    equal values v.  v = 0: while R >= 11, symbol 18 with min(R, 138) (7 extra bits: that - 11); then symbol 17 with R (3 extra bits:
+ *    R - 3) if R >= 3, else R symbols 0.  v > 0: symbol v once; then while R >= 3 of what is left, symbol 16 with min(R, 6) (2 extra
+ *    bits: that - 3); then what is left as symbols v.  The code-length code's lengths are tt_png_code_lengths(limit 7) of those
+ *    symbols' counts.  header[0] receives the header's bits, header[1 ..] the bits packed from the least significant bit of each
+ *    uint32 (zeros behind the last); the header is at most 17 + 57 + 287 x 7 = 2083 bits, TT_PNG_HEADER_WORDS = 72 words hold it.
+ *    stripe_bits_out receives the exact size of the stripe's block: header + sum count length + sum count (extra bits of the length
+ *    symbol) + matches (one distance bit each) -- the end-of-block code is in the counts -- + the 3 header bits of the empty stored
+ *    block that follows.  The stripe takes ceil(stripe_bits / 8) + 4 bytes.
+ *    TT_EINVAL: null pointer; cap_words < TT_PNG_HEADER_WORDS ("cap too small"); a length above 15; a used symbol (or symbol 256)
+ *    without a length; lengths whose Kraft sum exceeds 1.
+ *    tt_png_plan (host) does 4 and 5 for every record of a call: records [nstripes][288] as tt_png_tokens wrote them -> tables
+ *    [nstripes][TT_PNG_TABLE_WORDS = 288] (entry s < 286: the canonical code of symbol s with its bits REVERSED, so that it is ORed in
+ *    LSB first, | length << 16; words 286 / 287: the low / high half of the stripe's byte offset in the output), headers
+ *    [nstripes][TT_PNG_HEADER_WORDS], and the total bytes of all stripes, each starting where the one before ends.
+ *
+ * 6. Emit -- tt_png_emit: per stripe, at its byte offset: the header bits; every token's code in order -- a literal's code; a match's
+ *    length code, its extra bits, then the distance bit 0: at most 15 + 5 + 1 bits --; the end-of-block code; an empty stored block
+ *    (bits 000, zeros up to the byte, 00 00 FF FF), so that the next stripe starts on a byte.  One workgroup per stripe; a token's
+ *    bit position is the header's bits plus a workgroup scan of the lanes' token bits.  Bits are assembled in LDS in chunks of
+ *    TT_PNG_CHUNK = 16 384 bytes laid over the OUTPUT's 16-byte grid: a lane shifts its tokens into a 64-bit accumulator and ORs every
+ *    finished 32-bit word in (integer atomic OR: its first and last word are shared with its neighbours); a chunk then leaves through
+ *    16-byte vector stores, except the 16-byte units a stripe shares with its neighbours, whose bytes of this stripe are written one
+ *    by one.  No byte at or beyond out_bytes is written whatever the tables hold.
+ *    TT_EINVAL: null filtered / tables / headers / out; n, h or w <= 0; ch outside 1 .. 4; filtered, tables, headers or out off a
+ *    16-byte boundary; out_bytes <= 0; cap < out_bytes ("cap too small").
+ *    All three kernels are refused before the first HIP call; no allocation, no synchronisation.
+ *
+ * 7. Stream and file (export.py): a frame's zlib stream is 78 01, its stripes, 01 00 00 FF FF (the final, empty stored block), then
+ *    the Adler-32 of the whole filtered stream big-endian, combined from the stripes' pairs as zlib's adler32_combine does.
+ *    Worst case: no code is longer than a flat one of 8 and 9 bits, so a stripe takes at most 9/8 of its bytes + 272; on uniform noise
+ *    the stream is about 1 % above the raw bytes (there is no stored-block fallback). */
+#define TT_PNG_STRIPE 32768
+#define TT_PNG_BLOCK 1024
+#define TT_PNG_FILTER_BLOCK 256
+#define TT_PNG_ADAPTIVE 5
+#define TT_PNG_SYMS 286
+#define TT_PNG_RECORD_WORDS 288
+#define TT_PNG_TABLE_WORDS 288
+#define TT_PNG_HEADER_WORDS 72
+#define TT_PNG_CHUNK 16384
+int64_t tt_png_stream_bytes(int32_t h, int32_t w, int32_t ch);     /* h (1 + w ch); 0 for arguments tt_png_filter refuses */
+int64_t tt_png_frame_stride(int32_t h, int32_t w, int32_t ch);     /* ... rounded up to 16 */
+int64_t tt_png_stripes(int32_t h, int32_t w, int32_t ch);          /* stripes per frame */
+int tt_png_filter(const void* frames, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t filter, uint8_t* filtered, tt_stream_t stream);
+int tt_png_tokens(const uint8_t* filtered, int32_t n, int32_t h, int32_t w, int32_t ch, uint32_t* records, tt_stream_t stream);
+int tt_png_emit(const uint8_t* filtered, int32_t n, int32_t h, int32_t w, int32_t ch, const uint32_t* tables, const uint32_t* headers,
+                uint8_t* out, int64_t out_bytes, int64_t cap, tt_stream_t stream);
+int tt_png_code_lengths(const uint32_t* counts /* host */, int32_t nsym, int32_t limit, uint8_t* lengths /* host */);
+int tt_png_block_header(const uint32_t* counts /* host [286] */, const uint8_t* lengths /* host [286] */,
+                        uint32_t* header /* host [cap_words] */, int32_t cap_words, int64_t* stripe_bits_out /* host */);
+int tt_png_plan(const uint32_t* records /* host */, int64_t nstripes, uint32_t* tables /* host */, uint32_t* headers /* host */,
+                int64_t* total_bytes_out /* host */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,7 @@ class TtColorBin(C.Structure):
 
 
 TT_GIF_BINS = 32768
+TT_PNG_STRIPE, TT_PNG_SYMS, TT_PNG_RECORD_WORDS, TT_PNG_TABLE_WORDS, TT_PNG_HEADER_WORDS = 32768, 286, 288, 288, 72
 
 _i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -193,6 +194,16 @@ SIGNATURES = {
     "tt_palette_median_cut": (C.c_int, [_vp, _i32, _vp, C.POINTER(C.c_int32), _vp]),
     "tt_gif_lzw_bound": (_i64, [_i64]),
     "tt_gif_lzw": (C.c_int, [_vp, _i64, _i32, _vp, _i64, C.POINTER(C.c_int64)]),
+    # the PNG export: filter, tokens and emit on the device, code lengths and block headers on the host (additive as well)
+    "tt_png_stream_bytes": (_i64, [_i32, _i32, _i32]),
+    "tt_png_frame_stride": (_i64, [_i32, _i32, _i32]),
+    "tt_png_stripes": (_i64, [_i32, _i32, _i32]),
+    "tt_png_filter": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "tt_png_tokens": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "tt_png_emit": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "tt_png_code_lengths": (C.c_int, [_vp, _i32, _i32, _vp]),
+    "tt_png_block_header": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
+    "tt_png_plan": (C.c_int, [_vp, _i64, _vp, _vp, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -9,7 +9,18 @@ states all four rule by rule).
 integers), the palettes' upload, ``refine`` Lloyd iterations (map with per-entry sums, read 256 records back, move every used entry to
 the rounded mean of its pixels), the final map, and ONE readback of the indices (one byte per pixel, not three) and the exact error
 sums.  Everything is integer arithmetic: the same frames give the same file every time, from host and from device copies alike.
-Not here: dithering, transparency, frame differencing."""
+Not here: dithering, transparency, frame differencing.
+
+... and as PNG files, lossless (``tt_png_filter`` / ``tt_png_tokens`` / ``tt_png_emit``; code lengths and block headers are host
+routines of the library):
+
+    write_pngs(pipe(..., output_type="device").frames[0], folder)        # folder/0.png, 1.png, ...
+    write_apng(frames, "combined.png", duration=0.05)
+
+``png_streams``: ONE filter launch and ONE tokens launch for all frames, one readback of 1152 bytes per 32 KiB stripe, package-merge and
+the dynamic-block headers on the host, one upload of the tables and headers, ONE emit launch, one readback of the finished compressed
+streams -- the filtered bytes never leave the device.  Not here: LZ77 matches beyond distance 1, a stored-block fallback, 16-bit or
+palette PNGs, interlace, ancillary chunks."""
 from __future__ import annotations
 
 import ctypes as C
@@ -57,15 +68,16 @@ def _psnr(sse, values):
         return np.where(mse == 0.0, np.inf, 10.0 * np.log10(255.0 * 255.0 / mse))
 
 
-def _frames_u8(frames, who: str) -> torch.Tensor:
+def _frames_u8(frames, who: str, rgb: bool = True) -> torch.Tensor:
     """what ``metrics.compare_frames`` takes -> contiguous uint8 [F, H, W, 3] on the device (a host input is uploaded once).  Floating-point
-    frames in [0, 1] become ``rint(clamp(x, 0, 1) * 255)`` in fp32, the rounding tt_frames_out states for its kind 1."""
+    frames in [0, 1] become ``rint(clamp(x, 0, 1) * 255)`` in fp32, the rounding tt_frames_out states for its kind 1.  ``rgb=False``
+    (the PNG export): 1 to 4 channels."""
     x, shape, kind = _describe(frames, who)
     if len(shape) == 5 and shape[0] == 1:             # a pipeline's output for one video
         x, shape = x[0], shape[1:]
     if len(shape) != 4:
         raise ValueError(f"{who}: one video per file -- frames [F, H, W, 3], got a batch of {shape[0]} videos {shape}; pass them one at a time")
-    if shape[-1] != 3:
+    if rgb and shape[-1] != 3:
         raise ValueError(f"{who}: RGB frames (3 channels), got {shape[-1]} in {shape}")
     device = x.device if torch.is_tensor(x) else torch.device("cuda")
     x = _on_device(x, device)
@@ -209,3 +221,163 @@ def write_gif(frames, path_or_file, duration: float = 0.05, loop=0, **quantize_k
     q = quantize_frames(frames, **quantize_kwargs)
     write_gif_indexed(q.indices, q.palettes, q.ncolors, path_or_file, duration=duration, loop=loop, palette=q.palette)
     return q
+
+
+# ---- frames -> PNG files: the row filter, the run tokens and the Huffman-coded bits are made on the device (include/ttvdm.h, "PNG
+# export", rules 1 - 7); the host sees 1152 bytes of symbol counts per 32 KiB stripe and the finished compressed streams
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_COLOR_TYPE = {1: 0, 2: 4, 3: 2, 4: 6}
+ADLER_MOD = 65521
+
+
+def png_code_lengths(counts, limit: int = 15) -> np.ndarray:
+    """symbol counts (at most 286) -> uint8 code lengths that minimise sum count x length with no length above ``limit``
+    (tt_png_code_lengths: package-merge)"""
+    lib = _lib.load()
+    c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    out = np.zeros(c.size, dtype=np.uint8)
+    check(lib.tt_png_code_lengths(c.ctypes.data, c.size, int(limit), out.ctypes.data), "tt_png_code_lengths")
+    return out
+
+
+def png_block_header(counts, lengths):
+    """one stripe's 286 symbol counts and code lengths -> (the dynamic-block header's bits as a uint8 array of 0 / 1 in stream order, the
+    stripe's exact size in bits up to and with the three header bits of the stored block behind it) (tt_png_block_header)"""
+    lib = _lib.load()
+    c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    ln = np.ascontiguousarray(lengths, dtype=np.uint8).reshape(-1)
+    if c.size != _lib.TT_PNG_SYMS or ln.size != _lib.TT_PNG_SYMS:
+        raise ValueError(f"png_block_header: {_lib.TT_PNG_SYMS} counts and lengths, got {c.size} and {ln.size}")
+    words = np.zeros(_lib.TT_PNG_HEADER_WORDS, dtype=np.uint32)
+    bits = C.c_int64(0)
+    check(lib.tt_png_block_header(c.ctypes.data, ln.ctypes.data, words.ctypes.data, words.size, C.byref(bits)), "tt_png_block_header")
+    return np.unpackbits(words[1:].view(np.uint8), bitorder="little")[:int(words[0])], bits.value
+
+
+def png_plan(records: np.ndarray):
+    """the records of ``ops.png_tokens`` on the host [S, 288] -> (tables int32 [S, 288], headers int32 [S, 72], total bytes): per stripe
+    the reversed canonical codes with their lengths and the stripe's byte offset, and its block header (tt_png_plan)"""
+    lib = _lib.load()
+    rec = np.ascontiguousarray(records).view(np.uint32).reshape(-1, _lib.TT_PNG_RECORD_WORDS)
+    tables = np.zeros((rec.shape[0], _lib.TT_PNG_TABLE_WORDS), dtype=np.uint32)
+    headers = np.zeros((rec.shape[0], _lib.TT_PNG_HEADER_WORDS), dtype=np.uint32)
+    total = C.c_int64(0)
+    check(lib.tt_png_plan(rec.ctypes.data, rec.shape[0], tables.ctypes.data, headers.ctypes.data, C.byref(total)), "tt_png_plan")
+    return tables.view(np.int32), headers.view(np.int32), total.value
+
+
+def _adler_of_stripes(rec: np.ndarray, lens) -> int:
+    """the Adler-32 of a stream from its stripes' (s1, s2) pairs, each started from (1, 0), as zlib's adler32_combine joins two:
+    s1 = s1a + s1b - 1, s2 = s2a + s2b + len_b (s1a - 1), mod 65 521"""
+    s1, s2 = 1, 0
+    for (b1, b2), n in zip(rec, lens):
+        s2 = (s2 + int(b2) + n * (s1 - 1)) % ADLER_MOD
+        s1 = (s1 + int(b1) - 1) % ADLER_MOD
+    return (s2 << 16) | s1
+
+
+@dataclass
+class PngStreams:
+    """``streams``: per frame the zlib stream of its filtered bytes (the payload of IDAT); ``height``, ``width``, ``channels``"""
+    streams: list
+    height: int
+    width: int
+    channels: int
+
+
+def png_streams(frames, filter="adaptive") -> PngStreams:
+    """Frames -> their zlib streams.  ONE filter launch and ONE tokens launch for all frames, one readback of the stripes' records, the
+    code lengths and block headers on the host, one upload each of the tables and the headers, ONE emit launch, one readback of the
+    finished stripes.  Per frame the stream is 78 01, its stripes, 01 00 00 FF FF, the Adler-32 big-endian."""
+    from . import ops
+    if filter not in ops.PNG_FILTERS and not (type(filter) is int and 0 <= filter <= 5):
+        raise ValueError(f"encode_png: filter {filter!r} (one of {sorted(ops.PNG_FILTERS)}, or 0 to 5)")
+    x = _frames_u8(frames, "encode_png", rgb=False)
+    f, h, w, ch = x.shape
+    if h >= 1 << 31 or w >= 1 << 31:
+        raise ValueError(f"encode_png: a PNG is below 2^31 pixels a side, got {h} x {w}")
+    filtered = ops.png_filter(x, filter)
+    records = ops.png_tokens(filtered, (h, w, ch))
+    rec = records.cpu().numpy().view(np.uint32)                                                # readback 1: 1152 bytes per stripe
+    tables, headers, total = png_plan(rec)
+    out = ops.png_emit(filtered, (h, w, ch), torch.from_numpy(tables).to(x.device), torch.from_numpy(headers).to(x.device), total)
+    data = out.cpu().numpy()                                                                   # readback 2: the finished stripes
+    stripes = rec.shape[0] // f
+    stream_bytes = h * (1 + w * ch)
+    lens = [min(_lib.TT_PNG_STRIPE, stream_bytes - k * _lib.TT_PNG_STRIPE) for k in range(stripes)]
+    offsets = (tables[::stripes, 286].astype(np.int64) & 0xffffffff) | (tables[::stripes, 287].astype(np.int64) << 32)
+    ends = list(offsets[1:]) + [total]
+    streams = []
+    for i in range(f):
+        adler = _adler_of_stripes(rec[i * stripes:(i + 1) * stripes, 286:288], lens)
+        streams.append(b"".join((b"\x78\x01", data[int(offsets[i]):int(ends[i])].tobytes(), b"\x01\x00\x00\xff\xff", struct.pack(">I", adler))))
+    return PngStreams(streams, h, w, ch)
+
+
+def _png_chunk(tag: bytes, *parts: bytes) -> bytes:
+    import zlib
+    crc = zlib.crc32(tag)
+    for p in parts:
+        crc = zlib.crc32(p, crc)
+    return b"".join((struct.pack(">I", sum(len(p) for p in parts)), tag, *parts, struct.pack(">I", crc)))
+
+
+def _png_ihdr(s: PngStreams) -> bytes:
+    return _png_chunk(b"IHDR", struct.pack(">IIBBBBB", s.width, s.height, 8, PNG_COLOR_TYPE[s.channels], 0, 0, 0))
+
+
+def png_files(s: PngStreams) -> list:
+    """per frame the file: signature, IHDR (8 bit, colour type by channels: 0, 4, 2, 6; no interlace), ONE IDAT, IEND"""
+    head, end = PNG_SIGNATURE + _png_ihdr(s), _png_chunk(b"IEND")
+    return [b"".join((head, _png_chunk(b"IDAT", z), end)) for z in s.streams]
+
+
+def encode_png(frames, filter="adaptive") -> list:
+    """Frames -> one PNG file (bytes) per frame.  ``frames``: what ``write_gif`` takes, with 1 to 4 channels (grey, grey + alpha, RGB,
+    RGBA) -- a device uint8 / float32 NHWC tensor, ``DevicePixels``, numpy, a list of PIL images or a pipeline's "pil" / "np" / "device"
+    output for ONE video; floating-point frames are rounded as for ``write_gif``.  ``filter``: "adaptive" (per row the type with the
+    least sum of absolute signed residuals), or "none" / "sub" / "up" / "average" / "paeth" on every row.  Lossless; the same frames
+    give the same bytes from host and device copies alike."""
+    return png_files(png_streams(frames, filter))
+
+
+def write_pngs(frames, folder, pattern: str = "{idx}.png", filter="adaptive") -> list:
+    """``encode_png`` written as ``folder/pattern.format(idx=i)`` -- 0.png, 1.png, ... by default -- ; returns the paths.  The folder is
+    made when it does not exist."""
+    import os
+    files = encode_png(frames, filter)
+    os.makedirs(folder, exist_ok=True)
+    paths = [os.path.join(folder, pattern.format(idx=i)) for i in range(len(files))]
+    if len(set(paths)) != len(paths):
+        raise ValueError(f"write_pngs: pattern {pattern!r} names two frames alike (use {{idx}})")
+    for path, data in zip(paths, files):
+        with open(path, "wb") as fh:
+            fh.write(data)
+    return paths
+
+
+def write_apng(frames, path_or_file, duration: float = 0.05, loop: int = 0, filter="adaptive") -> None:
+    """The frames as ONE animated PNG: acTL (frames, ``loop`` plays; 0: for ever), then per frame an fcTL and the frame's stream -- the
+    first as IDAT, so that a viewer without APNG shows it, the others as fdAT; the streams are ``encode_png``'s.  Every frame covers the
+    canvas, dispose and blend 0.  Delay: the fraction round(duration 1000) / 1000 seconds, the numerator kept within 0 .. 65535."""
+    if not 0 <= int(loop) < 1 << 31:
+        raise ValueError(f"write_apng: loop = {loop} (0: for ever, or the number of plays)")
+    delay = min(65535, max(0, int(round(float(duration) * 1000.0))))
+    s = png_streams(frames, filter)
+    out = [PNG_SIGNATURE, _png_ihdr(s), _png_chunk(b"acTL", struct.pack(">II", len(s.streams), int(loop)))]
+    seq = 0
+    for i, z in enumerate(s.streams):
+        out.append(_png_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, s.width, s.height, 0, 0, delay, 1000, 0, 0)))
+        seq += 1
+        if i == 0:
+            out.append(_png_chunk(b"IDAT", z))
+        else:
+            out.append(_png_chunk(b"fdAT", struct.pack(">I", seq), z))
+            seq += 1
+    out.append(_png_chunk(b"IEND"))
+    data = b"".join(out)
+    if hasattr(path_or_file, "write"):
+        path_or_file.write(data)
+    else:
+        with open(path_or_file, "wb") as fh:
+            fh.write(data)

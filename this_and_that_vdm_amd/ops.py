@@ -1154,3 +1154,70 @@ def palette_map(frames: torch.Tensor, palettes: torch.Tensor, ncolors, stats: bo
     check(lib.tt_palette_map(_p(frames), n, h, w, ch, _p(palettes), npal, nc, _p(indices), _p(sse), _p(rec), _stream()), "tt_palette_map")
     _wrote(indices, "palette_map")
     return indices, sse, rec
+
+
+# ---- the PNG export's device half (tt_png_filter / tt_png_tokens / tt_png_emit; export.py drives them and holds the host half)
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+
+
+def _png_shape(shape, what: str):
+    h, w, ch = (int(v) for v in shape)
+    if h <= 0 or w <= 0 or not 1 <= ch <= 4:
+        raise RuntimeError(f"{what}: shape (h, w, ch) with 1 to 4 channels, got {tuple(shape)}")
+    return h, w, ch
+
+
+def _png_filtered(filtered: torch.Tensor, shape, what: str):
+    lib = _lib.load()
+    h, w, ch = _png_shape(shape, what)
+    _p(filtered)
+    stride = lib.tt_png_frame_stride(h, w, ch)
+    if filtered.dtype != torch.uint8 or filtered.dim() != 2 or filtered.shape[1] != stride or not filtered.is_contiguous() or filtered.shape[0] < 1:
+        raise RuntimeError(f"{what}: filtered must be a contiguous uint8 tensor [N, {stride}] (png_filter's), got {tuple(filtered.shape)} {filtered.dtype}")
+    return lib, filtered.shape[0], h, w, ch, lib.tt_png_stripes(h, w, ch)
+
+
+def png_filter(frames: torch.Tensor, filter=5):
+    """uint8 NHWC frames [N, H, W, C], C 1 .. 4 -> uint8 device tensor [N, stride]: per frame the PNG-filtered stream of H (1 + W C) bytes,
+    every row its filter-type byte and its filtered bytes; stride rounds that up to 16 and the padding is not written.  ``filter``: 0 .. 4
+    (none, sub, up, average, paeth on every row), 5 (per row the type with the least sum of |signed byte|, the lowest on a tie), or one
+    of those names (tt_png_filter).  Asynchronous on the current stream."""
+    lib = _lib.load()
+    _p(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_contiguous():
+        raise RuntimeError(f"png_filter: contiguous uint8 [N, H, W, C] frames, got {tuple(frames.shape)} {frames.dtype}")
+    kind = PNG_FILTERS.get(filter, filter)
+    if not isinstance(kind, int) or isinstance(kind, bool) or not 0 <= kind <= 5:
+        raise RuntimeError(f"png_filter: filter {filter!r} (0 to 5, or one of {sorted(PNG_FILTERS)})")
+    n, h, w, ch = frames.shape
+    _png_shape((h, w, ch), "png_filter")
+    out = torch.empty((n, lib.tt_png_frame_stride(h, w, ch)), dtype=torch.uint8, device=frames.device)
+    check(lib.tt_png_filter(_p(frames), n, h, w, ch, kind, _p(out), _stream()), "tt_png_filter")
+    _wrote(out, "png_filter")
+    return out
+
+
+def png_tokens(filtered: torch.Tensor, shape):
+    """``png_filter``'s output for frames of ``shape`` (h, w, ch) -> int32 device tensor [N stripes, 288] (uint32 bits): per 32 KiB stripe
+    of every frame's stream the counts of the 286 literal/length symbols its run tokens use and its Adler-32 pair (tt_png_tokens)."""
+    lib, n, h, w, ch, stripes = _png_filtered(filtered, shape, "png_tokens")
+    rec = torch.empty((n * stripes, _lib.TT_PNG_RECORD_WORDS), dtype=torch.int32, device=filtered.device)
+    check(lib.tt_png_tokens(_p(filtered), n, h, w, ch, _p(rec), _stream()), "tt_png_tokens")
+    _wrote(rec, "png_tokens")
+    return rec
+
+
+def png_emit(filtered: torch.Tensor, shape, tables: torch.Tensor, headers: torch.Tensor, out_bytes: int):
+    """``png_filter``'s output, and per stripe the code table with its byte offset [N stripes, 288] and the block header [N stripes, 72]
+    (int32 device tensors holding what tt_png_plan made) -> uint8 device tensor [out_bytes]: every stripe's DEFLATE block followed by an
+    empty stored block, at its offset (tt_png_emit)."""
+    lib, n, h, w, ch, stripes = _png_filtered(filtered, shape, "png_emit")
+    for t, words, name in ((tables, _lib.TT_PNG_TABLE_WORDS, "tables"), (headers, _lib.TT_PNG_HEADER_WORDS, "headers")):
+        _p(t)
+        if t.dtype != torch.int32 or tuple(t.shape) != (n * stripes, words) or not t.is_contiguous() or t.device != filtered.device:
+            raise RuntimeError(f"png_emit: {name} must be a contiguous int32 tensor [{n * stripes}, {words}] on {filtered.device}, got "
+                               f"{tuple(t.shape)} {t.dtype}")
+    out = torch.empty((int(out_bytes),), dtype=torch.uint8, device=filtered.device)
+    check(lib.tt_png_emit(_p(filtered), n, h, w, ch, _p(tables), _p(headers), _p(out), int(out_bytes), out.numel(), _stream()), "tt_png_emit")
+    _wrote(out, "png_emit")
+    return out
