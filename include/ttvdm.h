@@ -991,6 +991,89 @@ int tt_png_block_header(const uint32_t* counts /* host [286] */, const uint8_t* 
 int tt_png_plan(const uint32_t* records /* host */, int64_t nstripes, uint32_t* tables /* host */, uint32_t* headers /* host */,
                 int64_t* total_bytes_out /* host */);
 
+/* ------------------------------------------------------------------------------------------------
+ * JPEG export: frames written as baseline JPEG files (and as a Motion-JPEG AVI) whose colour conversion, chroma downsampling, DCT,
+ * quantiser, Huffman-coded bits and byte stuffing are made on the device (this_and_that_vdm_amd/export.py drives it).  Two device
+ * entry points (tt_jpeg_coeffs, tt_jpeg_scan) and three host routines (tt_jpeg_quant_tables, tt_jpeg_standard_table,
+ * tt_jpeg_optimized_table; plain C++, they touch no device).  Baseline JPEG as libjpeg writes it is integers from end to end: the same
+ * frames give the same bytes every time, and with the standard tables the scan equals libjpeg's ("islow" DCT) byte for byte.
+ * Additive: the ABI version is unchanged.  Only the finished scans and their lengths (and, for optimized tables, 4 KiB of counts per
+ * frame) reach the host.  Not here: progressive and arithmetic coding, 4:2:2, restart markers, EXIF / ICC, CMYK, 12-bit samples,
+ * trellis quantisation, a decoder.
+ *
+ * Input: frames [n, h, w, ch] uint8 NHWC on the device, ch 1 (grey) or 3 (RGB).  subsampling: TT_JPEG_444 (0) or TT_JPEG_420 (2);
+ * a grey frame has one component and ignores it.
+ *
+ * 1. Quantiser tables -- tt_jpeg_quant_tables (host): the Annex K luminance and chrominance tables scaled as jpeg_set_quality does:
+ *    s = 5000 / quality (integer division) for quality < 50, else 200 - 2 quality; every entry is clamp((base s + 50) / 100, 1, 255).
+ *    tables receives [2][64] bytes in natural (row-major) order.  TT_EINVAL: null tables; quality outside 1 .. 100.
+ * 2. Colour (16-bit fixed point, arithmetic shifts; grey input is Y as it stands):
+ *    Y = (19595 R + 38470 G + 7471 B + 32768) >> 16;  Cb = (-11059 R - 21709 G + 32768 B + 128 65536 + 32767) >> 16;
+ *    Cr = (32768 R - 27439 G - 5329 B + 128 65536 + 32767) >> 16.
+ * 3. Geometry.  4:4:4 and grey: every component is padded to whole 8 x 8 blocks by repeating its last column and row; an MCU is one
+ *    block of each component, MCUs left to right, top to bottom.  4:2:0: an MCU is 16 x 16 pixels; Y is padded by edge replication to
+ *    ceil(h / 8) 8 x ceil(w / 8) 8; the full-resolution Cb / Cr planes are edge-replicated to 2 ceil(h / 2) rows and 16 x (chroma
+ *    blocks per row) columns, every chroma sample is (a + b + c + d + bias) >> 2 over its 2 x 2 cell with bias 1 on even and 2 on odd
+ *    output columns, and the DOWNSAMPLED plane is then edge-replicated downwards to whole blocks.  An MCU is Y top-left, top-right,
+ *    bottom-left, bottom-right, Cb, Cr.  A Y block of an MCU beyond ceil(w / 8) block columns or ceil(h / 8) block rows is a dummy
+ *    block: its AC coefficients are zero and its DC is the DC of the block coded just before it in that MCU; it is coded like any other.
+ *    tt_jpeg_blocks: the blocks of one frame's scan, dummies included.
+ * 4. Transform: samples minus 128 through the jfdctint ("islow") forward DCT in 32-bit integers -- rows first (PASS1_BITS = 2), then
+ *    columns, CONST_BITS = 13, rounding right shifts, multipliers 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172 --;
+ *    the output is scaled by 8.
+ * 5. Quantiser: with d the DCT output and Q = 8 x the table entry, the coefficient is sign(d) ((|d| + (Q >> 1)) / Q), integer
+ *    division (the kernel divides; no reciprocal).
+ *    tt_jpeg_coeffs does 2 - 5 in ONE launch for all frames: a workgroup takes one MCU row down and 256 pixels across, reads every
+ *    pixel once, converts it (and sums the 4:2:0 cells) into LDS, then one lane per block transforms 8 x 8 samples held in registers
+ *    and stores the block's 64 int16 in ZIG-ZAG order: coeffs [n][tt_jpeg_blocks][64], blocks in scan order.  With counts != NULL a
+ *    second launch counts every frame's symbols (rule 6): counts [n][TT_JPEG_COUNT_WORDS = 4 x 256] uint32 -- DC luminance, AC
+ *    luminance, DC chrominance, AC chrominance, indexed by symbol.
+ *    TT_EINVAL: null frames / coeffs; n, h or w <= 0; ch not 1 or 3; quality outside 1 .. 100; subsampling not 0 or 2; coeffs or
+ *    counts off a 16-byte boundary.  TT_EUNSUPPORTED: a frame of 2^31 bytes or more; a scan bound of 2^31 bytes or more; n > 65535.
+ * 6. Entropy coding: baseline sequential Huffman, one interleaved scan, no restart markers.  DC: the difference to the previous
+ *    block of the same component in scan order (0 before the first), as its size category (the bits of |diff|) and that many
+ *    magnitude bits (diff, or diff - 1 when negative, low bits).  AC: over zig-zag 1 .. 63, symbol (run of zeros << 4 | size) with the
+ *    magnitude bits; 0xF0 stands for 16 zeros; 0x00 (EOB) only when the block ends in zeros.  Codes go MSB first, a 0x00 follows
+ *    every 0xFF byte, the last byte is filled with one-bits.
+ * 7. Huffman tables.  A table is BITS[16] (codes per length), HUFFVAL (symbols by ascending code) and, for the device, 256 uint32:
+ *    per symbol its canonical code (T.81 Annex C) | length << 16.  tt_jpeg_standard_table (host): `which` 0 .. 3 (DC luminance, AC
+ *    luminance, DC chrominance, AC chrominance) -> the Annex K.3 table.  tt_jpeg_optimized_table (host): counts[256] -> the table of
+ *    tt_png_code_lengths (limit 15) over 257 symbols -- entry 0 a reserved symbol of count 1, entries 1 .. 256 the counts --: first in
+ *    the package-merge's leaf order, the reserved symbol gets a longest code, and, placed last among the codes of that length, the
+ *    code of one-bits only, which therefore no real symbol has (T.81 Annex K.2); it is then dropped.  HUFFVAL is by (length, symbol).
+ *    TT_EINVAL: null pointer; which outside 0 .. 3.
+ *    tt_jpeg_scan: coeffs and tables [ntables][4][256] (ntables 1: one set for all frames; n: one per frame) -> every frame's finished,
+ *    stuffed scan at byte f tt_jpeg_scan_bound of out, and its length in lengths[f] (device uint32); bytes at or beyond the length are
+ *    not written.  Six launches and one memset for all frames, no host round trip: the bits of every block (one lane per block), an
+ *    exclusive scan over each frame's blocks (one workgroup per frame), the bits ORed MSB first into the zeroed unstuffed stream (a
+ *    lane's first and last 32-bit word are shared with its neighbours: integer atomic OR; the words between are stored), then per
+ *    TT_JPEG_CHUNK = 4096 bytes the count of 0xFF bytes, a scan of those counts, and the scatter with a 0x00 behind every 0xFF.
+ *    tt_jpeg_scan_bound: a block takes at most TT_JPEG_BLOCK_BITS = 64 x (16 + 11) bits, doubled for stuffing, plus the padded byte,
+ *    rounded up to 16.  ws: tt_jpeg_scan_ws_bytes of device scratch.  Whatever the tables hold, nothing is written outside out and ws.
+ *    TT_EINVAL: null coeffs / tables / out / lengths / ws; n, h or w <= 0; ch not 1 or 3; subsampling not 0 or 2; ntables not 1 or n;
+ *    coeffs, tables, out or ws off a 16-byte boundary; cap < n tt_jpeg_scan_bound ("cap too small"); ws_bytes too small.
+ *    TT_EUNSUPPORTED: as for tt_jpeg_coeffs.  Both entry points refuse before the first HIP call; no allocation, no synchronisation.
+ * 8. File (export.py): SOI; APP0 JFIF 1.01, units 0, density 1 x 1; one DQT marker per table (8-bit, zig-zag order); SOF0 (sampling
+ *    2 x 2 for Y in 4:2:0, else 1 x 1); one DHT marker per table; SOS; the scan; EOI. */
+#define TT_JPEG_444 0
+#define TT_JPEG_420 2
+#define TT_JPEG_TABLE_WORDS 256
+#define TT_JPEG_COUNT_WORDS 1024
+#define TT_JPEG_BLOCK_BITS 1728
+#define TT_JPEG_CHUNK 4096
+int64_t tt_jpeg_blocks(int32_t h, int32_t w, int32_t ch, int32_t subsampling);          /* 0 for arguments tt_jpeg_coeffs refuses */
+int64_t tt_jpeg_scan_bound(int32_t h, int32_t w, int32_t ch, int32_t subsampling);      /* a frame's stride in tt_jpeg_scan's out */
+int64_t tt_jpeg_scan_ws_bytes(int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling);
+int tt_jpeg_quant_tables(int32_t quality, uint8_t* tables /* host [2][64] */);
+int tt_jpeg_standard_table(int32_t which, uint8_t* bits /* host [16] */, uint8_t* huffval /* host [256] */, int32_t* nvals /* host */,
+                           uint32_t* codes /* host [256] */);
+int tt_jpeg_optimized_table(const uint32_t* counts /* host [256] */, uint8_t* bits /* host [16] */, uint8_t* huffval /* host [256] */,
+                            int32_t* nvals /* host */, uint32_t* codes /* host [256] */);
+int tt_jpeg_coeffs(const void* frames, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t quality, int32_t subsampling, int16_t* coeffs,
+                   uint32_t* counts /* or NULL */, tt_stream_t stream);
+int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables,
+                 int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

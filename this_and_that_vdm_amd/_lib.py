@@ -105,6 +105,7 @@ class TtColorBin(C.Structure):
 
 TT_GIF_BINS = 32768
 TT_PNG_STRIPE, TT_PNG_SYMS, TT_PNG_RECORD_WORDS, TT_PNG_TABLE_WORDS, TT_PNG_HEADER_WORDS = 32768, 286, 288, 288, 72
+TT_JPEG_444, TT_JPEG_420, TT_JPEG_TABLE_WORDS, TT_JPEG_COUNT_WORDS = 0, 2, 256, 1024
 
 _i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -204,6 +205,15 @@ SIGNATURES = {
     "tt_png_code_lengths": (C.c_int, [_vp, _i32, _i32, _vp]),
     "tt_png_block_header": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
     "tt_png_plan": (C.c_int, [_vp, _i64, _vp, _vp, C.POINTER(C.c_int64)]),
+    # the JPEG export: coefficients and the stuffed scan on the device, quantiser and Huffman tables on the host (additive as well)
+    "tt_jpeg_blocks": (_i64, [_i32, _i32, _i32, _i32]),
+    "tt_jpeg_scan_bound": (_i64, [_i32, _i32, _i32, _i32]),
+    "tt_jpeg_scan_ws_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "tt_jpeg_quant_tables": (C.c_int, [_i32, _vp]),
+    "tt_jpeg_standard_table": (C.c_int, [_i32, _vp, _vp, C.POINTER(C.c_int32), _vp]),
+    "tt_jpeg_optimized_table": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp]),
+    "tt_jpeg_coeffs": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "tt_jpeg_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

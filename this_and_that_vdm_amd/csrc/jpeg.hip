@@ -1,0 +1,527 @@
+// libttvdm: the device half of the JPEG export (include/ttvdm.h): tt_jpeg_coeffs -- colour conversion, 4:2:0 cell sums, the 8 x 8 integer
+// DCT, the quantiser and the zig-zag of every block of uint8 NHWC frames, in scan order, with the frames' symbol counts -- and
+// tt_jpeg_scan -- the Huffman-coded, byte-stuffed scan of every frame from those coefficients and a code table.
+// Integer arithmetic only; atomics are integer adds and ORs, which commute: every call gives the same bytes.
+#include "common.h"
+#include "jpeg_host.h"
+
+namespace {
+
+constexpr int CBLOCK = 256;                         // lanes of a coefficient tile: TILE_W pixels across, one MCU row down
+constexpr int TILE_W = 256;
+constexpr int SBLOCK = 256;                         // lanes of the per-block kernels (bits, counts, emit) and of a stuffing chunk
+constexpr int SCAN_BLOCK = 1024, SCAN_WAVES = SCAN_BLOCK / 64;
+constexpr int CHUNK = TT_JPEG_CHUNK;
+static_assert(CHUNK == 16 * SBLOCK, "a lane holds one 16-byte unit of a stuffing chunk");
+static_assert(TT_JPEG_COUNT_WORDS == 4 * TT_JPEG_TABLE_WORDS && TT_JPEG_TABLE_WORDS == 256, "four tables of 256 symbols");
+
+// ZZ[k]: the natural (row-major) index of the k-th coefficient of the zig-zag scan
+__device__ constexpr int ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ---------------------------------------------------------------- rule 2: colour
+__device__ __forceinline__ int to_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
+__device__ __forceinline__ int to_cb(int r, int g, int b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
+__device__ __forceinline__ int to_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
+
+// ---------------------------------------------------------------- rule 4: jfdctint's pass over eight values
+template <bool FIRST> __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+template <bool FIRST> __device__ __forceinline__ void fdct8(int& d0, int& d1, int& d2, int& d3, int& d4, int& d5, int& d6, int& d7) {
+  constexpr int N = FIRST ? 13 - 2 : 13 + 2;
+  const int t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  if (FIRST) { d0 = (t10 + t11) << 2; d4 = (t10 - t11) << 2; }
+  else { d0 = descale<FIRST>(t10 + t11, 2); d4 = descale<FIRST>(t10 - t11, 2); }
+  const int z1 = (t12 + t13) * 4433;
+  d2 = descale<FIRST>(z1 + t13 * 6270, N);
+  d6 = descale<FIRST>(z1 - t12 * 15137, N);
+  const int y1 = t4 + t7, y2 = t5 + t6, y3 = t4 + t6, y4 = t5 + t7, z5 = (y3 + y4) * 9633;
+  const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+  const int b1 = -y1 * 7373, b2 = -y2 * 20995, b3 = -y3 * 16069 + z5, b4 = -y4 * 3196 + z5;
+  d7 = descale<FIRST>(a4 + b1 + b3, N);
+  d5 = descale<FIRST>(a5 + b2 + b4, N);
+  d3 = descale<FIRST>(a6 + b2 + b3, N);
+  d1 = descale<FIRST>(a7 + b1 + b4, N);
+}
+
+// one pixel of frame `src` (h x w x ch) with both coordinates held inside the frame: edge replication
+__device__ __forceinline__ void pixel(const unsigned char* __restrict__ src, int h, int w, int ch, int y, int x, int& r, int& g, int& b) {
+  const unsigned char* p = src + ((long long)min(y, h - 1) * w + min(x, w - 1)) * ch;
+  r = p[0];
+  if (ch == 3) { g = p[1]; b = p[2]; } else { g = r; b = r; }
+}
+
+// grid (tiles per MCU row x MCU rows, n): a tile is one MCU row down and TILE_W pixels across.  SUB: 4:2:0 (16 x 16 MCUs of 6 blocks).
+// The tile's samples go to LDS once, converted (and, SUB, the chroma cells summed); then one lane per block transforms it.
+template <bool SUB> __global__ __launch_bounds__(CBLOCK) void jpeg_coeffs_kernel(const unsigned char* __restrict__ frames, int h, int w, int ch,
+                                                                                TtJpegGeometry geo, int tiles_x, TtJpegQuant quant,
+                                                                                short* __restrict__ coeffs, long long blocks) {
+  constexpr int MCU = SUB ? 16 : 8, ROWS = MCU, CW = SUB ? TILE_W / 2 : TILE_W, MCUS = TILE_W / MCU;
+  __shared__ __attribute__((aligned(16))) unsigned char y_s[ROWS][TILE_W];
+  __shared__ __attribute__((aligned(16))) unsigned char c_s[2][8][CW];
+  __shared__ int dc_s[MCUS][4];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x % tiles_x, mcu_y = blockIdx.x / tiles_x;
+  const int x0 = tile * TILE_W, y0 = mcu_y * MCU;
+  const unsigned char* __restrict__ src = frames + (long long)blockIdx.y * h * w * ch;
+  if (SUB) {
+    const int hc = (h + 1) >> 1;
+    for (int cell = tid; cell < 8 * CW; cell += CBLOCK) {
+      const int cy = cell / CW, cx = cell % CW;                      // the chroma sample of this tile; its 2 x 2 luminance samples
+      int sb = 0, sr = 0;
+      int r, g, b;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        pixel(src, h, w, ch, y0 + 2 * cy + (k >> 1), x0 + 2 * cx + (k & 1), r, g, b);
+        y_s[2 * cy + (k >> 1)][2 * cx + (k & 1)] = (unsigned char)to_y(r, g, b);
+        sb += to_cb(r, g, b);
+        sr += to_cr(r, g, b);
+      }
+      const int gy = (y0 >> 1) + cy;
+      if (gy >= hc) {                                                // below the chroma plane: its LAST ROW again, not the source's
+        sb = 0;
+        sr = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          pixel(src, h, w, ch, 2 * (hc - 1) + (k >> 1), x0 + 2 * cx + (k & 1), r, g, b);
+          sb += to_cb(r, g, b);
+          sr += to_cr(r, g, b);
+        }
+      }
+      const int bias = 1 + (cx & 1);                                 // x0 / 2 is even: the tile's parity is the plane's
+      c_s[0][cy][cx] = (unsigned char)((sb + bias) >> 2);
+      c_s[1][cy][cx] = (unsigned char)((sr + bias) >> 2);
+    }
+  } else {
+    for (int i = tid; i < 8 * TILE_W; i += CBLOCK) {
+      const int yy = i / TILE_W, xx = i % TILE_W;
+      int r, g, b;
+      pixel(src, h, w, ch, y0 + yy, x0 + xx, r, g, b);
+      if (ch == 3) {
+        y_s[yy][xx] = (unsigned char)to_y(r, g, b);
+        c_s[0][yy][xx] = (unsigned char)to_cb(r, g, b);
+        c_s[1][yy][xx] = (unsigned char)to_cr(r, g, b);
+      } else {
+        y_s[yy][xx] = (unsigned char)r;
+      }
+    }
+  }
+  __syncthreads();
+  // lane -> (MCU of the tile, block of the MCU)
+  const int bpm = geo.blocks_per_mcu;
+  const int m = tid / bpm, k = tid % bpm;
+  const int mcu_x = tile * MCUS + m;
+  const bool active = m < MCUS && mcu_x < geo.mcus_x;
+  bool real = active;
+  int comp = 0;
+  const unsigned char* base = &y_s[0][0];
+  int pitch = TILE_W;
+  if (SUB) {
+    if (k < 4) {
+      const int by = 2 * mcu_y + (k >> 1), bx = 2 * mcu_x + (k & 1);
+      real = active && by < (h + 7) / 8 && bx < (w + 7) / 8;
+      base = &y_s[(k >> 1) * 8][m * 16 + (k & 1) * 8];
+    } else {
+      comp = k - 3;
+      base = &c_s[k - 4][0][m * 8];
+      pitch = CW;
+    }
+  } else {
+    comp = k;
+    base = k == 0 ? &y_s[0][m * 8] : &c_s[k - 1][0][m * 8];
+  }
+  if (!active) base = &y_s[0][0];
+  short* __restrict__ out = coeffs + ((long long)blockIdx.y * blocks + ((long long)mcu_y * geo.mcus_x + mcu_x) * bpm + k) * 64;
+  if (real) {
+    int d[64];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const uint2 v = *(const uint2*)(base + r * pitch);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) d[r * 8 + c] = (int)(((c < 4 ? v.x : v.y) >> (8 * (c & 3))) & 0xffu) - 128;
+      fdct8<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) fdct8<false>(d[c], d[8 + c], d[16 + c], d[24 + c], d[32 + c], d[40 + c], d[48 + c], d[56 + c]);
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {                                   // rule 5
+      const int q = 8 * (int)(comp ? quant.q[1][i] : quant.q[0][i]);
+      const int v = d[i], mag = (int)((unsigned)(abs(v) + (q >> 1)) / (unsigned)q);
+      d[i] = v < 0 ? -mag : mag;
+    }
+    if (SUB && k < 4) dc_s[m][k] = d[0];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      unsigned wd[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wd[j] = ((unsigned)d[ZZ[8 * u + 2 * j]] & 0xffffu) | ((unsigned)d[ZZ[8 * u + 2 * j + 1]] << 16);
+      *(uint4*)(out + 8 * u) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+    }
+  }
+  if (SUB) {
+    __syncthreads();
+    if (active && !real) {                                           // a dummy block: the DC of the block coded before it in this MCU
+      int dc = dc_s[m][0];                                           // (block 0 of an MCU is never a dummy)
+      for (int j = 1; j < k; ++j) {
+        const int by = 2 * mcu_y + (j >> 1), bx = 2 * mcu_x + (j & 1);
+        if (by < (h + 7) / 8 && bx < (w + 7) / 8) dc = dc_s[m][j];
+      }
+      *(uint4*)out = make_uint4((unsigned)dc & 0xffffu, 0u, 0u, 0u);
+#pragma unroll
+      for (int u = 1; u < 8; ++u) *(uint4*)(out + 8 * u) = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- rule 6: a block's symbols
+// which component block b of a frame's scan belongs to (0 Y, else chroma), and the block whose DC it is coded against (-1: none)
+__device__ __forceinline__ void block_place(long long b, int bpm, int& chroma, long long& pred) {
+  const int k = (int)(b % bpm);
+  chroma = bpm == 6 ? k >= 4 : k > 0;
+  const long long back = bpm == 6 ? (k >= 4 ? 6 : (k == 0 ? 3 : 1)) : bpm;
+  pred = (bpm == 6 && k > 0 && k < 4) ? b - 1 : (b >= bpm ? b - back : -1);
+}
+__device__ __forceinline__ int category(int v) { return 32 - __clz(abs(v)); }
+__device__ __forceinline__ unsigned magnitude(int v, int n) { return (unsigned)(v < 0 ? v - 1 : v) & ((1u << n) - 1u); }
+
+// calls f(table: 0 DC / 1 AC, symbol, magnitude bits, how many of them) for every symbol of the block at `c` in order
+template <typename F> __device__ __forceinline__ void walk_block(const short* __restrict__ c, int pred_dc, F&& f) {
+  unsigned wd[32];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const uint4 v = *(const uint4*)(c + 8 * u);
+    wd[4 * u] = v.x; wd[4 * u + 1] = v.y; wd[4 * u + 2] = v.z; wd[4 * u + 3] = v.w;
+  }
+  const int diff = (int)(short)(wd[0] & 0xffffu) - pred_dc;
+  int n = category(diff);
+  f(0, n, magnitude(diff, n), n);
+  int run = 0;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    const int v = (int)(short)((wd[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+    if (v == 0) { ++run; continue; }
+    while (run > 15) { f(1, 0xF0, 0u, 0); run -= 16; }
+    n = category(v);
+    f(1, (run << 4) | n, magnitude(v, n), n);
+    run = 0;
+  }
+  if (run > 0) f(1, 0x00, 0u, 0);
+}
+
+__device__ __forceinline__ int pred_of(const short* __restrict__ frame_coeffs, long long pred) { return pred < 0 ? 0 : (int)frame_coeffs[pred * 64]; }
+
+// grid (ceil(blocks / SBLOCK), n): one lane per block; the frame's counts are summed in LDS first
+__global__ __launch_bounds__(SBLOCK) void jpeg_counts_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, unsigned* __restrict__ counts) {
+  __shared__ unsigned cnt_s[TT_JPEG_COUNT_WORDS];
+  for (int i = threadIdx.x; i < TT_JPEG_COUNT_WORDS; i += SBLOCK) cnt_s[i] = 0u;
+  __syncthreads();
+  const long long b = (long long)blockIdx.x * SBLOCK + threadIdx.x;
+  const short* __restrict__ fc = coeffs + (long long)blockIdx.y * blocks * 64;
+  if (b < blocks) {
+    int chroma;
+    long long pred;
+    block_place(b, bpm, chroma, pred);
+    unsigned* t = cnt_s + (chroma ? 2 * TT_JPEG_TABLE_WORDS : 0);
+    walk_block(fc + b * 64, pred_of(fc, pred), [&](int ac, int sym, unsigned, int) { atomicAdd(&t[ac * TT_JPEG_TABLE_WORDS + (sym & 0xff)], 1u); });
+  }
+  __syncthreads();
+  unsigned* __restrict__ dst = counts + (long long)blockIdx.y * TT_JPEG_COUNT_WORDS;
+  for (int i = threadIdx.x; i < TT_JPEG_COUNT_WORDS; i += SBLOCK)
+    if (cnt_s[i]) atomicAdd(&dst[i], cnt_s[i]);
+}
+
+__device__ __forceinline__ void load_tables(unsigned* tab_s, const unsigned* __restrict__ tables, int ntables) {
+  const unsigned* __restrict__ t = tables + (ntables > 1 ? (long long)blockIdx.y * TT_JPEG_COUNT_WORDS : 0);
+  for (int i = threadIdx.x; i < TT_JPEG_COUNT_WORDS; i += SBLOCK) tab_s[i] = t[i];
+  __syncthreads();
+}
+// a symbol's code and its length; whatever the table holds, a code with its magnitude bits stays within 16 + 11 bits
+__device__ __forceinline__ void code_of(const unsigned* t, int ac, int sym, unsigned& code, int& len) {
+  const unsigned e = t[ac * TT_JPEG_TABLE_WORDS + (sym & 0xff)];
+  len = (int)min(e >> 16, 16u);
+  code = e & ((1u << len) - 1u);
+}
+
+// the bits of every block: grid as jpeg_counts_kernel
+__global__ __launch_bounds__(SBLOCK) void jpeg_bits_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, const unsigned* __restrict__ tables,
+                                                           int ntables, unsigned* __restrict__ bits) {
+  __shared__ unsigned tab_s[TT_JPEG_COUNT_WORDS];
+  load_tables(tab_s, tables, ntables);
+  const long long b = (long long)blockIdx.x * SBLOCK + threadIdx.x;
+  if (b >= blocks) return;
+  const short* __restrict__ fc = coeffs + (long long)blockIdx.y * blocks * 64;
+  int chroma;
+  long long pred;
+  block_place(b, bpm, chroma, pred);
+  const unsigned* t = tab_s + (chroma ? 2 * TT_JPEG_TABLE_WORDS : 0);
+  unsigned total = 0u;
+  walk_block(fc + b * 64, pred_of(fc, pred), [&](int ac, int sym, unsigned, int n) {
+    unsigned code;
+    int len;
+    code_of(t, ac, sym, code, len);
+    total += (unsigned)(len + min(n, 11));
+  });
+  bits[(long long)blockIdx.y * blocks + b] = total;
+}
+
+// an exclusive scan of v[0 .. count) in place, one workgroup; returns the sum.  red_s: SCAN_WAVES + 1 words
+__device__ __forceinline__ unsigned scan_in_place(unsigned* __restrict__ v, long long count, unsigned* red_s) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned carry = 0u;
+  for (long long at = 0; at < count; at += SCAN_BLOCK) {
+    const long long i = at + tid;
+    const unsigned mine = i < count ? v[i] : 0u;
+    unsigned incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned a = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += a;
+    }
+    if (lane == 63) red_s[wave] = incl;
+    __syncthreads();
+    unsigned before = carry + incl - mine, all = 0u;
+    for (int wv = 0; wv < SCAN_WAVES; ++wv) {
+      if (wv < wave) before += red_s[wv];
+      all += red_s[wv];
+    }
+    if (i < count) v[i] = before;
+    carry += all;
+    __syncthreads();
+  }
+  return carry;
+}
+
+// grid (n): the blocks' bit offsets inside their frame, and the frame's unstuffed bytes
+__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_offsets_kernel(unsigned* __restrict__ bits, long long blocks, unsigned* __restrict__ plain_bytes) {
+  __shared__ unsigned red_s[SCAN_WAVES + 1];
+  const unsigned total = scan_in_place(bits + (long long)blockIdx.x * blocks, blocks, red_s);
+  if (threadIdx.x == 0) plain_bytes[blockIdx.x] = (total + 7u) >> 3;
+}
+
+// the bits themselves, MSB first, into 32-bit words whose most significant byte is the stream's first: one lane per block.  A lane's
+// first and last word are shared with its neighbours (OR); the words between are its own.  `words` is zeroed before.
+struct BitWriter {
+  unsigned* __restrict__ words;
+  long long limit;             // words of the frame's region
+  unsigned long long acc;
+  int nacc;
+  long long word;
+  bool first;
+  __device__ __forceinline__ void put(unsigned v, int len) {
+    acc = (acc << len) | v;
+    nacc += len;
+    if (nacc >= 32) {
+      nacc -= 32;
+      const unsigned out = (unsigned)(acc >> nacc);
+      if (word < limit) {
+        if (first) atomicOr(&words[word], out); else words[word] = out;
+      }
+      first = false;
+      ++word;
+    }
+  }
+  __device__ __forceinline__ void flush() {
+    if (nacc > 0 && word < limit) atomicOr(&words[word], (unsigned)(acc << (32 - nacc)));
+  }
+};
+
+__global__ __launch_bounds__(SBLOCK) void jpeg_emit_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, const unsigned* __restrict__ tables,
+                                                           int ntables, const unsigned* __restrict__ offsets, unsigned* __restrict__ plain, long long plain_stride) {
+  __shared__ unsigned tab_s[TT_JPEG_COUNT_WORDS];
+  load_tables(tab_s, tables, ntables);
+  const long long b = (long long)blockIdx.x * SBLOCK + threadIdx.x;
+  if (b >= blocks) return;
+  const short* __restrict__ fc = coeffs + (long long)blockIdx.y * blocks * 64;
+  int chroma;
+  long long pred;
+  block_place(b, bpm, chroma, pred);
+  const unsigned* t = tab_s + (chroma ? 2 * TT_JPEG_TABLE_WORDS : 0);
+  const unsigned at = offsets[(long long)blockIdx.y * blocks + b];
+  BitWriter bw{plain + (long long)blockIdx.y * (plain_stride / 4), plain_stride / 4, 0ull, (int)(at & 31u), (long long)(at >> 5), true};
+  unsigned pos = at;
+  walk_block(fc + b * 64, pred_of(fc, pred), [&](int ac, int sym, unsigned mag, int n) {
+    unsigned code;
+    int len;
+    code_of(t, ac, sym, code, len);
+    n = min(n, 11);
+    bw.put((code << n) | (mag & ((1u << n) - 1u)), len + n);
+    pos += (unsigned)(len + n);
+  });
+  if (b == blocks - 1 && (pos & 7u)) {                               // the frame's last byte is filled with one-bits
+    const int pad = 8 - (int)(pos & 7u);
+    bw.put((1u << pad) - 1u, pad);
+  }
+  bw.flush();
+}
+
+// ---------------------------------------------------------------- byte stuffing: count the FF bytes per chunk, scan, scatter
+// the lane's 16 bytes of its frame's unstuffed stream, in stream order; `have`: how many of them are inside the stream
+__device__ __forceinline__ void chunk_bytes(const unsigned* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
+                                            unsigned by[4], int& have, long long& at) {
+  at = (long long)blockIdx.x * CHUNK + 16 * threadIdx.x;
+  const long long total = min((long long)plain_bytes[blockIdx.y], plain_stride);
+  have = (int)max(0ll, min(16ll, total - at));
+  by[0] = by[1] = by[2] = by[3] = 0u;
+  if (have > 0) {
+    const uint4 v = *(const uint4*)((const unsigned char*)plain + (long long)blockIdx.y * plain_stride + at);
+    by[0] = v.x; by[1] = v.y; by[2] = v.z; by[3] = v.w;
+  }
+}
+__device__ __forceinline__ unsigned byte_at(const unsigned by[4], int j) { return (by[j >> 2] >> (24 - 8 * (j & 3))) & 0xffu; }
+
+// grid (chunks, n)
+__global__ __launch_bounds__(SBLOCK) void jpeg_ff_count_kernel(const unsigned* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
+                                                               unsigned* __restrict__ chunk_ff, int chunks) {
+  __shared__ unsigned red_s[SBLOCK / 64];
+  unsigned by[4];
+  int have;
+  long long at;
+  chunk_bytes(plain, plain_stride, plain_bytes, by, have, at);
+  unsigned ff = 0u;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ff += __shfl_down(ff, o, 64);
+  if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = ff;
+  __syncthreads();
+  if (threadIdx.x == 0) chunk_ff[(long long)blockIdx.y * chunks + blockIdx.x] = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+}
+
+// grid (n): the FF bytes before every chunk, and the frame's stuffed length
+__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_ff_scan_kernel(unsigned* __restrict__ chunk_ff, int chunks, const unsigned* __restrict__ plain_bytes,
+                                                                  unsigned* __restrict__ lengths) {
+  __shared__ unsigned red_s[SCAN_WAVES + 1];
+  const unsigned total = scan_in_place(chunk_ff + (long long)blockIdx.x * chunks, chunks, red_s);
+  if (threadIdx.x == 0) lengths[blockIdx.x] = plain_bytes[blockIdx.x] + total;
+}
+
+// grid (chunks, n)
+__global__ __launch_bounds__(SBLOCK) void jpeg_stuff_kernel(const unsigned* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
+                                                            const unsigned* __restrict__ chunk_ff, int chunks, unsigned char* __restrict__ out, long long stride) {
+  __shared__ unsigned red_s[SBLOCK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned by[4];
+  int have;
+  long long at;
+  chunk_bytes(plain, plain_stride, plain_bytes, by, have, at);
+  unsigned ff = 0u;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu;
+  unsigned incl = ff;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned a = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += a;
+  }
+  if (lane == 63) red_s[wave] = incl;
+  __syncthreads();
+  unsigned before = incl - ff;
+  for (int wv = 0; wv < wave; ++wv) before += red_s[wv];
+  long long pos = at + chunk_ff[(long long)blockIdx.y * chunks + blockIdx.x] + before;
+  unsigned char* __restrict__ dst = out + (long long)blockIdx.y * stride;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    if (j < have) {
+      const unsigned v = byte_at(by, j);
+      if (pos < stride) dst[pos] = (unsigned char)v;
+      ++pos;
+      if (v == 0xffu) {
+        if (pos < stride) dst[pos] = 0;
+        ++pos;
+      }
+    }
+  }
+}
+
+int refuse_shape(const char* who, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling) {
+  if (n <= 0 || h <= 0 || w <= 0) TT_FAIL(TT_EINVAL, "%s: empty problem (n = %d, h = %d, w = %d)", who, n, h, w);
+  if (ch != 1 && ch != 3) TT_FAIL(TT_EINVAL, "%s: %d channels (1: grey, or 3: RGB; JPEG has no alpha)", who, ch);
+  if (subsampling != TT_JPEG_444 && subsampling != TT_JPEG_420)
+    TT_FAIL(TT_EINVAL, "%s: subsampling = %d (0: 4:4:4, or 2: 4:2:0)", who, subsampling);
+  if ((long long)h * w * ch >= (1ll << 31)) TT_FAIL(TT_EUNSUPPORTED, "%s: a frame of %lld bytes (below 2^31)", who, (long long)h * w * ch);
+  if (tt_jpeg_scan_bound(h, w, ch, subsampling) >= (1ll << 31))
+    TT_FAIL(TT_EUNSUPPORTED, "%s: a scan bound of %lld bytes per frame (below 2^31)", who, (long long)tt_jpeg_scan_bound(h, w, ch, subsampling));
+  if (n > 65535) TT_FAIL(TT_EUNSUPPORTED, "%s: %d frames: more than one grid covers (65535)", who, n);
+  return TT_OK;
+}
+
+}  // namespace
+
+extern "C" int tt_jpeg_coeffs(const void* frames, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t quality, int32_t subsampling, int16_t* coeffs,
+                              uint32_t* counts, tt_stream_t stream) {
+  if (!frames || !coeffs) TT_FAIL(TT_EINVAL, "tt_jpeg_coeffs: null %s", !frames ? "frames" : "coeffs");
+  const int rc = refuse_shape("tt_jpeg_coeffs", n, h, w, ch, subsampling);
+  if (rc != TT_OK) return rc;
+  if (quality < 1 || quality > 100) TT_FAIL(TT_EINVAL, "tt_jpeg_coeffs: quality = %d (1 to 100)", quality);
+  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_coeffs: coeffs is not 16-byte aligned");
+  if ((uintptr_t)counts & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_coeffs: counts is not 16-byte aligned");
+  const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
+  const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
+  TtJpegQuant quant;
+  tt_jpeg_fill_quant(quality, &quant);
+  const bool sub = geo.blocks_per_mcu == 6;
+  const int tiles_x = (geo.mcus_x * (sub ? 16 : 8) + TILE_W - 1) / TILE_W;
+  const dim3 grid((unsigned)(tiles_x * geo.mcus_y), (unsigned)n);
+  if (sub)
+    hipLaunchKernelGGL(jpeg_coeffs_kernel<true>, grid, dim3(CBLOCK), 0, (hipStream_t)stream, (const unsigned char*)frames, (int)h, (int)w, (int)ch, geo,
+                       tiles_x, quant, (short*)coeffs, blocks);
+  else
+    hipLaunchKernelGGL(jpeg_coeffs_kernel<false>, grid, dim3(CBLOCK), 0, (hipStream_t)stream, (const unsigned char*)frames, (int)h, (int)w, (int)ch, geo,
+                       tiles_x, quant, (short*)coeffs, blocks);
+  if (counts) {
+    const hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * TT_JPEG_COUNT_WORDS * sizeof(uint32_t), (hipStream_t)stream);
+    if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "tt_jpeg_coeffs: zeroing counts: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(jpeg_counts_kernel, dim3((unsigned)((blocks + SBLOCK - 1) / SBLOCK), (unsigned)n), dim3(SBLOCK), 0, (hipStream_t)stream,
+                       (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, (unsigned*)counts);
+  }
+  TT_CHECK_LAUNCH("tt_jpeg_coeffs");
+  return TT_OK;
+}
+
+extern "C" int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables,
+                            int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  if (!coeffs || !tables || !out || !lengths || !ws)
+    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: null %s", !coeffs ? "coeffs" : (!tables ? "tables" : (!out ? "out" : (!lengths ? "lengths" : "ws"))));
+  const int rc = refuse_shape("tt_jpeg_scan", n, h, w, ch, subsampling);
+  if (rc != TT_OK) return rc;
+  if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ntables = %d (1, or one set per frame: %d)", ntables, n);
+  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: coeffs is not 16-byte aligned");
+  if ((uintptr_t)tables & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: tables is not 16-byte aligned");
+  if ((uintptr_t)out & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: out is not 16-byte aligned");
+  if ((uintptr_t)lengths & 3) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: lengths is not 4-byte aligned");
+  if ((uintptr_t)ws & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ws is not 16-byte aligned");
+  const long long stride = tt_jpeg_scan_bound(h, w, ch, subsampling);
+  if (cap < (long long)n * stride)
+    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: cap too small: %lld bytes, %d frames at tt_jpeg_scan_bound = %lld take %lld", (long long)cap, n, stride, (long long)n * stride);
+  if (ws_bytes < tt_jpeg_scan_ws_bytes(n, h, w, ch, subsampling))
+    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ws too small: %lld bytes, tt_jpeg_scan_ws_bytes = %lld", (long long)ws_bytes,
+            (long long)tt_jpeg_scan_ws_bytes(n, h, w, ch, subsampling));
+  const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
+  const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
+  const auto up = [](long long v) { return (v + 15) / 16 * 16; };
+  const long long plain_stride = up(stride / 2);                   // the layout tt_jpeg_scan_ws_bytes sizes
+  const int chunks = (int)((stride / 2 + CHUNK - 1) / CHUNK);
+  char* p = (char*)ws;
+  unsigned* bits = (unsigned*)p;
+  p += up(4 * n * blocks);
+  unsigned* plain_bytes = (unsigned*)p;
+  p += up(4 * (long long)n);
+  unsigned* chunk_ff = (unsigned*)p;
+  p += up(4ll * n * chunks);
+  unsigned* plain = (unsigned*)p;
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 per_block((unsigned)((blocks + SBLOCK - 1) / SBLOCK), (unsigned)n), per_chunk((unsigned)chunks, (unsigned)n);
+  const hipError_t e = hipMemsetAsync(plain, 0, (size_t)(n * plain_stride), s);
+  if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "tt_jpeg_scan: zeroing ws: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(jpeg_bits_kernel, per_block, dim3(SBLOCK), 0, s, (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, (const unsigned*)tables,
+                     (int)ntables, bits);
+  hipLaunchKernelGGL(jpeg_offsets_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, bits, blocks, plain_bytes);
+  hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(SBLOCK), 0, s, (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, (const unsigned*)tables,
+                     (int)ntables, (const unsigned*)bits, plain, plain_stride);
+  hipLaunchKernelGGL(jpeg_ff_count_kernel, per_chunk, dim3(SBLOCK), 0, s, (const unsigned*)plain, plain_stride, (const unsigned*)plain_bytes, chunk_ff, chunks);
+  hipLaunchKernelGGL(jpeg_ff_scan_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, chunk_ff, chunks, (const unsigned*)plain_bytes, (unsigned*)lengths);
+  hipLaunchKernelGGL(jpeg_stuff_kernel, per_chunk, dim3(SBLOCK), 0, s, (const unsigned*)plain, plain_stride, (const unsigned*)plain_bytes,
+                     (const unsigned*)chunk_ff, chunks, (unsigned char*)out, stride);
+  TT_CHECK_LAUNCH("tt_jpeg_scan");
+  return TT_OK;
+}

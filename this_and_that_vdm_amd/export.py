@@ -20,7 +20,18 @@ routines of the library):
 ``png_streams``: ONE filter launch and ONE tokens launch for all frames, one readback of 1152 bytes per 32 KiB stripe, package-merge and
 the dynamic-block headers on the host, one upload of the tables and headers, ONE emit launch, one readback of the finished compressed
 streams -- the filtered bytes never leave the device.  Not here: LZ77 matches beyond distance 1, a stored-block fallback, 16-bit or
-palette PNGs, interlace, ancillary chunks."""
+palette PNGs, interlace, ancillary chunks.
+
+... and as baseline JPEG files and a Motion-JPEG AVI (``tt_jpeg_coeffs`` / ``tt_jpeg_scan``; the quantiser and Huffman tables are host
+routines of the library):
+
+    write_jpegs(pipe(..., output_type="device").frames[0], folder)       # folder/im_0.jpg, im_1.jpg, ...: the data loaders' layout
+    write_mjpeg(frames, "clip.avi", fps=4)                               # Motion-JPEG, NOT H.264: a browser will not play it
+
+``encode_jpeg``: ONE launch from pixels to zig-zag coefficients for all frames, then the bits of every block, a scan for their
+positions, the bits themselves and the byte stuffing, with no host round trip in between when the standard Huffman tables are used;
+the lengths and the finished scans are read back.  With the standard tables the scan equals libjpeg's (Pillow's) byte for byte.
+Not here: progressive or arithmetic coding, 4:2:2, restart markers, EXIF / ICC, CMYK, 12 bits, trellis quantisation, a decoder."""
 from __future__ import annotations
 
 import ctypes as C
@@ -381,3 +392,258 @@ def write_apng(frames, path_or_file, duration: float = 0.05, loop: int = 0, filt
     else:
         with open(path_or_file, "wb") as fh:
             fh.write(data)
+
+
+# ---- frames -> baseline JPEG files and a Motion-JPEG AVI: colour conversion, chroma downsampling, the integer DCT, the quantiser, the
+# Huffman-coded bits and the byte stuffing are made on the device (include/ttvdm.h, "JPEG export", rules 1 - 8); the host sees the
+# finished scans and their lengths (and 4 KiB of symbol counts per frame when it makes optimized tables)
+JPEG_TABLE_NAMES = ("DC luminance", "AC luminance", "DC chrominance", "AC chrominance")
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_JPEG_STANDARD = {}          # device -> the standard code tables there
+
+
+@dataclass
+class JpegTable:
+    """One Huffman table: ``bits`` (codes per length 1 .. 16), ``huffval`` (the symbols by ascending code) -- what a DHT marker holds --
+    and ``codes`` uint32 [256]: per symbol its code | length << 16, what the device reads."""
+    bits: list
+    huffval: list
+    codes: np.ndarray
+
+
+def jpeg_quant_tables(quality: int) -> np.ndarray:
+    """-> uint8 [2, 64]: the luminance and chrominance quantiser tables of ``quality`` in natural order (tt_jpeg_quant_tables)"""
+    out = np.zeros((2, 64), dtype=np.uint8)
+    check(_lib.load().tt_jpeg_quant_tables(int(quality), out.ctypes.data), "tt_jpeg_quant_tables")
+    return out
+
+
+def _jpeg_table(call, what: str) -> JpegTable:
+    bits, vals, codes, n = np.zeros(16, dtype=np.uint8), np.zeros(256, dtype=np.uint8), np.zeros(256, dtype=np.uint32), C.c_int32(0)
+    check(call(bits.ctypes.data, vals.ctypes.data, C.byref(n), codes.ctypes.data), what)
+    return JpegTable(bits.tolist(), vals[:n.value].tolist(), codes)
+
+
+def jpeg_standard_tables() -> list:
+    """-> the four T.81 Annex K.3 tables, in the order of JPEG_TABLE_NAMES (tt_jpeg_standard_table)"""
+    lib = _lib.load()
+    return [_jpeg_table(lambda *a, k=k: lib.tt_jpeg_standard_table(k, *a), "tt_jpeg_standard_table") for k in range(4)]
+
+
+def jpeg_optimized_table(counts) -> JpegTable:
+    """256 symbol counts -> the table with the least total bits among codes of at most 15 bits that leave the all-ones code free
+    (tt_jpeg_optimized_table)"""
+    lib = _lib.load()
+    c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    if c.size != 256:
+        raise ValueError(f"jpeg_optimized_table: 256 counts, got {c.size}")
+    return _jpeg_table(lambda *a: lib.tt_jpeg_optimized_table(c.ctypes.data, *a), "tt_jpeg_optimized_table")
+
+
+def _jpeg_segment(marker: int, payload: bytes) -> bytes:
+    return b"\xff" + bytes([marker]) + struct.pack(">H", len(payload) + 2) + payload
+
+
+def jpeg_file(scan: bytes, height: int, width: int, channels: int, quality: int, subsampling: str, tables: list) -> bytes:
+    """one frame's entropy-coded scan -> its file (rule 8): SOI, APP0 JFIF 1.01, a DQT marker per quantiser table, SOF0, a DHT marker
+    per Huffman table, SOS, the scan, EOI -- the layout libjpeg writes"""
+    qt = jpeg_quant_tables(quality)
+    grey = channels == 1
+    out = [b"\xff\xd8", _jpeg_segment(0xe0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    for i in range(1 if grey else 2):
+        out.append(_jpeg_segment(0xdb, bytes([i]) + bytes(int(qt[i][z]) for z in _JPEG_ZIGZAG)))
+    luma = 0x22 if (not grey and subsampling == "4:2:0") else 0x11
+    sof = struct.pack(">BHHB", 8, height, width, 1 if grey else 3) + bytes([1, luma, 0]) + (b"" if grey else bytes([2, 0x11, 1, 3, 0x11, 1]))
+    out.append(_jpeg_segment(0xc0, sof))
+    for i in range(2 if grey else 4):
+        out.append(_jpeg_segment(0xc4, bytes([((i & 1) << 4) | (i >> 1)]) + bytes(tables[i].bits) + bytes(tables[i].huffval)))
+    sos = bytes([1 if grey else 3, 1, 0x00]) + (b"" if grey else bytes([2, 0x11, 3, 0x11])) + bytes([0, 63, 0])
+    out += [_jpeg_segment(0xda, sos), scan, b"\xff\xd9"]
+    return b"".join(out)
+
+
+def _jpeg_args(quality, subsampling, huffman, who: str):
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"{who}: quality {quality!r} (an integer, 1 to 100)")
+    if subsampling not in ("4:4:4", "4:2:0"):
+        raise ValueError(f"{who}: subsampling {subsampling!r} ('4:4:4' or '4:2:0'; 4:2:2 is not offered)")
+    if huffman not in ("standard", "optimized"):
+        raise ValueError(f"{who}: huffman {huffman!r} ('standard' or 'optimized')")
+    return int(quality)
+
+
+def encode_jpeg(frames, quality: int = 75, subsampling: str = "4:2:0", huffman: str = "standard") -> list:
+    """Frames -> one baseline JPEG file (bytes) per frame.  ``frames``: what ``write_gif`` takes, with 1 channel (grey, [F, H, W, 1]) or
+    3 (RGB) -- a device uint8 / float32 NHWC tensor, ``DevicePixels``, numpy, a list of PIL images or a pipeline's "pil" / "np" /
+    "device" output for ONE video; floating-point frames are rounded as for ``write_gif``.  ``quality`` 1 .. 100 scales the Annex K
+    quantiser tables as libjpeg does; ``subsampling`` "4:2:0" or "4:4:4" (a grey frame has no chroma and ignores it); ``huffman``
+    "standard" (the Annex K.3 tables: no host round trip between the first launch and the readback, and the scan equals libjpeg's
+    byte for byte) or "optimized" (per-frame tables from symbol counts taken on the device: one more readback of 4 KiB per frame).
+    Only the finished scans and their lengths cross to the host.  The same frames give the same bytes from host and device copies."""
+    from . import ops
+    quality = _jpeg_args(quality, subsampling, huffman, "encode_jpeg")
+    src, shape, _ = _describe(frames, "encode_jpeg")
+    if shape[-1] not in (1, 3):
+        raise ValueError(f"encode_jpeg: 1 (grey) or 3 (RGB) channels -- JPEG has no alpha --, got {shape[-1]} in {shape}")
+    if shape[-3] > 65535 or shape[-2] > 65535:
+        raise ValueError(f"encode_jpeg: a JPEG is at most 65535 pixels a side, got {shape[-3]} x {shape[-2]}")
+    x = _frames_u8(src, "encode_jpeg", rgb=False)
+    f, h, w, ch = x.shape
+    optimized = huffman == "optimized"
+    coeffs, counts = ops.jpeg_coeffs(x, quality, subsampling, counts=optimized)
+    if optimized:
+        cnt = counts.cpu().numpy().view(np.uint32)                                             # the extra readback: 4 KiB per frame
+        per_frame = [[jpeg_optimized_table(cnt[i, k]) for k in range(4)] for i in range(f)]
+        tables = torch.from_numpy(np.stack([np.stack([t.codes for t in ts]) for ts in per_frame]).view(np.int32)).to(x.device)
+    else:
+        standard = jpeg_standard_tables()
+        per_frame = [standard] * f
+        tables = _JPEG_STANDARD.get(x.device)
+        if tables is None:
+            tables = _JPEG_STANDARD[x.device] = torch.from_numpy(np.stack([t.codes for t in standard]).view(np.int32)[None]).to(x.device)
+    out, lengths = ops.jpeg_scan(coeffs, (h, w, ch), subsampling, tables)
+    lens = lengths.cpu().numpy().astype(np.int64)                                              # readback 1: one length per frame
+    packed = torch.cat([out[i, :int(lens[i])] for i in range(f)]).cpu().numpy()                # readback 2: the finished scans, no padding
+    ends = np.cumsum(lens)
+    return [jpeg_file(packed[int(e - n):int(e)].tobytes(), h, w, ch, quality, subsampling, per_frame[i]) for i, (e, n) in enumerate(zip(ends, lens))]
+
+
+def write_jpegs(frames, folder, pattern: str = "im_{idx}.jpg", **kw) -> list:
+    """``encode_jpeg(frames, **kw)`` written as ``folder/pattern.format(idx=i)`` -- im_0.jpg, im_1.jpg, ...: the layout the data loaders
+    read a clip from -- ; returns the paths.  The folder is made when it does not exist."""
+    import os
+    files = encode_jpeg(frames, **kw)
+    os.makedirs(folder, exist_ok=True)
+    paths = [os.path.join(folder, pattern.format(idx=i)) for i in range(len(files))]
+    if len(set(paths)) != len(paths):
+        raise ValueError(f"write_jpegs: pattern {pattern!r} names two frames alike (use {{idx}})")
+    for path, data in zip(paths, files):
+        with open(path, "wb") as fh:
+            fh.write(data)
+    return paths
+
+
+def _jpeg_size(data: bytes):
+    """(height, width) from a baseline JPEG's SOF0"""
+    at = 2
+    while at + 4 <= len(data) and data[at] == 0xff:
+        (size,) = struct.unpack(">H", data[at + 2:at + 4])
+        if data[at + 1] == 0xc0:
+            return struct.unpack(">HH", data[at + 5:at + 9])
+        at += 2 + size
+    raise ValueError("write_mjpeg: a frame is not a baseline JPEG (no SOF0)")
+
+
+def _riff_chunk(tag: bytes, payload: bytes) -> bytes:
+    return tag + struct.pack("<I", len(payload)) + payload + (b"\x00" if len(payload) & 1 else b"")
+
+
+def mjpeg_avi(files: list, fps=4) -> bytes:
+    """JPEG files of one size -> a Motion-JPEG AVI: RIFF 'AVI ', LIST hdrl (avih, LIST strl (strh vids / MJPG with rate / scale = fps,
+    strf: a BITMAPINFOHEADER, compression MJPG, 24 bits)), LIST movi (one 00dc chunk per frame, padded to even), idx1 (every frame a
+    key frame, offsets from the movi tag).  Motion-JPEG is NOT H.264: a browser does not play it."""
+    from fractions import Fraction
+    if not files:
+        raise ValueError("write_mjpeg: no frames")
+    rate = Fraction(fps).limit_denominator(100000) if not isinstance(fps, Fraction) else fps
+    if rate <= 0 or rate.numerator >= 1 << 32:
+        raise ValueError(f"write_mjpeg: fps = {fps} (positive)")
+    sizes = {_jpeg_size(d) for d in files}
+    if len(sizes) != 1:
+        raise ValueError(f"write_mjpeg: frames of several sizes: {sorted(sizes)}")
+    (h, w), n, largest = sizes.pop(), len(files), max(len(d) for d in files)
+    movi, index, at = [b"movi"], [], 4
+    for d in files:
+        index.append(struct.pack("<4sIII", b"00dc", 0x10, at, len(d)))
+        chunk = _riff_chunk(b"00dc", d)
+        movi.append(chunk)
+        at += len(chunk)
+    usec = int(round(1e6 / float(rate)))
+    avih = struct.pack("<14I", usec, int(largest * float(rate)) + 1, 0, 0x10, n, 0, 1, largest, w, h, 0, 0, 0, 0)
+    strh = struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, rate.denominator, rate.numerator, 0, n, largest, 0xffffffff, 0, 0, 0, w, h)
+    strf = struct.pack("<IiiHH4sIiiII", 40, w, h, 1, 24, b"MJPG", w * h * 3, 0, 0, 0, 0)
+    strl = _riff_chunk(b"LIST", b"strl" + _riff_chunk(b"strh", strh) + _riff_chunk(b"strf", strf))
+    hdrl = _riff_chunk(b"LIST", b"hdrl" + _riff_chunk(b"avih", avih) + strl)
+    body = b"AVI " + hdrl + _riff_chunk(b"LIST", b"".join(movi)) + _riff_chunk(b"idx1", b"".join(index))
+    if len(body) >= 1 << 32:
+        raise ValueError(f"write_mjpeg: {len(body)} bytes do not fit a RIFF file (below 4 GiB)")
+    return b"RIFF" + struct.pack("<I", len(body)) + body
+
+
+def write_mjpeg(frames, path_or_file, fps=4, **kw) -> None:
+    """``encode_jpeg(frames, **kw)`` as ONE Motion-JPEG AVI (``mjpeg_avi``) at ``fps`` frames a second (an integer, a float or a Fraction);
+    a path or a binary file object.  NOT H.264 and not what a browser plays."""
+    data = mjpeg_avi(encode_jpeg(frames, **kw), fps)
+    if hasattr(path_or_file, "write"):
+        path_or_file.write(data)
+    else:
+        with open(path_or_file, "wb") as fh:
+            fh.write(data)
+
+
+def read_mjpeg(path_or_bytes) -> dict:
+    """A small RIFF walker for the AVI ``write_mjpeg`` writes -> {"frames": [bytes], "fps": Fraction, "width", "height", "total_frames",
+    "handler", "compression", "index": [(flags, offset, size)]}.  Raises ValueError where the structure is not consistent: a chunk
+    that overruns its parent, a RIFF size that is not the file's, an idx1 entry that does not point at its 00dc chunk."""
+    from fractions import Fraction
+    if isinstance(path_or_bytes, (bytes, bytearray)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as fh:
+            data = fh.read()
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"AVI ":
+        raise ValueError("read_mjpeg: not a RIFF AVI file")
+    if struct.unpack("<I", data[4:8])[0] != len(data) - 8:
+        raise ValueError(f"read_mjpeg: the RIFF size {struct.unpack('<I', data[4:8])[0]} is not the file's {len(data) - 8}")
+    info = {"frames": [], "index": []}
+    movi_at = None
+    frame_at = []
+
+    def walk(at, end):
+        nonlocal movi_at
+        while at < end:
+            if at + 8 > end:
+                raise ValueError(f"read_mjpeg: a chunk header at {at} overruns its parent (ends at {end})")
+            tag, (size,) = data[at:at + 4], struct.unpack("<I", data[at + 4:at + 8])
+            body, stop = at + 8, at + 8 + size
+            if stop > end:
+                raise ValueError(f"read_mjpeg: chunk {tag!r} at {at} overruns its parent ({stop} > {end})")
+            if tag == b"LIST":
+                if data[body:body + 4] == b"movi":
+                    movi_at = body
+                walk(body + 4, stop)
+            elif tag == b"avih":
+                v = struct.unpack("<14I", data[body:stop])
+                info.update(usec_per_frame=v[0], total_frames=v[4], streams=v[6], width=v[8], height=v[9])
+            elif tag == b"strh":
+                v = struct.unpack("<4s4sIHHIIIIIIIIhhhh", data[body:stop])
+                info.update(stream_type=v[0], handler=v[1], fps=Fraction(v[7], v[6]), stream_length=v[9])
+            elif tag == b"strf":
+                v = struct.unpack("<IiiHH4sIiiII", data[body:stop])
+                info.update(strf_width=v[1], strf_height=v[2], bit_count=v[4], compression=v[5])
+            elif tag == b"00dc":
+                frame_at.append(at)
+                info["frames"].append(data[body:stop])
+            elif tag == b"idx1":
+                if size % 16:
+                    raise ValueError(f"read_mjpeg: idx1 of {size} bytes")
+                for i in range(0, size, 16):
+                    ck, flags, off, sz = struct.unpack("<4sIII", data[body + i:body + i + 16])
+                    if ck != b"00dc":
+                        raise ValueError(f"read_mjpeg: idx1 entry {i // 16} names {ck!r}")
+                    info["index"].append((flags, off, sz))
+            at = stop + (size & 1)
+
+    walk(12, len(data))
+    if movi_at is None or len(info["index"]) != len(frame_at):
+        raise ValueError(f"read_mjpeg: {len(frame_at)} frame chunks and {len(info['index'])} idx1 entries")
+    for i, ((flags, off, sz), at) in enumerate(zip(info["index"], frame_at)):
+        if movi_at + off != at or sz != len(info["frames"][i]):
+            raise ValueError(f"read_mjpeg: idx1 entry {i} (offset {off}, size {sz}) does not point at its chunk at {at - movi_at} of {len(info['frames'][i])} bytes")
+    return info
+
+
+def read_mjpeg_frames(path) -> list:
+    """the JPEG files inside a Motion-JPEG AVI, in order (``read_mjpeg``'s frames)"""
+    return read_mjpeg(path)["frames"]

@@ -1221,3 +1221,66 @@ def png_emit(filtered: torch.Tensor, shape, tables: torch.Tensor, headers: torch
     check(lib.tt_png_emit(_p(filtered), n, h, w, ch, _p(tables), _p(headers), _p(out), int(out_bytes), out.numel(), _stream()), "tt_png_emit")
     _wrote(out, "png_emit")
     return out
+
+
+# ---- the JPEG export's device half (tt_jpeg_coeffs / tt_jpeg_scan; export.py drives them and holds the tables and the file layer)
+JPEG_SUBSAMPLING = {"4:4:4": _lib.TT_JPEG_444, "4:2:0": _lib.TT_JPEG_420}
+
+
+def _jpeg_shape(shape, subsampling, what: str):
+    h, w, ch = (int(v) for v in shape)
+    if h <= 0 or w <= 0 or ch not in (1, 3):
+        raise RuntimeError(f"{what}: shape (h, w, ch) with 1 (grey) or 3 (RGB) channels -- JPEG has no alpha --, got {tuple(shape)}")
+    sub = JPEG_SUBSAMPLING.get(subsampling, subsampling)
+    if isinstance(sub, bool) or sub not in (_lib.TT_JPEG_444, _lib.TT_JPEG_420):
+        raise RuntimeError(f"{what}: subsampling {subsampling!r} (one of {sorted(JPEG_SUBSAMPLING)}, or 0 / 2)")
+    return h, w, ch, sub
+
+
+def jpeg_coeffs(frames: torch.Tensor, quality: int = 75, subsampling="4:2:0", counts: bool = True):
+    """uint8 NHWC frames [N, H, W, C], C 1 or 3 -> (int16 device tensor [N, blocks, 64]: every 8 x 8 block's quantised DCT coefficients
+    in zig-zag order, blocks in scan order with the 4:2:0 dummy blocks; int32 device tensor [N, 4, 256] (uint32 bits) of the frames'
+    symbol counts -- DC luminance, AC luminance, DC chrominance, AC chrominance -- or None with ``counts=False``) (tt_jpeg_coeffs).
+    Asynchronous on the current stream."""
+    lib = _lib.load()
+    _p(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_contiguous() or frames.shape[0] < 1:
+        raise RuntimeError(f"jpeg_coeffs: contiguous uint8 [N, H, W, C] frames, got {tuple(frames.shape)} {frames.dtype}")
+    n = frames.shape[0]
+    h, w, ch, sub = _jpeg_shape(frames.shape[1:], subsampling, "jpeg_coeffs")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise RuntimeError(f"jpeg_coeffs: quality {quality!r} (an integer, 1 to 100)")
+    coeffs = torch.empty((n, lib.tt_jpeg_blocks(h, w, ch, sub), 64), dtype=torch.int16, device=frames.device)
+    cnt = torch.empty((n, 4, _lib.TT_JPEG_TABLE_WORDS), dtype=torch.int32, device=frames.device) if counts else None
+    check(lib.tt_jpeg_coeffs(_p(frames), n, h, w, ch, quality, sub, _p(coeffs), _p(cnt), _stream()), "tt_jpeg_coeffs")
+    _wrote(coeffs, "jpeg_coeffs")
+    if cnt is not None:
+        _wrote(cnt, "jpeg_coeffs")
+    return coeffs, cnt
+
+
+def jpeg_scan(coeffs: torch.Tensor, shape, subsampling, tables: torch.Tensor):
+    """``jpeg_coeffs``' coefficients for frames of ``shape`` (h, w, ch) and code tables [1 or N, 4, 256] (int32 device tensor: per symbol
+    code | length << 16, what export.jpeg_standard_tables / jpeg_optimized_tables make) -> (uint8 device tensor [N, stride]: every
+    frame's finished, byte-stuffed scan; int32 device tensor [N]: its length; bytes behind it are not written) (tt_jpeg_scan)."""
+    lib = _lib.load()
+    h, w, ch, sub = _jpeg_shape(shape, subsampling, "jpeg_scan")
+    _p(coeffs)
+    blocks = lib.tt_jpeg_blocks(h, w, ch, sub)
+    if coeffs.dtype != torch.int16 or coeffs.dim() != 3 or tuple(coeffs.shape[1:]) != (blocks, 64) or not coeffs.is_contiguous() or coeffs.shape[0] < 1:
+        raise RuntimeError(f"jpeg_scan: coeffs must be a contiguous int16 tensor [N, {blocks}, 64] (jpeg_coeffs'), got {tuple(coeffs.shape)} {coeffs.dtype}")
+    n = coeffs.shape[0]
+    _p(tables)
+    if tables.dtype != torch.int32 or tables.dim() != 3 or tuple(tables.shape[1:]) != (4, _lib.TT_JPEG_TABLE_WORDS) or tables.shape[0] not in (1, n) \
+            or not tables.is_contiguous() or tables.device != coeffs.device:
+        raise RuntimeError(f"jpeg_scan: tables must be a contiguous int32 tensor [1 or {n}, 4, {_lib.TT_JPEG_TABLE_WORDS}] on {coeffs.device}, got "
+                           f"{tuple(tables.shape)} {tables.dtype}")
+    stride = lib.tt_jpeg_scan_bound(h, w, ch, sub)
+    out = torch.empty((n, stride), dtype=torch.uint8, device=coeffs.device)
+    lengths = torch.empty((n,), dtype=torch.int32, device=coeffs.device)
+    ws = torch.empty((lib.tt_jpeg_scan_ws_bytes(n, h, w, ch, sub),), dtype=torch.uint8, device=coeffs.device)
+    check(lib.tt_jpeg_scan(_p(coeffs), n, h, w, ch, sub, _p(tables), tables.shape[0], _p(out), out.numel(), _p(lengths), _p(ws), ws.numel(), _stream()),
+          "tt_jpeg_scan")
+    _wrote(out, "jpeg_scan")
+    _wrote(lengths, "jpeg_scan")
+    return out, lengths
