@@ -1074,6 +1074,99 @@ int tt_jpeg_coeffs(const void* frames, int32_t n, int32_t h, int32_t w, int32_t 
 int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables,
                  int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * JPEG import: baseline JPEG files decoded on the device to uint8 [n, h, w, ch] NHWC frames, byte for byte what libjpeg ("islow"
+ * inverse DCT, fancy upsampling; Pillow's decoder) gives (this_and_that_vdm_amd/ingest.py drives it).  Only the compressed bytes cross
+ * to the device.  Two host routines (tt_jpeg_parse, tt_jpeg_decode_table; plain C++, they touch no device), two device entry points
+ * (tt_jpeg_entropy, tt_jpeg_pixels) and two size queries.  Integers from end to end: equality is the bound.  Additive: the ABI version
+ * is unchanged.  Accepted: SOF0, 8-bit samples, one interleaved scan, one component (any sampling factor, taken as 1 x 1) or three
+ * (YCbCr, sampling 1x1 / 1x1 / 1x1 or 2x2 / 1x1 / 1x1), 8-bit DQT, up to two DC and two AC Huffman tables, any component -> table map;
+ * APPn and COM segments are skipped.  Not here: progressive, arithmetic and 12-bit files, restart markers, several scans, 4:2:2, CMYK /
+ * Adobe files, EXIF orientation (not applied).  Coefficients whose inverse DCT leaves 0 .. 255 clamp to 0 / 255; libjpeg's range-limit
+ * table wraps there, so such crafted files are not held to it.
+ *
+ * 1. Parse -- tt_jpeg_parse (host): one file -> TtJpegHeader: the geometry, the subsampling, the byte range of the entropy-coded
+ *    segment (behind the SOS header, before EOI), per component its quantiser table in natural (row-major) order and its DC / AC table
+ *    index (0 or 1), and BITS / HUFFVAL of the tables DC 0, AC 0, DC 1, AC 1 (zeros for a table the file neither defines nor uses).
+ *    TT_EINVAL: null pointer; size <= 0; no SOI; a segment or the file ends early ("ends before"); no EOI behind the scan.
+ *    TT_EUNSUPPORTED, each by name: SOF1 / SOF2 and the other frame types ("progressive", "arithmetic", "extended sequential");
+ *    12-bit samples; a non-zero DRI ("restart"); a second SOS ("several scans"); sampling other than the above ("sampling"); 16-bit
+ *    DQT; four components or an Adobe APP14 segment; a table a component names but no DQT / DHT defines ("missing"); a Huffman table
+ *    index above 1; a scan that does not hold every component in order or has Ss / Se / Ah / Al other than 0 / 63 / 0 / 0.
+ * 2. Decode tables -- tt_jpeg_decode_table (host): BITS / HUFFVAL -> TT_JPEG_DECODE_WORDS = 256 uint32 the kernel reads: words 0 ..
+ *    127: 256 uint16 indexed by the next 8 bits, length << 8 | symbol for a code of at most 8 bits, else 0; words 128 + l, l = 1 .. 16:
+ *    the largest code of length l as int32, -1 for none (T.81 F.2.2.3 MAXCODE); words 145 + l: (index into HUFFVAL of the first code of
+ *    length l) - (that code) as int32; words 192 .. 255: HUFFVAL, 256 bytes.  The kernel masks every index it forms with 255: whatever
+ *    the words hold, nothing outside them is read.  TT_EINVAL: null pointer; a BITS that oversubscribes the code space; more than 256
+ *    codes.  A frame's table set is TT_JPEG_DECODE_SET_WORDS = 4 x 256 + 4 words: the tables DC 0, AC 0, DC 1, AC 1, then one word whose
+ *    bit 2 c is the DC and bit 2 c + 1 the AC table index of component c, then three zero words.
+ * 3. Unstuff (device): per frame the 0x00 behind every 0xFF is dropped -- per TT_JPEG_CHUNK of the stuffed bytes the count of such
+ *    pairs (a pair may straddle two chunks: the byte before a chunk is read with it), a scan of the counts, a gather.  An 0xFF followed
+ *    by anything else, or ending the scan, sets TT_JPEG_STATUS_MARKER.
+ * 4. Entropy decode (device), self-synchronising.  The plain stream of L bits is cut into subsequences of S = TT_JPEG_SUBSEQ_BITS bits,
+ *    one lane each; 256 lanes, one workgroup, take a sequence of tt_jpeg_sequence_bits = 256 S bits.  A lane's state is (p, m, z): bit
+ *    position, block within the MCU, zig-zag index.  f_i(entry) decodes the whole symbols (code and magnitude bits, T.81 F.2.2) that
+ *    start in [max(entry p, i S), (i + 1) S) and gives the exit state and the blocks completed.  Pass 0: x_i = f_i((i S, 0, 0)), lane 0
+ *    from the true state; pass k: x_i = f_i(x_{i-1}) where the entry changed.  After k passes the first k + 1 lanes are exact, so at
+ *    most 255 further passes run, fewer when a pass changes nothing (a workgroup-uniform exit).  ONE workgroup walks the sequences of a
+ *    frame in order, the true state carried from one to the next; frames run side by side.  No workgroup waits on another; every loop's
+ *    bound is computed before it starts (sequences: ceil(L / 256 S); passes: 256; symbols of a lane: S); no host readback.  Outcomes
+ *    under a speculative state: a bit pattern that is no code, with 16 or more bits left: one bit is skipped; a run that passes index
+ *    63: the block ends; a symbol that would read beyond L (or no code within the bits left): the lane stops, and every lane behind it
+ *    passes its entry state on.  A magnitude's size is the symbol's low 4 bits.  Lanes write nothing until the states are final; then
+ *    an exclusive scan of the block counts gives every lane its first block, and a last pass from the true entries writes the DC
+ *    differences and AC values into the zero-filled coeffs [n][tt_jpeg_blocks][64] int16, zig-zag, scan order, dummy blocks included --
+ *    tt_jpeg_coeffs' layout -- guarded by block < tt_jpeg_blocks.  On that true path an invalid code, a DC size above 11 or a run
+ *    beyond 63 sets TT_JPEG_STATUS_CODE.  A prefix sum per component over the DC differences (int32, stored as int16) makes them
+ *    absolute.  TT_JPEG_STATUS_BLOCKS: blocks found != tt_jpeg_blocks.  TT_JPEG_STATUS_TAIL: what is left of the stream is not fewer than
+ *    8 one-bits.  TT_JPEG_STATUS_SPAN: offset / length outside scans or above max_bytes (the frame is taken as empty).  A frame whose
+ *    status is not 0 is corrupt or truncated; its coefficients mean nothing.
+ *    tt_jpeg_entropy: scans (device bytes, scans_bytes of them), frame f's stuffed scan at offsets[f] with lengths[f] bytes (device
+ *    int64 / uint32), max_bytes >= every length (it sizes grids and ws), tables [ntables][TT_JPEG_DECODE_SET_WORDS] (ntables 1 or n) ->
+ *    coeffs and status [n] (device uint32).  ws: tt_jpeg_entropy_ws_bytes(n, max_bytes).  Two memsets and five launches.
+ *    TT_EINVAL: null pointer; n, h, w, max_bytes or scans_bytes <= 0; ch not 1 or 3; subsampling not 0 or 2; ntables not 1 or n;
+ *    tables, coeffs or ws off a 16-byte boundary; offsets off 8, lengths or status off 4; ws_bytes too small.  TT_EUNSUPPORTED: as
+ *    tt_jpeg_coeffs; max_bytes of 2^28 or more.
+ * 5. Reconstruct -- tt_jpeg_pixels (device), one launch: per block coef x Q, then jidctint: columns first, then rows, 32-bit integers.
+ *    Even part: z1 = (in2 + in6) 4433, tmp2 = z1 - in6 15137, tmp3 = z1 + in2 6270, tmp0 = (in0 + in4) << 13, tmp1 = (in0 - in4) << 13;
+ *    odd part: the multipliers 2446 16819 25172 12299 7373 20995 16069 3196 9633 of the export's rule 4 in jidctint's order; descale
+ *    (round half up, arithmetic shift) by 11 after the columns and 18 after the rows; + 128; clamp to 0 .. 255.  Grey: that, cropped.
+ *    4:2:0: the chroma planes of hc x wc = ceil(h / 2) x ceil(w / 2) REAL samples are upsampled: v[2r] = 3 s[r] + s[max(r - 1, 0)],
+ *    v[2r + 1] = 3 s[r] + s[min(r + 1, hc - 1)], out[2c] = (3 v[c] + v[max(c - 1, 0)] + 8) >> 4, out[2c + 1] = (3 v[c] + v[min(c + 1,
+ *    wc - 1)] + 7) >> 4 -- the clamps act at the real size, not at the padded plane --; with wc <= 2 every chroma sample is repeated
+ *    2 x 2 instead, as libjpeg does.  Colour: R = Y + ((91881 (Cr - 128) + 32768) >> 16), G = Y + ((-22554 (Cb - 128) - 46802 (Cr -
+ *    128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16), clamped.  Dummy blocks are dropped.
+ *    quant: device bytes [ntables][3][64], per component, natural order.  TT_EINVAL / TT_EUNSUPPORTED as tt_jpeg_coeffs, and ntables.
+ * 6. Output: frames uint8 [n, h, w, ch]; nothing is written outside it.
+ *    Every entry point refuses before the first HIP call; no allocation, no synchronisation. */
+#define TT_JPEG_DECODE_WORDS 256
+#define TT_JPEG_DECODE_SET_WORDS 1028
+#ifndef TT_JPEG_SUBSEQ_BITS
+#define TT_JPEG_SUBSEQ_BITS 1024                /* a build flag may try another S (a multiple of 32, 64 or more) */
+#endif
+#define TT_JPEG_STATUS_MARKER 1u
+#define TT_JPEG_STATUS_CODE 2u
+#define TT_JPEG_STATUS_BLOCKS 4u
+#define TT_JPEG_STATUS_TAIL 8u
+#define TT_JPEG_STATUS_SPAN 16u
+typedef struct {
+  int32_t h, w, ch, subsampling;
+  int64_t scan_offset, scan_bytes;
+  int32_t dc_table[3], ac_table[3];
+  uint8_t quant[3][64];
+  uint8_t bits[4][16];
+  uint8_t huffval[4][256];
+} TtJpegHeader;
+int tt_jpeg_parse(const uint8_t* data /* host */, int64_t size, TtJpegHeader* header /* host */);
+int tt_jpeg_decode_table(const uint8_t* bits /* host [16] */, const uint8_t* huffval /* host [256] */, uint32_t* table /* host [256] */);
+int64_t tt_jpeg_sequence_bits(void);
+int64_t tt_jpeg_entropy_ws_bytes(int32_t n, int64_t max_bytes);                          /* 0 for arguments tt_jpeg_entropy refuses */
+int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, int64_t max_bytes, int32_t n,
+                    int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs,
+                    uint32_t* status, void* ws, int64_t ws_bytes, tt_stream_t stream);
+int tt_jpeg_pixels(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint8_t* quant,
+                   int32_t ntables, void* frames, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

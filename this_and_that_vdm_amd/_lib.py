@@ -106,6 +106,18 @@ class TtColorBin(C.Structure):
 TT_GIF_BINS = 32768
 TT_PNG_STRIPE, TT_PNG_SYMS, TT_PNG_RECORD_WORDS, TT_PNG_TABLE_WORDS, TT_PNG_HEADER_WORDS = 32768, 286, 288, 288, 72
 TT_JPEG_444, TT_JPEG_420, TT_JPEG_TABLE_WORDS, TT_JPEG_COUNT_WORDS = 0, 2, 256, 1024
+TT_JPEG_CHUNK, TT_JPEG_DECODE_WORDS, TT_JPEG_DECODE_SET_WORDS = 4096, 256, 1028
+TT_JPEG_STATUS = {1: "a marker inside the scan", 2: "an invalid Huffman code", 4: "the wrong number of blocks", 8: "bits left over behind the last block",
+                  16: "a scan outside the buffer"}
+
+
+class TtJpegHeader(C.Structure):
+    """What tt_jpeg_parse reads from one baseline JPEG file: the field order of include/ttvdm.h."""
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("ch", C.c_int32), ("subsampling", C.c_int32),
+                ("scan_offset", C.c_int64), ("scan_bytes", C.c_int64),
+                ("dc_table", C.c_int32 * 3), ("ac_table", C.c_int32 * 3),
+                ("quant", (C.c_uint8 * 64) * 3), ("bits", (C.c_uint8 * 16) * 4), ("huffval", (C.c_uint8 * 256) * 4)]
+
 
 _i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -214,6 +226,13 @@ SIGNATURES = {
     "tt_jpeg_optimized_table": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp]),
     "tt_jpeg_coeffs": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "tt_jpeg_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    # the JPEG import: header and decode tables on the host, unstuffing, entropy decode and reconstruction on the device (additive as well)
+    "tt_jpeg_parse": (C.c_int, [_vp, _i64, C.POINTER(TtJpegHeader)]),
+    "tt_jpeg_decode_table": (C.c_int, [_vp, _vp, _vp]),
+    "tt_jpeg_sequence_bits": (_i64, []),
+    "tt_jpeg_entropy_ws_bytes": (_i64, [_i32, _i64]),
+    "tt_jpeg_entropy": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "tt_jpeg_pixels": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,569 @@
+// libttvdm: the device half of the JPEG import (include/ttvdm.h, "JPEG import"): tt_jpeg_entropy -- byte unstuffing, the
+// self-synchronising Huffman decode of every frame's scan into tt_jpeg_coeffs' coefficient layout, the DC prefix sums -- and
+// tt_jpeg_pixels -- dequantiser, the jidctint inverse DCT, fancy 4:2:0 chroma upsampling and the colour conversion in one launch.
+// Integer arithmetic only; the one atomic is an OR into a frame's status word: every call gives the same bytes.
+#include "common.h"
+#include "jpeg_host.h"
+
+namespace {
+
+constexpr int UBLOCK = 256;                         // lanes of an unstuffing chunk: 16 bytes a lane
+constexpr int CHUNK = TT_JPEG_CHUNK;
+static_assert(CHUNK == 16 * UBLOCK, "a lane holds one 16-byte unit of an unstuffing chunk");
+constexpr int SCAN_BLOCK = 1024, SCAN_WAVES = SCAN_BLOCK / 64;
+constexpr int ELANES = TT_JPEG_DECODE_LANES, EWAVES = ELANES / 64;
+constexpr int SUBSEQ = TT_JPEG_SUBSEQ_BITS;
+constexpr unsigned SEQ_BITS = (unsigned)SUBSEQ * ELANES, SEQ_WORDS = SEQ_BITS / 32;
+static_assert(SUBSEQ % 32 == 0 && SUBSEQ >= 64, "a subsequence is whole dwords and longer than any symbol (16 + 15 bits)");
+constexpr int PBLOCK = 256, TILE_W = 256;           // the reconstruction's tile: one MCU row down, TILE_W pixels across
+
+// ZZ[k]: the natural (row-major) index of the k-th coefficient of the zig-zag scan
+__device__ constexpr int ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ---------------------------------------------------------------- rule 3: unstuffing
+// frame f's stuffed scan: its first byte and its length, both held inside `scans`; a span that is not gives an empty frame
+__device__ __forceinline__ long long span_of(long long scans_bytes, const long long* __restrict__ offsets, const unsigned* __restrict__ lengths,
+                                             long long max_bytes, int f, unsigned& len, bool& bad) {
+  const long long off = offsets[f], l = (long long)lengths[f];
+  bad = off < 0 || l > max_bytes || off > scans_bytes || l > scans_bytes - off;
+  len = bad ? 0u : (unsigned)l;
+  return bad ? 0 : off;
+}
+__device__ __forceinline__ const unsigned char* frame_span(const unsigned char* __restrict__ scans, long long scans_bytes, const long long* __restrict__ offsets,
+                                                           const unsigned* __restrict__ lengths, long long max_bytes, int f, unsigned& len, bool& bad) {
+  return scans + span_of(scans_bytes, offsets, lengths, max_bytes, f, len, bad);
+}
+
+// the chunk's bytes (and the one before them) into LDS, then per lane: the 0x00 bytes behind an 0xFF among its 16, as a bit mask
+__device__ __forceinline__ unsigned chunk_drops(const unsigned char* __restrict__ src, unsigned len, unsigned char* raw_s, bool& marker) {
+  const unsigned c0 = blockIdx.x * (unsigned)CHUNK;
+  for (int i = threadIdx.x; i < CHUNK + 1; i += UBLOCK) {
+    const long long g = (long long)c0 + i - 1;
+    raw_s[i] = (g >= 0 && g < (long long)len) ? src[g] : (unsigned char)0;
+  }
+  __syncthreads();
+  unsigned mask = 0u;
+  marker = false;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const unsigned at = c0 + 16 * threadIdx.x + j;
+    if (at < len) {
+      const unsigned b = raw_s[1 + 16 * threadIdx.x + j], before = raw_s[16 * threadIdx.x + j];
+      if (before == 0xffu && b == 0u) mask |= 1u << j;
+      marker = marker || (before == 0xffu && b != 0u) || (at == len - 1 && b == 0xffu);
+    }
+  }
+  return mask;
+}
+
+// grid (chunks, n)
+__global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_count_kernel(const unsigned char* __restrict__ scans, long long scans_bytes, const long long* __restrict__ offsets,
+                                                                   const unsigned* __restrict__ lengths, long long max_bytes, unsigned* __restrict__ chunk_drop,
+                                                                   int chunks, unsigned* __restrict__ status) {
+  __shared__ unsigned char raw_s[CHUNK + 16];
+  __shared__ unsigned red_s[UBLOCK / 64];
+  unsigned len;
+  bool bad, marker;
+  const unsigned char* src = frame_span(scans, scans_bytes, offsets, lengths, max_bytes, blockIdx.y, len, bad);
+  unsigned drops = __popc(chunk_drops(src, len, raw_s, marker));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) drops += __shfl_down(drops, o, 64);
+  if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = drops;
+  const unsigned flags = (marker ? TT_JPEG_STATUS_MARKER : 0u) | ((bad && blockIdx.x == 0 && threadIdx.x == 0) ? TT_JPEG_STATUS_SPAN : 0u);
+  if (flags) atomicOr(&status[blockIdx.y], flags);
+  __syncthreads();
+  if (threadIdx.x == 0) chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x] = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+}
+
+// an exclusive scan of v[0 .. count) in place, one workgroup; returns the sum.  red_s: SCAN_WAVES words
+__device__ __forceinline__ unsigned scan_in_place(unsigned* __restrict__ v, long long count, unsigned* red_s) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned carry = 0u;
+  for (long long at = 0; at < count; at += SCAN_BLOCK) {
+    const long long i = at + tid;
+    const unsigned mine = i < count ? v[i] : 0u;
+    unsigned incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned a = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += a;
+    }
+    if (lane == 63) red_s[wave] = incl;
+    __syncthreads();
+    unsigned before = carry + incl - mine, all = 0u;
+    for (int wv = 0; wv < SCAN_WAVES; ++wv) {
+      if (wv < wave) before += red_s[wv];
+      all += red_s[wv];
+    }
+    if (i < count) v[i] = before;
+    carry += all;
+    __syncthreads();
+  }
+  return carry;
+}
+
+// grid (n): the dropped bytes before every chunk, and the frame's plain (unstuffed) length
+__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_unstuff_scan_kernel(unsigned* __restrict__ chunk_drop, int chunks, const long long* __restrict__ offsets,
+                                                                      const unsigned* __restrict__ lengths, long long scans_bytes, long long max_bytes,
+                                                                      unsigned* __restrict__ plain_bytes) {
+  __shared__ unsigned red_s[SCAN_WAVES];
+  const unsigned total = scan_in_place(chunk_drop + (long long)blockIdx.x * chunks, chunks, red_s);
+  if (threadIdx.x == 0) {
+    unsigned len;
+    bool bad;
+    span_of(scans_bytes, offsets, lengths, max_bytes, blockIdx.x, len, bad);
+    plain_bytes[blockIdx.x] = len - min(total, len);
+  }
+}
+
+// grid (chunks, n): every byte that stays moves down by the drops before it
+__global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_gather_kernel(const unsigned char* __restrict__ scans, long long scans_bytes, const long long* __restrict__ offsets,
+                                                                    const unsigned* __restrict__ lengths, long long max_bytes, const unsigned* __restrict__ chunk_drop,
+                                                                    int chunks, unsigned char* __restrict__ plain, long long plain_stride) {
+  __shared__ unsigned char raw_s[CHUNK + 16];
+  __shared__ unsigned red_s[UBLOCK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned len;
+  bool bad, marker;
+  const unsigned char* src = frame_span(scans, scans_bytes, offsets, lengths, max_bytes, blockIdx.y, len, bad);
+  const unsigned mask = chunk_drops(src, len, raw_s, marker);
+  const unsigned mine = __popc(mask);
+  unsigned incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned a = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += a;
+  }
+  if (lane == 63) red_s[wave] = incl;
+  __syncthreads();
+  unsigned before = incl - mine + chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x];
+  for (int wv = 0; wv < wave; ++wv) before += red_s[wv];
+  const unsigned at0 = blockIdx.x * (unsigned)CHUNK + 16 * threadIdx.x;
+  unsigned char* __restrict__ dst = plain + (long long)blockIdx.y * plain_stride;
+  long long pos = (long long)at0 - before;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    if (at0 + j < len && !((mask >> j) & 1u)) {
+      if (pos >= 0 && pos < plain_stride) dst[pos] = raw_s[1 + 16 * threadIdx.x + j];
+      ++pos;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- rule 4: the entropy decoder
+struct DecState { unsigned p, mz; };                 // bit position; block within the MCU << 6 | zig-zag index
+__device__ __forceinline__ bool same(const DecState& a, const DecState& b) { return a.p == b.p && a.mz == b.mz; }
+
+// a frame's constants, uniform over the workgroup
+struct DecFrame {
+  unsigned L;                                        // bits of the plain stream
+  unsigned map;                                      // bit 2 c: component c's DC table, bit 2 c + 1: its AC table
+  int bpm;
+  unsigned blocks;                                   // tt_jpeg_blocks
+};
+
+// f_i: the whole symbols that start in [max(st.p, start), end) of the window `win_s` (big-endian dwords, bit 0 of word 0 is bit `win0` of
+// the stream); st becomes the exit state; returns the blocks completed.  WRITE: the values go to `out` (the frame's coefficients), the
+// first block touched is `block`, and what a valid stream never holds is ORed into `err`.  At most SUBSEQ iterations: every one takes a
+// bit or more, and end - start <= SUBSEQ.
+template <bool WRITE>
+__device__ __forceinline__ unsigned decode_span(const unsigned* win_s, unsigned win0, const unsigned* tab_s, const DecFrame& fr, unsigned start, unsigned end,
+                                                DecState& st, short* __restrict__ out, unsigned block, unsigned& err) {
+  unsigned p = st.p, m = st.mz >> 6, z = st.mz & 63u, done = 0u;
+  if (p < start) return 0u;                          // a lane before this one stopped at the end of the stream: pass the state on
+  for (int it = 0; it < SUBSEQ && p < end; ++it) {
+    const unsigned rel = p - win0, wi = rel >> 5;
+    const unsigned long long two = ((unsigned long long)win_s[wi] << 32) | win_s[wi + 1];
+    const unsigned v = (unsigned)((two << (rel & 31u)) >> 32);          // the 32 bits at p
+    const unsigned avail = fr.L - p;
+    const unsigned comp = fr.bpm == 6 ? (m < 4u ? 0u : m - 3u) : m;
+    const unsigned id = (fr.map >> (2u * comp + (z ? 1u : 0u))) & 1u;
+    const unsigned* t = tab_s + (id * 2u + (z ? 1u : 0u)) * TT_JPEG_DECODE_WORDS;
+    const unsigned pair = t[v >> 25];
+    const unsigned e = ((v >> 24) & 1u) ? pair >> 16 : pair & 0xffffu;
+    unsigned len = e >> 8, sym = e & 0xffu;
+    if (len == 0u) {
+#pragma unroll
+      for (unsigned l = 9; l <= 16; ++l) {
+        const unsigned code = v >> (32 - l);
+        if (len == 0u && (int)code <= (int)t[128 + l]) {
+          len = l;
+          const unsigned at = (code + t[145 + l]) & 255u;
+          sym = (t[192 + (at >> 2)] >> (8u * (at & 3u))) & 0xffu;
+        }
+      }
+    }
+    if (len == 0u) {
+      if (avail < 16u) break;                        // no code within the bits left: the lane stops
+      if (WRITE) err |= TT_JPEG_STATUS_CODE;
+      p += 1u;                                       // no code at all: skip one bit
+      continue;
+    }
+    const unsigned n = sym & 15u;
+    if (len + n > avail) break;                      // the symbol would read beyond L: the lane stops
+    const unsigned raw = n ? (v << len) >> (32u - n) : 0u;
+    const int value = n ? ((raw >> (n - 1u)) ? (int)raw : (int)raw - (int)((1u << n) - 1u)) : 0;
+    p += len + n;
+    bool ends = false;
+    if (z == 0u) {
+      if (WRITE) {
+        if (sym > 11u) err |= TT_JPEG_STATUS_CODE;
+        if (block + done < fr.blocks) out[(long long)(block + done) * 64] = (short)value;
+      }
+      z = 1u;
+    } else if (n == 0u) {
+      if ((sym >> 4) == 15u) { z += 16u; ends = z > 63u; }
+      else ends = true;                              // EOB
+    } else {
+      z += sym >> 4;
+      if (z > 63u) {
+        ends = true;                                 // a run that passes index 63: the block ends
+        if (WRITE) err |= TT_JPEG_STATUS_CODE;
+      } else {
+        if (WRITE && block + done < fr.blocks) out[(long long)(block + done) * 64 + z] = (short)value;
+        ++z;
+        ends = z > 63u;
+      }
+    }
+    if (ends) {
+      z = 0u;
+      m = (int)m + 1 == fr.bpm ? 0u : m + 1u;
+      ++done;
+    }
+  }
+  st.p = p;
+  st.mz = m << 6 | z;
+  return done;
+}
+
+// grid (n), ELANES lanes: ONE workgroup walks its frame's sequences in order.  Nothing another workgroup writes is read.
+__global__ __launch_bounds__(ELANES) void jpeg_entropy_kernel(const unsigned char* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
+                                                            long long max_bytes, const unsigned* __restrict__ tables, int ntables, int bpm, unsigned blocks,
+                                                            short* __restrict__ coeffs, unsigned* __restrict__ status) {
+  __shared__ unsigned win_s[SEQ_WORDS + 2];
+  __shared__ unsigned tab_s[TT_JPEG_DECODE_SET_WORDS];
+  __shared__ unsigned ex_p[ELANES], ex_mz[ELANES];
+  __shared__ unsigned red_s[EWAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned* __restrict__ tset = tables + (ntables > 1 ? (long long)blockIdx.x * TT_JPEG_DECODE_SET_WORDS : 0);
+  for (int i = tid; i < TT_JPEG_DECODE_SET_WORDS; i += ELANES) tab_s[i] = tset[i];
+  const unsigned nbytes = (unsigned)min((long long)plain_bytes[blockIdx.x], max_bytes);
+  const unsigned char* __restrict__ stream = plain + (long long)blockIdx.x * plain_stride;
+  const unsigned* __restrict__ words = (const unsigned*)stream;
+  const long long stride_words = plain_stride / 4;
+  short* __restrict__ out = coeffs + (long long)blockIdx.x * blocks * 64;
+  __syncthreads();
+  DecFrame fr;
+  fr.L = nbytes * 8u;                                // max_bytes < 2^28: below 2^31
+  fr.map = tab_s[4 * TT_JPEG_DECODE_WORDS];
+  fr.bpm = bpm;
+  fr.blocks = blocks;
+  DecState carried = {0u, 0u};                       // the true state at the head of the sequence
+  unsigned base = 0u, err = 0u;                      // blocks completed before the sequence
+  const unsigned nseq = (fr.L + SEQ_BITS - 1u) / SEQ_BITS;
+  for (unsigned q = 0; q < nseq; ++q) {
+    const unsigned win0 = q * SEQ_BITS;
+    __syncthreads();                                 // the window and the states of the sequence before are done with
+    // The last words of the window may hold workspace bytes behind the stream's L bits that nothing wrote.  No result depends on them:
+    // a code of at most `avail` bits is decided by bits before L alone (the table is a prefix code, the shortest match is taken), and it
+    // and its magnitude bits are used only when len + n <= avail; every other outcome with avail < 16 is the same `break`, and "no code:
+    // skip a bit" needs avail >= 16, i.e. 16 real bits.  (The CPU emulation reads zeros there and gives the same states.)
+    for (unsigned i = tid; i < SEQ_WORDS + 2u; i += ELANES) {
+      const long long gw = (long long)q * SEQ_WORDS + i;
+      win_s[i] = gw < stride_words ? __builtin_bswap32(words[gw]) : 0u;
+    }
+    __syncthreads();
+    const unsigned start = win0 + (unsigned)tid * SUBSEQ, end = min(start + (unsigned)SUBSEQ, fr.L);
+    const bool active = start < fr.L;                // a lane behind the end of the stream decodes nothing and never asks for a pass
+    const int last = (int)min((unsigned)ELANES - 1u, (fr.L - win0 - 1u) / (unsigned)SUBSEQ);       // the last lane with bits of the stream
+    unsigned none = 0u;
+    DecState used = carried, x;
+    if (tid) { used.p = start; used.mz = 0u; }
+    x = used;
+    unsigned done = decode_span<false>(win_s, win0, tab_s, fr, start, end, x, out, 0u, none);
+    ex_p[tid] = x.p;
+    ex_mz[tid] = x.mz;
+    for (int pass = 1; pass < ELANES; ++pass) {       // after k passes the first k + 1 lanes are exact
+      __syncthreads();
+      DecState entry = carried;
+      if (tid) { entry.p = ex_p[tid - 1]; entry.mz = ex_mz[tid - 1]; }
+      const bool changed = active && !same(entry, used);
+      if (!__syncthreads_or(changed)) break;         // uniform: nobody's entry moved, the states are final
+      if (changed) {
+        used = entry;
+        x = used;
+        done = decode_span<false>(win_s, win0, tab_s, fr, start, end, x, out, 0u, none);
+        ex_p[tid] = x.p;
+        ex_mz[tid] = x.mz;
+      }
+    }
+    // every lane's first block: an exclusive scan of the blocks completed
+    unsigned incl = done;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned a = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += a;
+    }
+    if (lane == 63) red_s[wave] = incl;
+    __syncthreads();                                 // also: every ex_p / ex_mz of the last pass is stored
+    unsigned first = base + incl - done, all = 0u;
+    for (int wv = 0; wv < EWAVES; ++wv) {
+      if (wv < wave) first += red_s[wv];
+      all += red_s[wv];
+    }
+    x = used;
+    decode_span<true>(win_s, win0, tab_s, fr, start, end, x, out, first, err);
+    carried.p = ex_p[last];
+    carried.mz = ex_mz[last];
+    base += all;
+  }
+  if (tid == 0) {
+    if (base != blocks) err |= TT_JPEG_STATUS_BLOCKS;
+    const unsigned left = fr.L - min(carried.p, fr.L);
+    const unsigned ones = left ? (1u << min(left, 8u)) - 1u : 0u;
+    if (left >= 8u || (left && ((unsigned)stream[nbytes - 1] & ones) != ones)) err |= TT_JPEG_STATUS_TAIL;
+  }
+  if (err) atomicOr(&status[blockIdx.x], err);
+}
+
+// grid (n), SCAN_BLOCK lanes: one lane per MCU, a prefix sum per component over the DC differences (int32), stored as int16
+__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_dc_kernel(short* __restrict__ coeffs, long long blocks, int bpm) {
+  __shared__ int red_s[SCAN_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  short* __restrict__ fc = coeffs + (long long)blockIdx.x * blocks * 64;
+  const long long mcus = blocks / bpm;
+  const int ncomp = bpm == 1 ? 1 : 3, ny = bpm == 6 ? 4 : 1;
+  int carry[3] = {0, 0, 0};
+  for (long long at = 0; at < mcus; at += SCAN_BLOCK) {
+    const long long u = at + tid;
+    for (int c = 0; c < ncomp; ++c) {
+      const int k0 = c == 0 ? 0 : ny + c - 1, nk = c == 0 ? ny : 1;
+      int d[4] = {0, 0, 0, 0}, mine = 0;
+      if (u < mcus)
+        for (int k = 0; k < nk; ++k) { d[k] = fc[(u * bpm + k0 + k) * 64]; mine += d[k]; }
+      int incl = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int a = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += a;
+      }
+      if (lane == 63) red_s[wave] = incl;
+      __syncthreads();
+      int before = carry[c] + incl - mine, all = 0;
+      for (int wv = 0; wv < SCAN_WAVES; ++wv) {
+        if (wv < wave) before += red_s[wv];
+        all += red_s[wv];
+      }
+      if (u < mcus)
+        for (int k = 0; k < nk; ++k) { before += d[k]; fc[(u * bpm + k0 + k) * 64] = (short)before; }
+      carry[c] += all;
+      __syncthreads();
+    }
+  }
+}
+
+// ---------------------------------------------------------------- rule 5: reconstruction
+// jidctint's arithmetic in 32-bit two's complement: sums and products are formed in unsigned, so crafted coefficients wrap instead of
+// overflowing a signed int; the descale is an arithmetic shift of the wrapped value
+template <int N> __device__ __forceinline__ int descale(unsigned x) { return (int)(x + (1u << (N - 1))) >> N; }
+// jidctint's pass over eight values; N: the descale
+template <int N> __device__ __forceinline__ void idct8(int& d0, int& d1, int& d2, int& d3, int& d4, int& d5, int& d6, int& d7) {
+  const unsigned i0 = (unsigned)d0, i1 = (unsigned)d1, i2 = (unsigned)d2, i3 = (unsigned)d3, i4 = (unsigned)d4, i5 = (unsigned)d5, i6 = (unsigned)d6,
+                 i7 = (unsigned)d7;
+  const unsigned z1 = (i2 + i6) * 4433u;
+  const unsigned e2 = z1 - i6 * 15137u, e3 = z1 + i2 * 6270u;
+  const unsigned e0 = (i0 + i4) << 13, e1 = (i0 - i4) << 13;
+  const unsigned t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
+  const unsigned y1 = i7 + i1, y2 = i5 + i3, y3 = i7 + i3, y4 = i5 + i1, z5 = (y3 + y4) * 9633u;
+  const unsigned a0 = i7 * 2446u, a1 = i5 * 16819u, a2 = i3 * 25172u, a3 = i1 * 12299u;
+  const unsigned b1 = 0u - y1 * 7373u, b2 = 0u - y2 * 20995u, b3 = z5 - y3 * 16069u, b4 = z5 - y4 * 3196u;
+  const unsigned o0 = a0 + b1 + b3, o1 = a1 + b2 + b4, o2 = a2 + b2 + b3, o3 = a3 + b1 + b4;
+  d0 = descale<N>(t10 + o3); d7 = descale<N>(t10 - o3);
+  d1 = descale<N>(t11 + o2); d6 = descale<N>(t11 - o2);
+  d2 = descale<N>(t12 + o1); d5 = descale<N>(t12 - o1);
+  d3 = descale<N>(t13 + o0); d4 = descale<N>(t13 - o0);
+}
+__device__ __forceinline__ unsigned clamp8(int v) { return (unsigned)min(max(v, 0), 255); }
+
+// the block at `c` (zig-zag int16) dequantised by q (natural order), inverted, as 8 rows of 8 samples at dst (8-byte aligned rows)
+__device__ __forceinline__ void block_samples(const short* __restrict__ c, const unsigned char* q, unsigned char* dst, int pitch) {
+  int d[64];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const uint4 v = *(const uint4*)(c + 8 * u);
+    const unsigned wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = 8 * u + j;
+      d[ZZ[k]] = (int)(short)((wd[j >> 1] >> (16 * (j & 1))) & 0xffffu) * (int)q[ZZ[k]];
+    }
+  }
+#pragma unroll
+  for (int col = 0; col < 8; ++col) idct8<11>(d[col], d[8 + col], d[16 + col], d[24 + col], d[32 + col], d[40 + col], d[48 + col], d[56 + col]);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    idct8<18>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
+    unsigned lo = 0u, hi = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      lo |= clamp8(d[r * 8 + j] + 128) << (8 * j);
+      hi |= clamp8(d[r * 8 + 4 + j] + 128) << (8 * j);
+    }
+    *(uint2*)(dst + r * pitch) = make_uint2(lo, hi);
+  }
+}
+
+__device__ __forceinline__ void store_rgb(unsigned char* __restrict__ p, int y, int cb, int cr) {
+  cb -= 128;
+  cr -= 128;
+  p[0] = (unsigned char)clamp8(y + ((91881 * cr + 32768) >> 16));
+  p[1] = (unsigned char)clamp8(y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+  p[2] = (unsigned char)clamp8(y + ((116130 * cb + 32768) >> 16));
+}
+
+// grid (tiles per MCU row x MCU rows, n): a tile is one MCU row down and TILE_W pixels across.  One lane per block inverts it into LDS;
+// then every lane converts the tile's pixels.  SUB (4:2:0): the chroma blocks of the MCU rows above and below and of one MCU to either
+// side are inverted as well -- the upsampler's neighbours -- into a plane of 3 x CBW blocks per component.
+constexpr int CBW = TILE_W / 16 + 2, CPITCH = 8 * CBW;
+template <bool SUB> __global__ __launch_bounds__(PBLOCK) void jpeg_pixels_kernel(const short* __restrict__ coeffs, long long blocks, int h, int w, int ch,
+                                                                               TtJpegGeometry geo, int tiles_x, const unsigned char* __restrict__ quant,
+                                                                               int ntables, unsigned char* __restrict__ frames) {
+  constexpr int MCU = SUB ? 16 : 8, MCUS = TILE_W / MCU;
+  __shared__ __attribute__((aligned(16))) unsigned char y_s[MCU][TILE_W];
+  __shared__ __attribute__((aligned(16))) unsigned char c_s[SUB ? 2 * 24 * CPITCH : 2 * 8 * TILE_W];
+  __shared__ unsigned char q_s[3 * 64];
+  const int tid = threadIdx.x;
+  const int tile = blockIdx.x % tiles_x, mcu_y = blockIdx.x / tiles_x;
+  const int x0 = tile * TILE_W, y0 = mcu_y * MCU;
+  if (tid < 192) q_s[tid] = quant[(ntables > 1 ? (long long)blockIdx.y * 192 : 0) + tid];
+  __syncthreads();
+  const short* __restrict__ fc = coeffs + (long long)blockIdx.y * blocks * 64;
+  const int bpm = geo.blocks_per_mcu;
+  if (SUB) {
+    if (tid < 4 * MCUS) {                            // the tile's Y blocks
+      const int m = tid >> 2, k = tid & 3, mcu_x = tile * MCUS + m;
+      if (mcu_x < geo.mcus_x && 2 * mcu_y + (k >> 1) < (h + 7) / 8 && 2 * mcu_x + (k & 1) < (w + 7) / 8)       // dummy blocks are dropped
+        block_samples(fc + (((long long)mcu_y * geo.mcus_x + mcu_x) * 6 + k) * 64, q_s, &y_s[(k >> 1) * 8][m * 16 + (k & 1) * 8], TILE_W);
+    } else if (tid < 4 * MCUS + 2 * 3 * CBW) {       // chroma: 3 block rows of CBW blocks per component
+      const int i = tid - 4 * MCUS, comp = i / (3 * CBW), brow = (i % (3 * CBW)) / CBW, bcol = i % CBW;
+      const int my = mcu_y - 1 + brow, mx = tile * MCUS - 1 + bcol;
+      if (my >= 0 && my < geo.mcus_y && mx >= 0 && mx < geo.mcus_x)
+        block_samples(fc + (((long long)my * geo.mcus_x + mx) * 6 + 4 + comp) * 64, q_s + 64 * (1 + comp), c_s + (comp * 24 + brow * 8) * CPITCH + bcol * 8, CPITCH);
+    }
+  } else {
+    const int m = tid / bpm, k = tid % bpm, mcu_x = tile * MCUS + m;
+    if (m < MCUS && mcu_x < geo.mcus_x)
+      block_samples(fc + (((long long)mcu_y * geo.mcus_x + mcu_x) * bpm + k) * 64, q_s + 64 * k, k == 0 ? &y_s[0][m * 8] : c_s + (k - 1) * 8 * TILE_W + m * 8,
+                    TILE_W);
+  }
+  __syncthreads();
+  unsigned char* __restrict__ dst = frames + (long long)blockIdx.y * h * w * ch;
+  const int hc = (h + 1) >> 1, wc = (w + 1) >> 1;
+  const bool fancy = wc > 2;
+  for (int i = tid; i < MCU * TILE_W; i += PBLOCK) {
+    const int yy = i / TILE_W, xx = i % TILE_W, gy = y0 + yy, gx = x0 + xx;
+    if (gy >= h || gx >= w) continue;
+    unsigned char* __restrict__ p = dst + ((long long)gy * w + gx) * ch;
+    const int y = y_s[yy][xx];
+    if (ch == 1) { p[0] = (unsigned char)y; continue; }
+    if (!SUB) { store_rgb(p, y, c_s[yy * TILE_W + xx], c_s[(8 + yy) * TILE_W + xx]); continue; }
+    // the chroma sample (r, c) of the plane sits at row r - (8 mcu_y - 8), column c - (x0 / 2 - 8) of the component's LDS plane
+    const int r = gy >> 1, c = gx >> 1, rb = 8 * mcu_y - 8, cbase = (x0 >> 1) - 8;
+    int cc[2];
+#pragma unroll
+    for (int comp = 0; comp < 2; ++comp) {
+      const unsigned char* s = c_s + comp * 24 * CPITCH;
+      if (!fancy) { cc[comp] = s[(r - rb) * CPITCH + c - cbase]; continue; }
+      const int r2 = (gy & 1) ? min(r + 1, hc - 1) : max(r - 1, 0), c2 = (gx & 1) ? min(c + 1, wc - 1) : max(c - 1, 0);
+      const int va = 3 * s[(r - rb) * CPITCH + c - cbase] + s[(r2 - rb) * CPITCH + c - cbase];
+      const int vb = 3 * s[(r - rb) * CPITCH + c2 - cbase] + s[(r2 - rb) * CPITCH + c2 - cbase];
+      cc[comp] = (3 * va + vb + ((gx & 1) ? 7 : 8)) >> 4;
+    }
+    store_rgb(p, y, cc[0], cc[1]);
+  }
+}
+
+int refuse_shape(const char* who, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling) {
+  if (n <= 0 || h <= 0 || w <= 0) TT_FAIL(TT_EINVAL, "%s: empty problem (n = %d, h = %d, w = %d)", who, n, h, w);
+  if (ch != 1 && ch != 3) TT_FAIL(TT_EINVAL, "%s: %d channels (1: grey, or 3: RGB)", who, ch);
+  if (subsampling != TT_JPEG_444 && subsampling != TT_JPEG_420)
+    TT_FAIL(TT_EINVAL, "%s: subsampling = %d (0: 4:4:4, or 2: 4:2:0)", who, subsampling);
+  if ((long long)h * w * ch >= (1ll << 31)) TT_FAIL(TT_EUNSUPPORTED, "%s: a frame of %lld bytes (below 2^31)", who, (long long)h * w * ch);
+  if (tt_jpeg_scan_bound(h, w, ch, subsampling) >= (1ll << 31))
+    TT_FAIL(TT_EUNSUPPORTED, "%s: a scan bound of %lld bytes per frame (below 2^31)", who, (long long)tt_jpeg_scan_bound(h, w, ch, subsampling));
+  if (n > 65535) TT_FAIL(TT_EUNSUPPORTED, "%s: %d frames: more than one grid covers (65535)", who, n);
+  return TT_OK;
+}
+
+}  // namespace
+
+extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, int64_t max_bytes, int32_t n,
+                               int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs,
+                               uint32_t* status, void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  if (!scans || !offsets || !lengths || !tables || !coeffs || !status || !ws)
+    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: null %s",
+            !scans ? "scans" : (!offsets ? "offsets" : (!lengths ? "lengths" : (!tables ? "tables" : (!coeffs ? "coeffs" : (!status ? "status" : "ws"))))));
+  const int rc = refuse_shape("tt_jpeg_entropy", n, h, w, ch, subsampling);
+  if (rc != TT_OK) return rc;
+  if (scans_bytes <= 0 || max_bytes <= 0) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: empty scans (scans_bytes = %lld, max_bytes = %lld)", (long long)scans_bytes, (long long)max_bytes);
+  if (max_bytes >= (1ll << 28)) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_entropy: max_bytes = %lld (a scan below 2^28 bytes)", (long long)max_bytes);
+  if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ntables = %d (1, or one set per frame: %d)", ntables, n);
+  if ((uintptr_t)offsets & 7) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: offsets is not 8-byte aligned");
+  if ((uintptr_t)lengths & 3) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: lengths is not 4-byte aligned");
+  if ((uintptr_t)tables & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: tables is not 16-byte aligned");
+  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: coeffs is not 16-byte aligned");
+  if ((uintptr_t)status & 3) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: status is not 4-byte aligned");
+  if ((uintptr_t)ws & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ws is not 16-byte aligned");
+  if (ws_bytes < tt_jpeg_entropy_ws_bytes(n, max_bytes))
+    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ws too small: %lld bytes, tt_jpeg_entropy_ws_bytes = %lld", (long long)ws_bytes, (long long)tt_jpeg_entropy_ws_bytes(n, max_bytes));
+  const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
+  const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
+  const auto up = [](long long v) { return (v + 15) / 16 * 16; };
+  const int chunks = (int)((max_bytes + CHUNK - 1) / CHUNK);
+  const long long plain_stride = tt_jpeg_plain_stride(max_bytes);   // the layout tt_jpeg_entropy_ws_bytes sizes
+  char* p = (char*)ws;
+  unsigned* plain_bytes = (unsigned*)p;
+  p += up(4 * (long long)n);
+  unsigned* chunk_drop = (unsigned*)p;
+  p += up(4ll * n * chunks);
+  unsigned char* plain = (unsigned char*)p;
+  const hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(status, 0, sizeof(uint32_t) * (size_t)n, s);
+  if (e == hipSuccess) e = hipMemsetAsync(coeffs, 0, (size_t)n * (size_t)blocks * 128, s);
+  if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "tt_jpeg_entropy: zeroing coeffs and status: %s", hipGetErrorString(e));
+  const dim3 per_chunk((unsigned)chunks, (unsigned)n);
+  hipLaunchKernelGGL(jpeg_unstuff_count_kernel, per_chunk, dim3(UBLOCK), 0, s, (const unsigned char*)scans, (long long)scans_bytes, (const long long*)offsets,
+                     (const unsigned*)lengths, (long long)max_bytes, chunk_drop, chunks, (unsigned*)status);
+  hipLaunchKernelGGL(jpeg_unstuff_scan_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, chunk_drop, chunks, (const long long*)offsets, (const unsigned*)lengths,
+                     (long long)scans_bytes, (long long)max_bytes, plain_bytes);
+  hipLaunchKernelGGL(jpeg_unstuff_gather_kernel, per_chunk, dim3(UBLOCK), 0, s, (const unsigned char*)scans, (long long)scans_bytes, (const long long*)offsets,
+                     (const unsigned*)lengths, (long long)max_bytes, (const unsigned*)chunk_drop, chunks, plain, plain_stride);
+  hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(ELANES), 0, s, (const unsigned char*)plain, plain_stride, (const unsigned*)plain_bytes,
+                     (long long)max_bytes, (const unsigned*)tables, (int)ntables, (int)geo.blocks_per_mcu, (unsigned)blocks, (short*)coeffs, (unsigned*)status);
+  hipLaunchKernelGGL(jpeg_dc_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, (short*)coeffs, blocks, (int)geo.blocks_per_mcu);
+  TT_CHECK_LAUNCH("tt_jpeg_entropy");
+  return TT_OK;
+}
+
+extern "C" int tt_jpeg_pixels(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint8_t* quant, int32_t ntables,
+                              void* frames, tt_stream_t stream) {
+  if (!coeffs || !quant || !frames) TT_FAIL(TT_EINVAL, "tt_jpeg_pixels: null %s", !coeffs ? "coeffs" : (!quant ? "quant" : "frames"));
+  const int rc = refuse_shape("tt_jpeg_pixels", n, h, w, ch, subsampling);
+  if (rc != TT_OK) return rc;
+  if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "tt_jpeg_pixels: ntables = %d (1, or one set per frame: %d)", ntables, n);
+  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_pixels: coeffs is not 16-byte aligned");
+  const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
+  const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
+  const bool sub = geo.blocks_per_mcu == 6;
+  const int tiles_x = (geo.mcus_x * (sub ? 16 : 8) + TILE_W - 1) / TILE_W;
+  const dim3 grid((unsigned)(tiles_x * geo.mcus_y), (unsigned)n);
+  if (sub)
+    hipLaunchKernelGGL(jpeg_pixels_kernel<true>, grid, dim3(PBLOCK), 0, (hipStream_t)stream, (const short*)coeffs, blocks, (int)h, (int)w, (int)ch, geo, tiles_x,
+                       (const unsigned char*)quant, (int)ntables, (unsigned char*)frames);
+  else
+    hipLaunchKernelGGL(jpeg_pixels_kernel<false>, grid, dim3(PBLOCK), 0, (hipStream_t)stream, (const short*)coeffs, blocks, (int)h, (int)w, (int)ch, geo, tiles_x,
+                       (const unsigned char*)quant, (int)ntables, (unsigned char*)frames);
+  TT_CHECK_LAUNCH("tt_jpeg_pixels");
+  return TT_OK;
+}

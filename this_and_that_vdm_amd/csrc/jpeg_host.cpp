@@ -130,3 +130,182 @@ extern "C" int tt_jpeg_optimized_table(const uint32_t* counts, uint8_t* bits, ui
   code_table(bits, huffval, codes);
   return TT_OK;
 }
+
+// ---------------------------------------------------------------- JPEG import, rules 1 and 2 (include/ttvdm.h)
+namespace {
+
+const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                            35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+const char* frame_kind(int marker) {
+  switch (marker) {
+    case 0xc1: return "SOF1: extended sequential";
+    case 0xc2: return "SOF2: progressive";
+    case 0xc3: return "SOF3: lossless";
+    case 0xc9: case 0xca: case 0xcb: case 0xcd: case 0xce: case 0xcf: return "arithmetic coding";
+    default: return "a differential (hierarchical) frame";
+  }
+}
+
+}  // namespace
+
+extern "C" int tt_jpeg_parse(const uint8_t* data, int64_t size, TtJpegHeader* header) {
+  if (!data || !header) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: null %s", !data ? "data" : "header");
+  if (size <= 0) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: size = %lld", (long long)size);
+  if (size < 2 || data[0] != 0xff || data[1] != 0xd8) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: no SOI marker: not a JPEG file");
+  TtJpegHeader hd;
+  memset(&hd, 0, sizeof(hd));
+  uint8_t quant[4][64];
+  bool have_quant[4] = {false, false, false, false}, have_huff[4] = {false, false, false, false}, have_frame = false;
+  int comp_id[3] = {0, 0, 0}, comp_quant[3] = {0, 0, 0};
+  int64_t at = 2;
+  for (;;) {
+    if (at + 4 > size) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before its scan (a marker segment at byte %lld)", (long long)at);
+    if (data[at] != 0xff) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: byte %lld is 0x%02x where a marker begins", (long long)at, data[at]);
+    const int marker = data[at + 1];
+    if (marker == 0xff) { ++at; continue; }                          // fill bytes before a marker
+    if (marker == 0xd9) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before its scan (EOI at byte %lld)", (long long)at);
+    if (marker == 0x01 || (marker >= 0xd0 && marker <= 0xd8)) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: marker 0x%02x at byte %lld, before the scan", marker, (long long)at);
+    const int64_t len = ((int64_t)data[at + 2] << 8) | data[at + 3];
+    if (len < 2 || at + 2 + len > size) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of segment 0x%02x at byte %lld", marker, (long long)at);
+    const uint8_t* p = data + at + 4;
+    const int64_t n = len - 2;
+    if (marker == 0xc0) {
+      if (have_frame) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a second frame header");
+      if (n < 6) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of its SOF0 segment");
+      if (p[0] != 8) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: %d-bit samples (8-bit only; 12-bit files are not decoded)", p[0]);
+      hd.h = (p[1] << 8) | p[2];
+      hd.w = (p[3] << 8) | p[4];
+      const int nc = p[5];
+      if (nc == 4) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: four components (CMYK / YCCK files are not decoded)");
+      if (nc != 1 && nc != 3) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: %d components (1: grey, or 3: YCbCr)", nc);
+      if (n < 6 + 3 * nc) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of its SOF0 segment");
+      if (hd.h <= 0 || hd.w <= 0) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a frame of %d x %d (a height of 0 waits for a DNL marker)", hd.h, hd.w);
+      hd.ch = nc;
+      int samp[3] = {0x11, 0x11, 0x11};
+      for (int c = 0; c < nc; ++c) {
+        comp_id[c] = p[6 + 3 * c];
+        samp[c] = p[7 + 3 * c];
+        comp_quant[c] = p[8 + 3 * c];
+        if (comp_quant[c] > 3) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: component %d names quantiser table %d (0 to 3)", c, comp_quant[c]);
+      }
+      if (nc == 1) hd.subsampling = TT_JPEG_444;                     // one component: whatever its sampling factors say, 1 x 1
+      else if (samp[0] == 0x11 && samp[1] == 0x11 && samp[2] == 0x11) hd.subsampling = TT_JPEG_444;
+      else if (samp[0] == 0x22 && samp[1] == 0x11 && samp[2] == 0x11) hd.subsampling = TT_JPEG_420;
+      else TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: sampling %dx%d / %dx%d / %dx%d (4:4:4 or 4:2:0; 4:2:2 and others are not decoded)", samp[0] >> 4,
+                   samp[0] & 15, samp[1] >> 4, samp[1] & 15, samp[2] >> 4, samp[2] & 15);
+      have_frame = true;
+    } else if ((marker >= 0xc1 && marker <= 0xcf) && marker != 0xc4 && marker != 0xc8 && marker != 0xcc) {
+      TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: %s (baseline SOF0 only)", frame_kind(marker));
+    } else if (marker == 0xcc) {
+      TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: arithmetic coding (a DAC segment)");
+    } else if (marker == 0xdb) {
+      int64_t k = 0;
+      while (k < n) {
+        const int pq = p[k] >> 4, tq = p[k] & 15;
+        if (pq != 0) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a 16-bit DQT (8-bit quantiser tables only)");
+        if (tq > 3) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: DQT defines table %d (0 to 3)", tq);
+        if (k + 65 > n) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of a DQT table");
+        for (int z = 0; z < 64; ++z) quant[tq][ZIGZAG[z]] = p[k + 1 + z];
+        have_quant[tq] = true;
+        k += 65;
+      }
+    } else if (marker == 0xc4) {
+      int64_t k = 0;
+      while (k < n) {
+        const int tc = p[k] >> 4, th = p[k] & 15;
+        if (tc > 1) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: DHT table class %d (0: DC, or 1: AC)", tc);
+        if (th > 1) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: Huffman table index %d (baseline: 0 or 1)", th);
+        if (k + 17 > n) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of a DHT table");
+        int total = 0;
+        for (int l = 0; l < 16; ++l) total += p[k + 1 + l];
+        if (total > 256) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: a DHT table of %d codes (256 at most)", total);
+        if (k + 17 + total > n) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of a DHT table");
+        const int slot = th * 2 + tc;                                // DC 0, AC 0, DC 1, AC 1
+        memcpy(hd.bits[slot], p + k + 1, 16);
+        memset(hd.huffval[slot], 0, 256);
+        memcpy(hd.huffval[slot], p + k + 17, (size_t)total);
+        have_huff[slot] = true;
+        k += 17 + total;
+      }
+    } else if (marker == 0xdd) {
+      if (n < 2) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of its DRI segment");
+      if (p[0] || p[1]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a restart interval of %d MCUs (files with restart markers are not decoded)", (p[0] << 8) | p[1]);
+    } else if (marker == 0xee) {
+      if (n >= 5 && memcmp(p, "Adobe", 5) == 0) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: an Adobe APP14 segment (Adobe colour transforms are not decoded)");
+    } else if (marker == 0xda) {
+      if (!have_frame) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: SOS before SOF0");
+      if (n < 1 || n != 4 + 2 * p[0]) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: an SOS segment of %lld bytes for %d components", (long long)n, n < 1 ? 0 : p[0]);
+      if (p[0] != hd.ch) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: several scans: the first holds %d of %d components (one interleaved scan only)", p[0], hd.ch);
+      for (int c = 0; c < hd.ch; ++c) {
+        if (p[1 + 2 * c] != comp_id[c]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: the scan's component %d is not the frame's (components in frame order only)", c);
+        const int td = p[2 + 2 * c] >> 4, ta = p[2 + 2 * c] & 15;
+        if (td > 1 || ta > 1) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: Huffman table index %d (baseline: 0 or 1)", td > 1 ? td : ta);
+        if (!have_huff[td * 2]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: missing DC Huffman table %d (component %d)", td, c);
+        if (!have_huff[ta * 2 + 1]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: missing AC Huffman table %d (component %d)", ta, c);
+        if (!have_quant[comp_quant[c]]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: missing quantiser table %d (component %d)", comp_quant[c], c);
+        hd.dc_table[c] = td;
+        hd.ac_table[c] = ta;
+        memcpy(hd.quant[c], quant[comp_quant[c]], 64);
+      }
+      const uint8_t* t = p + 1 + 2 * hd.ch;
+      if (t[0] != 0 || t[1] != 63 || t[2] != 0)
+        TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a scan of coefficients %d to %d, approximation 0x%02x (progressive; sequential 0 to 63 only)", t[0], t[1], t[2]);
+      hd.scan_offset = at + 2 + len;
+      break;
+    }                                                               // APPn, COM and anything else with a length: skipped
+    at += 2 + len;
+  }
+  // the entropy-coded segment ends at the first marker that is neither a stuffed FF 00 nor fill
+  int64_t i = hd.scan_offset;
+  for (;; ++i) {
+    if (i + 1 >= size) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before EOI (%lld bytes)", (long long)size);
+    if (data[i] != 0xff || data[i + 1] == 0x00) continue;
+    const int m = data[i + 1];
+    if (m == 0xd9) break;
+    if (m >= 0xd0 && m <= 0xd7) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a restart marker in the scan (files with restart markers are not decoded)");
+    if (m == 0xda || m == 0xc4 || m == 0xdb) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: several scans (marker 0x%02x behind the first; one interleaved scan only)", m);
+    TT_FAIL(TT_EINVAL, "tt_jpeg_parse: marker 0x%02x inside the scan at byte %lld", m, (long long)i);
+  }
+  hd.scan_bytes = i - hd.scan_offset;
+  *header = hd;
+  return TT_OK;
+}
+
+extern "C" int tt_jpeg_decode_table(const uint8_t* bits, const uint8_t* huffval, uint32_t* table) {
+  if (!bits || !huffval || !table) TT_FAIL(TT_EINVAL, "tt_jpeg_decode_table: null %s", !bits ? "bits" : (!huffval ? "huffval" : "table"));
+  int total = 0;
+  uint32_t space = 0;                                                // of 65536: the code space the lengths take
+  for (int l = 1; l <= 16; ++l) {
+    total += bits[l - 1];
+    space += (uint32_t)bits[l - 1] << (16 - l);
+  }
+  if (total > 256) TT_FAIL(TT_EINVAL, "tt_jpeg_decode_table: BITS counts %d codes (256 at most)", total);
+  if (space > 65536u) TT_FAIL(TT_EINVAL, "tt_jpeg_decode_table: BITS oversubscribes the code space (%u / 65536)", space);
+  memset(table, 0, sizeof(uint32_t) * TT_JPEG_DECODE_WORDS);
+  uint16_t look[256];
+  memset(look, 0, sizeof(look));
+  uint32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    table[145 + l] = (uint32_t)(k - (int32_t)code);
+    for (int i = 0; i < bits[l - 1]; ++i, ++k, ++code)
+      if (l <= 8)
+        for (uint32_t fill = 0; fill < (1u << (8 - l)); ++fill) look[((code << (8 - l)) | fill) & 255u] = (uint16_t)(l << 8 | huffval[k]);
+    table[128 + l] = bits[l - 1] ? code - 1 : 0xffffffffu;
+    code <<= 1;
+  }
+  for (int i = 0; i < 128; ++i) table[i] = look[2 * i] | (uint32_t)look[2 * i + 1] << 16;
+  for (int i = 0; i < 64; ++i)
+    table[192 + i] = huffval[4 * i] | (uint32_t)huffval[4 * i + 1] << 8 | (uint32_t)huffval[4 * i + 2] << 16 | (uint32_t)huffval[4 * i + 3] << 24;
+  return TT_OK;
+}
+
+extern "C" int64_t tt_jpeg_sequence_bits(void) { return (int64_t)TT_JPEG_SUBSEQ_BITS * TT_JPEG_DECODE_LANES; }
+
+extern "C" int64_t tt_jpeg_entropy_ws_bytes(int32_t n, int64_t max_bytes) {
+  if (n <= 0 || max_bytes <= 0 || max_bytes >= (1ll << 28)) return 0;
+  const auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
+  const int64_t chunks = (max_bytes + TT_JPEG_CHUNK - 1) / TT_JPEG_CHUNK;
+  return up(4 * (int64_t)n) + up(4 * n * chunks) + n * tt_jpeg_plain_stride(max_bytes);
+}

@@ -22,3 +22,7 @@ inline TtJpegGeometry tt_jpeg_geometry(int32_t h, int32_t w, int32_t ch, int32_t
 // the quantiser tables as the kernels take them: a kernel argument, read through scalar loads
 struct TtJpegQuant { uint8_t q[2][64]; };
 void tt_jpeg_fill_quant(int32_t quality, TtJpegQuant* out);
+// JPEG import: the lanes of the entropy decoder's one workgroup per frame, and a frame's stride in the workspace's plain (unstuffed)
+// streams: the stream, then 16 bytes the decoder's whole-dword window may read past its end
+constexpr int TT_JPEG_DECODE_LANES = 256;
+inline int64_t tt_jpeg_plain_stride(int64_t max_bytes) { return (max_bytes + 15) / 16 * 16 + 16; }

@@ -1,0 +1,159 @@
+"""Baseline JPEG files decoded on the device (include/ttvdm.h, "JPEG import"): a clip folder im_0.jpg .. im_{F-1}.jpg, a folder
+``export.write_jpegs`` wrote, a Motion-JPEG AVI or a request's image become uint8 [F, H, W, ch] NHWC device tensors holding byte for
+byte what ``np.asarray(PIL.Image.open(f))`` holds.  The host reads the files' headers (tt_jpeg_parse) and builds the decode tables
+(tt_jpeg_decode_table); only the compressed scans cross to the device, where they are unstuffed, entropy-decoded, dequantised,
+inverted, upsampled and converted.  There is no CPU fallback and no Pillow here.
+
+Not applied: EXIF orientation (``load_image`` of the reference applies it; rotate the result when the files carry one).  Refused by
+name: progressive, arithmetic and 12-bit files, restart markers, several scans, 4:2:2, CMYK / Adobe files."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+_SUBSAMPLING = {_lib.TT_JPEG_444: "4:4:4", _lib.TT_JPEG_420: "4:2:0"}
+
+
+@dataclass
+class JpegHeader:
+    """What ``parse_jpeg`` reads from one file: the geometry, ``subsampling`` ("4:4:4" / "4:2:0"; grey files are "4:4:4"), the byte range
+    of the entropy-coded scan, ``quant`` uint8 [3, 64] (per component, natural order), ``dc_table`` / ``ac_table`` (per component, 0 or
+    1) and the Huffman tables DC 0, AC 0, DC 1, AC 1 as ``bits`` uint8 [4, 16] and ``huffval`` uint8 [4, 256]."""
+    height: int
+    width: int
+    channels: int
+    subsampling: str
+    scan_offset: int
+    scan_bytes: int
+    quant: np.ndarray
+    dc_table: list
+    ac_table: list
+    bits: np.ndarray
+    huffval: np.ndarray
+
+
+def parse_jpeg(data: bytes) -> JpegHeader:
+    """One baseline JPEG file -> its header (tt_jpeg_parse); ValueError with the library's text for what is refused."""
+    lib = _lib.load()
+    hd = _lib.TtJpegHeader()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    rc = lib.tt_jpeg_parse(buf.ctypes.data if buf.size else None, buf.size, C.byref(hd))
+    if rc != 0:
+        raise ValueError(lib.tt_last_error().decode(errors="replace"))
+    return JpegHeader(hd.h, hd.w, hd.ch, _SUBSAMPLING[hd.subsampling], hd.scan_offset, hd.scan_bytes,
+                      np.ctypeslib.as_array(hd.quant).copy(), list(hd.dc_table)[:hd.ch], list(hd.ac_table)[:hd.ch],
+                      np.ctypeslib.as_array(hd.bits).copy(), np.ctypeslib.as_array(hd.huffval).copy())
+
+
+def jpeg_decode_table(bits, huffval) -> np.ndarray:
+    """BITS [16] and HUFFVAL (up to 256 symbols by ascending code) -> uint32 [256]: the table the decoder reads (tt_jpeg_decode_table)"""
+    b = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+    v = np.zeros(256, dtype=np.uint8)
+    vals = np.asarray(huffval, dtype=np.uint8).reshape(-1)
+    if b.size != 16 or vals.size > 256:
+        raise ValueError(f"jpeg_decode_table: 16 BITS and at most 256 symbols, got {b.size} and {vals.size}")
+    v[:vals.size] = vals
+    out = np.zeros(_lib.TT_JPEG_DECODE_WORDS, dtype=np.uint32)
+    check(_lib.load().tt_jpeg_decode_table(b.ctypes.data, v.ctypes.data, out.ctypes.data), "tt_jpeg_decode_table")
+    return out
+
+
+def jpeg_decode_set(tables, dc_table=(0, 1, 1), ac_table=(0, 1, 1)) -> np.ndarray:
+    """Four (BITS, HUFFVAL) pairs -- DC 0, AC 0, DC 1, AC 1 -- and the components' table indices -> uint32 [1028]: one frame's table set.
+    The defaults are the export's map: luminance on the tables 0, both chrominance components on the tables 1 (pass
+    ``export.jpeg_standard_tables()`` in ITS order DC lum, AC lum, DC chr, AC chr: the same slots)."""
+    out = np.zeros(_lib.TT_JPEG_DECODE_SET_WORDS, dtype=np.uint32)
+    for k, t in enumerate(tables):
+        bits, vals = (t.bits, t.huffval) if hasattr(t, "bits") else t
+        out[k * 256:(k + 1) * 256] = jpeg_decode_table(bits, vals)
+    word = 0
+    for c, (d, a) in enumerate(zip(dc_table, ac_table)):
+        if d not in (0, 1) or a not in (0, 1):
+            raise ValueError(f"jpeg_decode_set: table indices are 0 or 1, got DC {d} / AC {a} for component {c}")
+        word |= (d << (2 * c)) | (a << (2 * c + 1))
+    out[4 * 256] = word
+    return out
+
+
+def _read(f) -> bytes:
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    with open(os.fspath(f), "rb") as fh:
+        return fh.read()
+
+
+def decode_jpeg(files, device) -> torch.Tensor:
+    """Baseline JPEG files of ONE geometry and subsampling -- bytes or paths, one or a list -- -> uint8 [F, H, W, ch] on ``device``, ch 1
+    (grey) or 3 (RGB): Pillow's decoded pixels, byte for byte.  One upload (the scans, end to end), one readback (a status word per
+    frame).  ValueError: a file the parser refuses (its text names the cause), files that differ in size or subsampling, a frame whose
+    scan is corrupt or truncated (the frame is named)."""
+    from . import ops
+    items = list(files) if isinstance(files, (list, tuple)) else [files]
+    if not items:
+        raise ValueError("decode_jpeg: no files")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"decode_jpeg: decodes on the HIP device, got {device} (there is no CPU fallback)")
+    blobs, heads = [], []
+    for i, f in enumerate(items):
+        data = _read(f)
+        try:
+            hd = parse_jpeg(data)
+        except ValueError as e:
+            raise ValueError(f"decode_jpeg: file {i}: {e}") from None
+        if heads and (hd.height, hd.width, hd.channels, hd.subsampling) != (heads[0].height, heads[0].width, heads[0].channels, heads[0].subsampling):
+            raise ValueError(f"decode_jpeg: file {i} is {hd.height} x {hd.width} x {hd.channels} {hd.subsampling}, file 0 is {heads[0].height} x "
+                             f"{heads[0].width} x {heads[0].channels} {heads[0].subsampling}: one geometry and subsampling per call")
+        if hd.scan_bytes < 1:
+            raise ValueError(f"decode_jpeg: file {i}: an empty scan")
+        heads.append(hd)
+        blobs.append(data[hd.scan_offset:hd.scan_offset + hd.scan_bytes])
+    h0 = heads[0]
+    lens = np.array([len(b) for b in blobs], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    same_tables = all(np.array_equal(h.bits, h0.bits) and np.array_equal(h.huffval, h0.huffval) and h.dc_table == h0.dc_table and h.ac_table == h0.ac_table
+                      for h in heads[1:])
+    same_quant = all(np.array_equal(h.quant, h0.quant) for h in heads[1:])
+
+    def table_set(h):
+        pad = [0] * (3 - h.channels)
+        return jpeg_decode_set([(h.bits[k], h.huffval[k]) for k in range(4)], h.dc_table + pad, h.ac_table + pad)
+
+    sets = np.stack([table_set(h) for h in (heads[:1] if same_tables else heads)])
+    quant = np.stack([h.quant for h in (heads[:1] if same_quant else heads)])
+    scans = torch.from_numpy(np.frombuffer(b"".join(blobs), dtype=np.uint8).copy()).to(device)
+    shape = (h0.height, h0.width, h0.channels)
+    coeffs, status = ops.jpeg_entropy(scans, torch.from_numpy(offs).to(device), torch.from_numpy(lens.astype(np.int32)).to(device), int(lens.max()), shape,
+                                      h0.subsampling, torch.from_numpy(sets.view(np.int32)).to(device))
+    frames = ops.jpeg_pixels(coeffs, shape, h0.subsampling, torch.from_numpy(quant).to(device))
+    for i, s in enumerate(status.cpu().tolist()):
+        if s:
+            why = ", ".join(text for bit, text in _lib.TT_JPEG_STATUS.items() if s & bit)
+            raise ValueError(f"decode_jpeg: frame {i} is corrupt or truncated ({why}; status {s})")
+    return frames
+
+
+def read_jpegs(folder, pattern: str = "im_{idx}.jpg", device="cuda") -> torch.Tensor:
+    """``folder/pattern.format(idx=i)`` for i = 0, 1, ... up to the first missing index -- the layout the data loaders read a clip from
+    and ``export.write_jpegs`` writes -- decoded by ``decode_jpeg``."""
+    paths = []
+    while os.path.exists(os.path.join(folder, pattern.format(idx=len(paths)))):
+        paths.append(os.path.join(folder, pattern.format(idx=len(paths))))
+        if len(paths) > 1 and paths[-1] == paths[-2]:
+            raise ValueError(f"read_jpegs: pattern {pattern!r} names two frames alike (use {{idx}})")
+    if not paths:
+        raise ValueError(f"read_jpegs: {os.path.join(folder, pattern.format(idx=0))} does not exist")
+    return decode_jpeg(paths, device)
+
+
+def read_mjpeg_video(path, device="cuda") -> torch.Tensor:
+    """The frames of a Motion-JPEG AVI (``export.write_mjpeg``'s) decoded by ``decode_jpeg``."""
+    from . import export
+    return decode_jpeg(export.read_mjpeg_frames(path), device)

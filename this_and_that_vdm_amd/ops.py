@@ -1284,3 +1284,60 @@ def jpeg_scan(coeffs: torch.Tensor, shape, subsampling, tables: torch.Tensor):
     _wrote(out, "jpeg_scan")
     _wrote(lengths, "jpeg_scan")
     return out, lengths
+
+
+# ---- the JPEG import's device half (tt_jpeg_entropy / tt_jpeg_pixels; ingest.py parses the files and builds the tables)
+def jpeg_entropy(scans: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, max_bytes: int, shape, subsampling, tables: torch.Tensor):
+    """Byte-stuffed scans -> (int16 device tensor [N, blocks, 64]: ``jpeg_coeffs``' layout; int32 device tensor [N]: every frame's status
+    bits, 0 for a clean decode) (tt_jpeg_entropy).  ``scans``: uint8 device tensor holding frame f's scan at byte ``offsets[f]`` (int64
+    device tensor [N]; any layout, ``jpeg_scan``'s [N, stride] rows among them) with ``lengths[f]`` bytes (int32 device tensor [N]);
+    ``max_bytes``: a host integer no length exceeds; ``tables``: int32 device tensor [1 or N, 1028] of decode-table sets
+    (ingest.jpeg_decode_set).  Asynchronous on the current stream."""
+    lib = _lib.load()
+    h, w, ch, sub = _jpeg_shape(shape, subsampling, "jpeg_entropy")
+    for t in (scans, offsets, lengths, tables):
+        _p(t)
+    if scans.dtype != torch.uint8 or not scans.is_contiguous() or scans.numel() < 1:
+        raise RuntimeError(f"jpeg_entropy: scans must be a contiguous uint8 tensor, got {tuple(scans.shape)} {scans.dtype}")
+    n = offsets.numel()
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or n < 1 or not offsets.is_contiguous() or lengths.dtype != torch.int32 \
+            or tuple(lengths.shape) != (n,) or not lengths.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy: offsets int64 [N] and lengths int32 [N], got {tuple(offsets.shape)} {offsets.dtype} and "
+                           f"{tuple(lengths.shape)} {lengths.dtype}")
+    if tables.dtype != torch.int32 or tables.dim() != 2 or tables.shape[1] != _lib.TT_JPEG_DECODE_SET_WORDS or tables.shape[0] not in (1, n) \
+            or not tables.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy: tables must be a contiguous int32 tensor [1 or {n}, {_lib.TT_JPEG_DECODE_SET_WORDS}], got "
+                           f"{tuple(tables.shape)} {tables.dtype}")
+    if any(t.device != scans.device for t in (offsets, lengths, tables)):
+        raise RuntimeError("jpeg_entropy: scans, offsets, lengths and tables must be on one device")
+    if isinstance(max_bytes, bool) or not isinstance(max_bytes, int) or max_bytes < 1:
+        raise RuntimeError(f"jpeg_entropy: max_bytes {max_bytes!r} (a positive integer)")
+    coeffs = torch.empty((n, lib.tt_jpeg_blocks(h, w, ch, sub), 64), dtype=torch.int16, device=scans.device)
+    status = torch.empty((n,), dtype=torch.int32, device=scans.device)
+    ws = torch.empty((max(lib.tt_jpeg_entropy_ws_bytes(n, max_bytes), 16),), dtype=torch.uint8, device=scans.device)
+    check(lib.tt_jpeg_entropy(_p(scans), scans.numel(), _p(offsets), _p(lengths), max_bytes, n, h, w, ch, sub, _p(tables), tables.shape[0], _p(coeffs),
+                              _p(status), _p(ws), ws.numel(), _stream()), "tt_jpeg_entropy")
+    _wrote(coeffs, "jpeg_entropy")
+    _wrote(status, "jpeg_entropy")
+    return coeffs, status
+
+
+def jpeg_pixels(coeffs: torch.Tensor, shape, subsampling, quant: torch.Tensor) -> torch.Tensor:
+    """``jpeg_entropy``'s (or ``jpeg_coeffs``') coefficients of frames of ``shape`` (h, w, ch) and quantiser tables [1 or N, 3, 64] (uint8
+    device tensor: per component, natural order) -> uint8 device tensor [N, h, w, ch]: dequantised, inverse DCT, 4:2:0 chroma upsampled,
+    converted to RGB -- libjpeg's decoded pixels (tt_jpeg_pixels).  Asynchronous on the current stream."""
+    lib = _lib.load()
+    h, w, ch, sub = _jpeg_shape(shape, subsampling, "jpeg_pixels")
+    _p(coeffs)
+    blocks = lib.tt_jpeg_blocks(h, w, ch, sub)
+    if coeffs.dtype != torch.int16 or coeffs.dim() != 3 or tuple(coeffs.shape[1:]) != (blocks, 64) or not coeffs.is_contiguous() or coeffs.shape[0] < 1:
+        raise RuntimeError(f"jpeg_pixels: coeffs must be a contiguous int16 tensor [N, {blocks}, 64], got {tuple(coeffs.shape)} {coeffs.dtype}")
+    n = coeffs.shape[0]
+    _p(quant)
+    if quant.dtype != torch.uint8 or quant.dim() != 3 or tuple(quant.shape[1:]) != (3, 64) or quant.shape[0] not in (1, n) or not quant.is_contiguous() \
+            or quant.device != coeffs.device:
+        raise RuntimeError(f"jpeg_pixels: quant must be a contiguous uint8 tensor [1 or {n}, 3, 64] on {coeffs.device}, got {tuple(quant.shape)} {quant.dtype}")
+    frames = torch.empty((n, h, w, ch), dtype=torch.uint8, device=coeffs.device)
+    check(lib.tt_jpeg_pixels(_p(coeffs), n, h, w, ch, sub, _p(quant), quant.shape[0], _p(frames), _stream()), "tt_jpeg_pixels")
+    _wrote(frames, "jpeg_pixels")
+    return frames

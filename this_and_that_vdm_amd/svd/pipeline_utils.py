@@ -154,6 +154,14 @@ class DevicePixels:
             raise ValueError("DevicePixels.from_pil: RGB images (uint8 [H, W, 3]) of one size; convert other modes with .convert('RGB')")
         return cls(upload_pixels(np.stack(arrs, 0), device))
 
+    @classmethod
+    def from_jpeg(cls, files, device) -> "DevicePixels":
+        """Baseline JPEG file(s) of one size -- paths or bytes -- decoded on the device (``ingest.decode_jpeg``): only the compressed
+        bytes are uploaded, and the pixels are the ones ``PIL.Image.open(f).convert("RGB")`` holds.  EXIF orientation is not applied."""
+        from .. import ingest
+        pixels = ingest.decode_jpeg(files, device)
+        return cls(pixels.expand(-1, -1, -1, 3) if pixels.shape[-1] == 1 else pixels)          # a grey file: L -> RGB repeats the channel
+
     @property
     def shape(self):
         return self.pixels.shape
