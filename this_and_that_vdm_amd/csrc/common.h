@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include "ttvdm.h"
+#include "host_common.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
@@ -24,8 +25,6 @@ template <> struct Elem<f32_tag> { static constexpr int ES = 4, EPC = 4; typedef
 // 16 zero bytes (x4 for safety) that out-of-range tile lanes point their global source at.
 static __device__ __attribute__((aligned(64))) unsigned int tt_zero_page[64] = {0};   // per-TU copy: no -fgpu-rdc needed
 
-void tt_set_error(const char* fmt, ...);
-#define TT_FAIL(code, ...) do { tt_set_error(__VA_ARGS__); return (code); } while (0)
 // the tt_*_kernel queries (host only): a kernel instance's name -- the demangled symbol without return type, parameters and namespaces,
 // every template argument written out, as a kernel trace prints it -- formatted into the caller's buffer (TT_EINVAL: it does not fit)
 int tt_put_name(const char* who, char* name, int32_t cap, const char* fmt, ...);

@@ -2,6 +2,7 @@
 // uint8 NHWC frames -- and tt_palette_map -- every pixel's nearest palette entry, the frames' squared-error sums and the per-entry
 // sums of a Lloyd step.  Integer arithmetic and integer atomics only: adds commute, every call gives the same bits.
 #include "common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -81,12 +82,6 @@ __global__ __launch_bounds__(BLOCK) void color_hist_kernel(const unsigned char* 
 
 struct PalCounts { unsigned char minus1[TT_GIF_MAX_PALETTES]; };     // ncolors - 1 per palette, as kernel arguments
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // grid (runs, n): workgroup x of frame y walks the frame's tiles of MAP_TILE pixels x, x + runs, ...; lane t of a tile holds its pixels
 // t, t + BLOCK, ..: a wave's loads and its index stores are runs of consecutive bytes
 template <bool STATS>
@@ -151,7 +146,7 @@ __global__ __launch_bounds__(BLOCK) void palette_map_kernel(const unsigned char*
       }
     }
   }
-  err = wave_sum_u64(err);
+  err = wave_sum(err);
   if (lane == 0) red_s[wave] = err;
   __syncthreads();
   if (tid == 0) {

@@ -5,8 +5,6 @@
 #include <string.h>
 #include <vector>
 
-#define TT_FAIL(code, ...) do { tt_set_error(__VA_ARGS__); return (code); } while (0)
-
 namespace {
 
 struct Box {

@@ -2,8 +2,7 @@
 // (together with lib.cpp, which holds tt_set_error), which is how tests/test_gif_export_cpu.py builds it under the sanitizers.
 #pragma once
 #include "ttvdm.h"
-
-void tt_set_error(const char* fmt, ...);           // lib.cpp
+#include "host_common.h"
 
 // GIF's LZW: codes are at most 12 bits wide, so the table ends at entry 4095
 constexpr int TT_LZW_MAX_BITS = 12;

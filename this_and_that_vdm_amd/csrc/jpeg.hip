@@ -3,6 +3,7 @@
 // tt_jpeg_scan -- the Huffman-coded, byte-stuffed scan of every frame from those coefficients and a code table.
 // Integer arithmetic only; atomics are integer adds and ORs, which commute: every call gives the same bytes.
 #include "common.h"
+#include "block_scan.h"
 #include "jpeg_host.h"
 
 namespace {
@@ -16,8 +17,7 @@ static_assert(CHUNK == 16 * SBLOCK, "a lane holds one 16-byte unit of a stuffing
 static_assert(TT_JPEG_COUNT_WORDS == 4 * TT_JPEG_TABLE_WORDS && TT_JPEG_TABLE_WORDS == 256, "four tables of 256 symbols");
 
 // ZZ[k]: the natural (row-major) index of the k-th coefficient of the zig-zag scan
-__device__ constexpr int ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__device__ constexpr int ZZ[64] = TT_JPEG_ZIGZAG;
 
 // ---------------------------------------------------------------- rule 2: colour
 __device__ __forceinline__ int to_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
@@ -264,37 +264,10 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_bits_kernel(const short* __restri
   bits[(long long)blockIdx.y * blocks + b] = total;
 }
 
-// an exclusive scan of v[0 .. count) in place, one workgroup; returns the sum.  red_s: SCAN_WAVES + 1 words
-__device__ __forceinline__ unsigned scan_in_place(unsigned* __restrict__ v, long long count, unsigned* red_s) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned carry = 0u;
-  for (long long at = 0; at < count; at += SCAN_BLOCK) {
-    const long long i = at + tid;
-    const unsigned mine = i < count ? v[i] : 0u;
-    unsigned incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned a = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += a;
-    }
-    if (lane == 63) red_s[wave] = incl;
-    __syncthreads();
-    unsigned before = carry + incl - mine, all = 0u;
-    for (int wv = 0; wv < SCAN_WAVES; ++wv) {
-      if (wv < wave) before += red_s[wv];
-      all += red_s[wv];
-    }
-    if (i < count) v[i] = before;
-    carry += all;
-    __syncthreads();
-  }
-  return carry;
-}
-
 // grid (n): the blocks' bit offsets inside their frame, and the frame's unstuffed bytes
 __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_offsets_kernel(unsigned* __restrict__ bits, long long blocks, unsigned* __restrict__ plain_bytes) {
   __shared__ unsigned red_s[SCAN_WAVES + 1];
-  const unsigned total = scan_in_place(bits + (long long)blockIdx.x * blocks, blocks, red_s);
+  const unsigned total = scan_in_place<SCAN_WAVES>(bits + (long long)blockIdx.x * blocks, blocks, red_s);
   if (threadIdx.x == 0) plain_bytes[blockIdx.x] = (total + 7u) >> 3;
 }
 
@@ -380,18 +353,15 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_ff_count_kernel(const unsigned* _
   unsigned ff = 0u;
 #pragma unroll
   for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ff += __shfl_down(ff, o, 64);
-  if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = ff;
-  __syncthreads();
-  if (threadIdx.x == 0) chunk_ff[(long long)blockIdx.y * chunks + blockIdx.x] = red_s[0] + red_s[1] + red_s[2] + red_s[3];
+  const unsigned all = block_sum<SBLOCK / 64>(ff, red_s);
+  if (threadIdx.x == 0) chunk_ff[(long long)blockIdx.y * chunks + blockIdx.x] = all;
 }
 
 // grid (n): the FF bytes before every chunk, and the frame's stuffed length
 __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_ff_scan_kernel(unsigned* __restrict__ chunk_ff, int chunks, const unsigned* __restrict__ plain_bytes,
                                                                   unsigned* __restrict__ lengths) {
   __shared__ unsigned red_s[SCAN_WAVES + 1];
-  const unsigned total = scan_in_place(chunk_ff + (long long)blockIdx.x * chunks, chunks, red_s);
+  const unsigned total = scan_in_place<SCAN_WAVES>(chunk_ff + (long long)blockIdx.x * chunks, (long long)chunks, red_s);
   if (threadIdx.x == 0) lengths[blockIdx.x] = plain_bytes[blockIdx.x] + total;
 }
 
@@ -399,7 +369,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_ff_scan_kernel(unsigned* __re
 __global__ __launch_bounds__(SBLOCK) void jpeg_stuff_kernel(const unsigned* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
                                                             const unsigned* __restrict__ chunk_ff, int chunks, unsigned char* __restrict__ out, long long stride) {
   __shared__ unsigned red_s[SBLOCK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned by[4];
   int have;
   long long at;
@@ -407,16 +376,8 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_stuff_kernel(const unsigned* __re
   unsigned ff = 0u;
 #pragma unroll
   for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu;
-  unsigned incl = ff;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned a = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += a;
-  }
-  if (lane == 63) red_s[wave] = incl;
-  __syncthreads();
-  unsigned before = incl - ff;
-  for (int wv = 0; wv < wave; ++wv) before += red_s[wv];
+  unsigned all;
+  const unsigned before = block_scan_excl<SBLOCK / 64>(ff, red_s, all);
   long long pos = at + chunk_ff[(long long)blockIdx.y * chunks + blockIdx.x] + before;
   unsigned char* __restrict__ dst = out + (long long)blockIdx.y * stride;
 #pragma unroll
@@ -433,24 +394,12 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_stuff_kernel(const unsigned* __re
   }
 }
 
-int refuse_shape(const char* who, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling) {
-  if (n <= 0 || h <= 0 || w <= 0) TT_FAIL(TT_EINVAL, "%s: empty problem (n = %d, h = %d, w = %d)", who, n, h, w);
-  if (ch != 1 && ch != 3) TT_FAIL(TT_EINVAL, "%s: %d channels (1: grey, or 3: RGB; JPEG has no alpha)", who, ch);
-  if (subsampling != TT_JPEG_444 && subsampling != TT_JPEG_420)
-    TT_FAIL(TT_EINVAL, "%s: subsampling = %d (0: 4:4:4, or 2: 4:2:0)", who, subsampling);
-  if ((long long)h * w * ch >= (1ll << 31)) TT_FAIL(TT_EUNSUPPORTED, "%s: a frame of %lld bytes (below 2^31)", who, (long long)h * w * ch);
-  if (tt_jpeg_scan_bound(h, w, ch, subsampling) >= (1ll << 31))
-    TT_FAIL(TT_EUNSUPPORTED, "%s: a scan bound of %lld bytes per frame (below 2^31)", who, (long long)tt_jpeg_scan_bound(h, w, ch, subsampling));
-  if (n > 65535) TT_FAIL(TT_EUNSUPPORTED, "%s: %d frames: more than one grid covers (65535)", who, n);
-  return TT_OK;
-}
-
 }  // namespace
 
 extern "C" int tt_jpeg_coeffs(const void* frames, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t quality, int32_t subsampling, int16_t* coeffs,
                               uint32_t* counts, tt_stream_t stream) {
   if (!frames || !coeffs) TT_FAIL(TT_EINVAL, "tt_jpeg_coeffs: null %s", !frames ? "frames" : "coeffs");
-  const int rc = refuse_shape("tt_jpeg_coeffs", n, h, w, ch, subsampling);
+  const int rc = tt_jpeg_refuse_shape("tt_jpeg_coeffs", n, h, w, ch, subsampling, "; JPEG has no alpha");
   if (rc != TT_OK) return rc;
   if (quality < 1 || quality > 100) TT_FAIL(TT_EINVAL, "tt_jpeg_coeffs: quality = %d (1 to 100)", quality);
   if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_coeffs: coeffs is not 16-byte aligned");
@@ -482,7 +431,7 @@ extern "C" int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t
                             int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream) {
   if (!coeffs || !tables || !out || !lengths || !ws)
     TT_FAIL(TT_EINVAL, "tt_jpeg_scan: null %s", !coeffs ? "coeffs" : (!tables ? "tables" : (!out ? "out" : (!lengths ? "lengths" : "ws"))));
-  const int rc = refuse_shape("tt_jpeg_scan", n, h, w, ch, subsampling);
+  const int rc = tt_jpeg_refuse_shape("tt_jpeg_scan", n, h, w, ch, subsampling, "; JPEG has no alpha");
   if (rc != TT_OK) return rc;
   if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ntables = %d (1, or one set per frame: %d)", ntables, n);
   if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: coeffs is not 16-byte aligned");
@@ -493,22 +442,17 @@ extern "C" int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t
   const long long stride = tt_jpeg_scan_bound(h, w, ch, subsampling);
   if (cap < (long long)n * stride)
     TT_FAIL(TT_EINVAL, "tt_jpeg_scan: cap too small: %lld bytes, %d frames at tt_jpeg_scan_bound = %lld take %lld", (long long)cap, n, stride, (long long)n * stride);
-  if (ws_bytes < tt_jpeg_scan_ws_bytes(n, h, w, ch, subsampling))
-    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ws too small: %lld bytes, tt_jpeg_scan_ws_bytes = %lld", (long long)ws_bytes,
-            (long long)tt_jpeg_scan_ws_bytes(n, h, w, ch, subsampling));
+  const TtJpegScanWs lay(n, h, w, ch, subsampling);
+  if (ws_bytes < lay.total)
+    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ws too small: %lld bytes, tt_jpeg_scan_ws_bytes = %lld", (long long)ws_bytes, (long long)lay.total);
   const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
   const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
-  const auto up = [](long long v) { return (v + 15) / 16 * 16; };
-  const long long plain_stride = up(stride / 2);                   // the layout tt_jpeg_scan_ws_bytes sizes
-  const int chunks = (int)((stride / 2 + CHUNK - 1) / CHUNK);
-  char* p = (char*)ws;
-  unsigned* bits = (unsigned*)p;
-  p += up(4 * n * blocks);
-  unsigned* plain_bytes = (unsigned*)p;
-  p += up(4 * (long long)n);
-  unsigned* chunk_ff = (unsigned*)p;
-  p += up(4ll * n * chunks);
-  unsigned* plain = (unsigned*)p;
+  const long long plain_stride = lay.plain_stride;
+  const int chunks = (int)lay.chunks;
+  unsigned* bits = (unsigned*)((char*)ws + lay.bits);
+  unsigned* plain_bytes = (unsigned*)((char*)ws + lay.plain_bytes);
+  unsigned* chunk_ff = (unsigned*)((char*)ws + lay.chunk_ff);
+  unsigned* plain = (unsigned*)((char*)ws + lay.plain);
   const hipStream_t s = (hipStream_t)stream;
   const dim3 per_block((unsigned)((blocks + SBLOCK - 1) / SBLOCK), (unsigned)n), per_chunk((unsigned)chunks, (unsigned)n);
   const hipError_t e = hipMemsetAsync(plain, 0, (size_t)(n * plain_stride), s);

@@ -3,6 +3,7 @@
 // tt_jpeg_pixels -- dequantiser, the jidctint inverse DCT, fancy 4:2:0 chroma upsampling and the colour conversion in one launch.
 // Integer arithmetic only; the one atomic is an OR into a frame's status word: every call gives the same bytes.
 #include "common.h"
+#include "block_scan.h"
 #include "jpeg_host.h"
 
 namespace {
@@ -18,8 +19,7 @@ static_assert(SUBSEQ % 32 == 0 && SUBSEQ >= 64, "a subsequence is whole dwords a
 constexpr int PBLOCK = 256, TILE_W = 256;           // the reconstruction's tile: one MCU row down, TILE_W pixels across
 
 // ZZ[k]: the natural (row-major) index of the k-th coefficient of the zig-zag scan
-__device__ constexpr int ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__device__ constexpr int ZZ[64] = TT_JPEG_ZIGZAG;
 
 // ---------------------------------------------------------------- rule 3: unstuffing
 // frame f's stuffed scan: its first byte and its length, both held inside `scans`; a span that is not gives an empty frame
@@ -66,41 +66,11 @@ __global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_count_kernel(const unsign
   unsigned len;
   bool bad, marker;
   const unsigned char* src = frame_span(scans, scans_bytes, offsets, lengths, max_bytes, blockIdx.y, len, bad);
-  unsigned drops = __popc(chunk_drops(src, len, raw_s, marker));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) drops += __shfl_down(drops, o, 64);
-  if ((threadIdx.x & 63) == 0) red_s[threadIdx.x >> 6] = drops;
+  const unsigned drops = __popc(chunk_drops(src, len, raw_s, marker));
   const unsigned flags = (marker ? TT_JPEG_STATUS_MARKER : 0u) | ((bad && blockIdx.x == 0 && threadIdx.x == 0) ? TT_JPEG_STATUS_SPAN : 0u);
   if (flags) atomicOr(&status[blockIdx.y], flags);
-  __syncthreads();
-  if (threadIdx.x == 0) chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x] = red_s[0] + red_s[1] + red_s[2] + red_s[3];
-}
-
-// an exclusive scan of v[0 .. count) in place, one workgroup; returns the sum.  red_s: SCAN_WAVES words
-__device__ __forceinline__ unsigned scan_in_place(unsigned* __restrict__ v, long long count, unsigned* red_s) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned carry = 0u;
-  for (long long at = 0; at < count; at += SCAN_BLOCK) {
-    const long long i = at + tid;
-    const unsigned mine = i < count ? v[i] : 0u;
-    unsigned incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned a = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += a;
-    }
-    if (lane == 63) red_s[wave] = incl;
-    __syncthreads();
-    unsigned before = carry + incl - mine, all = 0u;
-    for (int wv = 0; wv < SCAN_WAVES; ++wv) {
-      if (wv < wave) before += red_s[wv];
-      all += red_s[wv];
-    }
-    if (i < count) v[i] = before;
-    carry += all;
-    __syncthreads();
-  }
-  return carry;
+  const unsigned all = block_sum<UBLOCK / 64>(drops, red_s);
+  if (threadIdx.x == 0) chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x] = all;
 }
 
 // grid (n): the dropped bytes before every chunk, and the frame's plain (unstuffed) length
@@ -108,7 +78,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_unstuff_scan_kernel(unsigned*
                                                                       const unsigned* __restrict__ lengths, long long scans_bytes, long long max_bytes,
                                                                       unsigned* __restrict__ plain_bytes) {
   __shared__ unsigned red_s[SCAN_WAVES];
-  const unsigned total = scan_in_place(chunk_drop + (long long)blockIdx.x * chunks, chunks, red_s);
+  const unsigned total = scan_in_place<SCAN_WAVES>(chunk_drop + (long long)blockIdx.x * chunks, (long long)chunks, red_s);
   if (threadIdx.x == 0) {
     unsigned len;
     bool bad;
@@ -123,22 +93,11 @@ __global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_gather_kernel(const unsig
                                                                     int chunks, unsigned char* __restrict__ plain, long long plain_stride) {
   __shared__ unsigned char raw_s[CHUNK + 16];
   __shared__ unsigned red_s[UBLOCK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned len;
+  unsigned len, all;
   bool bad, marker;
   const unsigned char* src = frame_span(scans, scans_bytes, offsets, lengths, max_bytes, blockIdx.y, len, bad);
   const unsigned mask = chunk_drops(src, len, raw_s, marker);
-  const unsigned mine = __popc(mask);
-  unsigned incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned a = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += a;
-  }
-  if (lane == 63) red_s[wave] = incl;
-  __syncthreads();
-  unsigned before = incl - mine + chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x];
-  for (int wv = 0; wv < wave; ++wv) before += red_s[wv];
+  const unsigned before = chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x] + block_scan_excl<UBLOCK / 64>((unsigned)__popc(mask), red_s, all);
   const unsigned at0 = blockIdx.x * (unsigned)CHUNK + 16 * threadIdx.x;
   unsigned char* __restrict__ dst = plain + (long long)blockIdx.y * plain_stride;
   long long pos = (long long)at0 - before;
@@ -245,7 +204,7 @@ __global__ __launch_bounds__(ELANES) void jpeg_entropy_kernel(const unsigned cha
   __shared__ unsigned tab_s[TT_JPEG_DECODE_SET_WORDS];
   __shared__ unsigned ex_p[ELANES], ex_mz[ELANES];
   __shared__ unsigned red_s[EWAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const unsigned* __restrict__ tset = tables + (ntables > 1 ? (long long)blockIdx.x * TT_JPEG_DECODE_SET_WORDS : 0);
   for (int i = tid; i < TT_JPEG_DECODE_SET_WORDS; i += ELANES) tab_s[i] = tset[i];
   const unsigned nbytes = (unsigned)min((long long)plain_bytes[blockIdx.x], max_bytes);
@@ -298,20 +257,9 @@ __global__ __launch_bounds__(ELANES) void jpeg_entropy_kernel(const unsigned cha
         ex_mz[tid] = x.mz;
       }
     }
-    // every lane's first block: an exclusive scan of the blocks completed
-    unsigned incl = done;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned a = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += a;
-    }
-    if (lane == 63) red_s[wave] = incl;
-    __syncthreads();                                 // also: every ex_p / ex_mz of the last pass is stored
-    unsigned first = base + incl - done, all = 0u;
-    for (int wv = 0; wv < EWAVES; ++wv) {
-      if (wv < wave) first += red_s[wv];
-      all += red_s[wv];
-    }
+    // every lane's first block: an exclusive scan of the blocks completed.  Its barrier also: every ex_p / ex_mz of the last pass is stored
+    unsigned all;
+    const unsigned first = base + block_scan_excl<EWAVES>(done, red_s, all);
     x = used;
     decode_span<true>(win_s, win0, tab_s, fr, start, end, x, out, first, err);
     carried.p = ex_p[last];
@@ -330,7 +278,7 @@ __global__ __launch_bounds__(ELANES) void jpeg_entropy_kernel(const unsigned cha
 // grid (n), SCAN_BLOCK lanes: one lane per MCU, a prefix sum per component over the DC differences (int32), stored as int16
 __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_dc_kernel(short* __restrict__ coeffs, long long blocks, int bpm) {
   __shared__ int red_s[SCAN_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   short* __restrict__ fc = coeffs + (long long)blockIdx.x * blocks * 64;
   const long long mcus = blocks / bpm;
   const int ncomp = bpm == 1 ? 1 : 3, ny = bpm == 6 ? 4 : 1;
@@ -342,19 +290,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_dc_kernel(short* __restrict__
       int d[4] = {0, 0, 0, 0}, mine = 0;
       if (u < mcus)
         for (int k = 0; k < nk; ++k) { d[k] = fc[(u * bpm + k0 + k) * 64]; mine += d[k]; }
-      int incl = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int a = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += a;
-      }
-      if (lane == 63) red_s[wave] = incl;
-      __syncthreads();
-      int before = carry[c] + incl - mine, all = 0;
-      for (int wv = 0; wv < SCAN_WAVES; ++wv) {
-        if (wv < wave) before += red_s[wv];
-        all += red_s[wv];
-      }
+      int all;
+      int before = carry[c] + block_scan_excl<SCAN_WAVES>(mine, red_s, all);
       if (u < mcus)
         for (int k = 0; k < nk; ++k) { before += d[k]; fc[(u * bpm + k0 + k) * 64] = (short)before; }
       carry[c] += all;
@@ -484,18 +421,6 @@ template <bool SUB> __global__ __launch_bounds__(PBLOCK) void jpeg_pixels_kernel
   }
 }
 
-int refuse_shape(const char* who, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling) {
-  if (n <= 0 || h <= 0 || w <= 0) TT_FAIL(TT_EINVAL, "%s: empty problem (n = %d, h = %d, w = %d)", who, n, h, w);
-  if (ch != 1 && ch != 3) TT_FAIL(TT_EINVAL, "%s: %d channels (1: grey, or 3: RGB)", who, ch);
-  if (subsampling != TT_JPEG_444 && subsampling != TT_JPEG_420)
-    TT_FAIL(TT_EINVAL, "%s: subsampling = %d (0: 4:4:4, or 2: 4:2:0)", who, subsampling);
-  if ((long long)h * w * ch >= (1ll << 31)) TT_FAIL(TT_EUNSUPPORTED, "%s: a frame of %lld bytes (below 2^31)", who, (long long)h * w * ch);
-  if (tt_jpeg_scan_bound(h, w, ch, subsampling) >= (1ll << 31))
-    TT_FAIL(TT_EUNSUPPORTED, "%s: a scan bound of %lld bytes per frame (below 2^31)", who, (long long)tt_jpeg_scan_bound(h, w, ch, subsampling));
-  if (n > 65535) TT_FAIL(TT_EUNSUPPORTED, "%s: %d frames: more than one grid covers (65535)", who, n);
-  return TT_OK;
-}
-
 }  // namespace
 
 extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, int64_t max_bytes, int32_t n,
@@ -504,7 +429,7 @@ extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const 
   if (!scans || !offsets || !lengths || !tables || !coeffs || !status || !ws)
     TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: null %s",
             !scans ? "scans" : (!offsets ? "offsets" : (!lengths ? "lengths" : (!tables ? "tables" : (!coeffs ? "coeffs" : (!status ? "status" : "ws"))))));
-  const int rc = refuse_shape("tt_jpeg_entropy", n, h, w, ch, subsampling);
+  const int rc = tt_jpeg_refuse_shape("tt_jpeg_entropy", n, h, w, ch, subsampling, "");
   if (rc != TT_OK) return rc;
   if (scans_bytes <= 0 || max_bytes <= 0) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: empty scans (scans_bytes = %lld, max_bytes = %lld)", (long long)scans_bytes, (long long)max_bytes);
   if (max_bytes >= (1ll << 28)) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_entropy: max_bytes = %lld (a scan below 2^28 bytes)", (long long)max_bytes);
@@ -515,19 +440,16 @@ extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const 
   if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: coeffs is not 16-byte aligned");
   if ((uintptr_t)status & 3) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: status is not 4-byte aligned");
   if ((uintptr_t)ws & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ws is not 16-byte aligned");
-  if (ws_bytes < tt_jpeg_entropy_ws_bytes(n, max_bytes))
-    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ws too small: %lld bytes, tt_jpeg_entropy_ws_bytes = %lld", (long long)ws_bytes, (long long)tt_jpeg_entropy_ws_bytes(n, max_bytes));
+  const TtJpegEntropyWs lay(n, max_bytes);
+  if (ws_bytes < lay.total)
+    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ws too small: %lld bytes, tt_jpeg_entropy_ws_bytes = %lld", (long long)ws_bytes, (long long)lay.total);
   const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
   const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
-  const auto up = [](long long v) { return (v + 15) / 16 * 16; };
-  const int chunks = (int)((max_bytes + CHUNK - 1) / CHUNK);
-  const long long plain_stride = tt_jpeg_plain_stride(max_bytes);   // the layout tt_jpeg_entropy_ws_bytes sizes
-  char* p = (char*)ws;
-  unsigned* plain_bytes = (unsigned*)p;
-  p += up(4 * (long long)n);
-  unsigned* chunk_drop = (unsigned*)p;
-  p += up(4ll * n * chunks);
-  unsigned char* plain = (unsigned char*)p;
+  const int chunks = (int)lay.chunks;
+  const long long plain_stride = lay.plain_stride;
+  unsigned* plain_bytes = (unsigned*)((char*)ws + lay.plain_bytes);
+  unsigned* chunk_drop = (unsigned*)((char*)ws + lay.chunk_drop);
+  unsigned char* plain = (unsigned char*)ws + lay.plain;
   const hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(status, 0, sizeof(uint32_t) * (size_t)n, s);
   if (e == hipSuccess) e = hipMemsetAsync(coeffs, 0, (size_t)n * (size_t)blocks * 128, s);
@@ -549,7 +471,7 @@ extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const 
 extern "C" int tt_jpeg_pixels(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint8_t* quant, int32_t ntables,
                               void* frames, tt_stream_t stream) {
   if (!coeffs || !quant || !frames) TT_FAIL(TT_EINVAL, "tt_jpeg_pixels: null %s", !coeffs ? "coeffs" : (!quant ? "quant" : "frames"));
-  const int rc = refuse_shape("tt_jpeg_pixels", n, h, w, ch, subsampling);
+  const int rc = tt_jpeg_refuse_shape("tt_jpeg_pixels", n, h, w, ch, subsampling, "");
   if (rc != TT_OK) return rc;
   if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "tt_jpeg_pixels: ntables = %d (1, or one set per frame: %d)", ntables, n);
   if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_pixels: coeffs is not 16-byte aligned");

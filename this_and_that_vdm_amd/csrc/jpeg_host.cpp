@@ -3,10 +3,9 @@
 // a reserved symbol keeping the all-ones code free) and the sizes tt_jpeg_coeffs / tt_jpeg_scan work with.  include/ttvdm.h states them
 // rule by rule; integers only, no device.
 #include "jpeg_host.h"
+#include "huffman_host.h"
 
 #include <string.h>
-
-#define TT_FAIL(code, ...) do { tt_set_error(__VA_ARGS__); return (code); } while (0)
 
 namespace {
 
@@ -74,12 +73,7 @@ extern "C" int64_t tt_jpeg_scan_bound(int32_t h, int32_t w, int32_t ch, int32_t 
 }
 
 extern "C" int64_t tt_jpeg_scan_ws_bytes(int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling) {
-  const int64_t blocks = tt_jpeg_blocks(h, w, ch, subsampling);
-  if (!blocks || n <= 0) return 0;
-  const int64_t plain = tt_jpeg_scan_bound(h, w, ch, subsampling) / 2;              // the unstuffed bits of a frame, a multiple of 8 bytes
-  const int64_t chunks = (plain + TT_JPEG_CHUNK - 1) / TT_JPEG_CHUNK;
-  const auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
-  return up(4 * n * blocks) + up(4 * (int64_t)n) + up(4 * n * chunks) + n * up(plain);
+  return TtJpegScanWs(n, h, w, ch, subsampling).total;
 }
 
 extern "C" int tt_jpeg_quant_tables(int32_t quality, uint8_t* tables) {
@@ -118,7 +112,7 @@ extern "C" int tt_jpeg_optimized_table(const uint32_t* counts, uint8_t* bits, ui
   uint8_t lengths[257];
   shifted[0] = 1;
   memcpy(shifted + 1, counts, 256 * sizeof(uint32_t));
-  const int rc = tt_png_code_lengths(shifted, 257, TT_JPEG_CODE_LIMIT, lengths);
+  const int rc = tt_code_lengths("tt_jpeg_optimized_table", shifted, 257, TT_JPEG_CODE_LIMIT, lengths);
   if (rc != TT_OK) return rc;
   memset(bits, 0, 16);
   memset(huffval, 0, 256);
@@ -134,8 +128,7 @@ extern "C" int tt_jpeg_optimized_table(const uint32_t* counts, uint8_t* bits, ui
 // ---------------------------------------------------------------- JPEG import, rules 1 and 2 (include/ttvdm.h)
 namespace {
 
-const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                            35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+const uint8_t ZIGZAG[64] = TT_JPEG_ZIGZAG;
 
 const char* frame_kind(int marker) {
   switch (marker) {
@@ -304,8 +297,5 @@ extern "C" int tt_jpeg_decode_table(const uint8_t* bits, const uint8_t* huffval,
 extern "C" int64_t tt_jpeg_sequence_bits(void) { return (int64_t)TT_JPEG_SUBSEQ_BITS * TT_JPEG_DECODE_LANES; }
 
 extern "C" int64_t tt_jpeg_entropy_ws_bytes(int32_t n, int64_t max_bytes) {
-  if (n <= 0 || max_bytes <= 0 || max_bytes >= (1ll << 28)) return 0;
-  const auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
-  const int64_t chunks = (max_bytes + TT_JPEG_CHUNK - 1) / TT_JPEG_CHUNK;
-  return up(4 * (int64_t)n) + up(4 * n * chunks) + n * tt_jpeg_plain_stride(max_bytes);
+  return TtJpegEntropyWs(n, max_bytes).total;
 }

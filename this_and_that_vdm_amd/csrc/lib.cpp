@@ -5,6 +5,7 @@
 #include <string.h>
 #include <vector>
 #include "ttvdm.h"
+#include "host_common.h"
 
 static thread_local char g_err[512] = "";
 
@@ -36,8 +37,6 @@ extern "C" const char* tt_last_error(void) { return g_err; }
 // ------------------------------------------------------------------------------------------------ tt_resample_coeffs
 // Pillow's 8-bit resampling tables (precompute_coeffs + normalize_coeffs_8bpc) of one axis, restated in fp64 with libm in the order
 // include/ttvdm.h gives: the kernels of tt_resize_u8 / tt_vae_image (image.hip) only do integer arithmetic on what this writes.
-#define TT_FAIL(code, ...) do { tt_set_error(__VA_ARGS__); return (code); } while (0)
-
 namespace {
 const double PI = 3.14159265358979323846;
 double sinc_pi(double x) { if (x == 0.0) return 1.0; x *= PI; return sin(x) / x; }

@@ -3,6 +3,7 @@
 // tile and its 10-pixel halo of both operands in LDS as fp32 (exact for both kinds), per channel a horizontal and a vertical pass in
 // fp64, 12 partial sums per tile to the workspace.  frame_metrics_finalize_kernel (one workgroup per frame) adds them in tile order.
 #include "common.h"
+#include "block_scan.h"
 #include <math.h>
 
 // every fp64 operation below is rounded on its own: the header states the arithmetic operation by operation, and a == b must give
@@ -23,12 +24,6 @@ static_assert(BLOCK == TILE * TILE, "the vertical pass gives every window of a t
 // CU's 160 KiB, so four workgroups (16 waves) stay resident per CU -- a 32 x 32 tile with fp64 rows would take 110 KB and leave one.
 
 struct Window { double g[WIN]; };
-
-__device__ __forceinline__ double wave_sum(double v) {          // a fixed tree: the same bits every time
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // rows x cols pixels (ch channels, element size ES) whose first element is at p, row pitch `pitch` bytes -> s[r * LW + e] as fp32.
 // Every aligned 16 bytes that lies inside a row's span is one vector load; what is left at the ends goes element by element.

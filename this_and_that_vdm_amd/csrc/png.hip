@@ -3,6 +3,7 @@
 // Adler-32 pair -- and tt_png_emit -- the stripes' DEFLATE blocks, bit for bit, from the code tables the host made of those counts.
 // Integer arithmetic only; LDS atomics are adds and ORs, which commute: every call gives the same bytes.
 #include "common.h"
+#include "block_scan.h"
 #include "png_host.h"
 
 namespace {
@@ -52,9 +53,7 @@ __global__ __launch_bounds__(FBLOCK) void png_filter_kernel(const unsigned char*
     }
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
-      unsigned long long s = cost[t];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+      const unsigned long long s = wave_sum(cost[t]);
       if (lane == 0) cost_s[wave][t] = s;
     }
     __syncthreads();
@@ -197,12 +196,8 @@ __global__ __launch_bounds__(BLOCK) void png_tokens_kernel(const unsigned char* 
     s1 += b;
     s2 += b * (unsigned)max(len - (base + j), 0);                     // 32 terms of at most 255 x 32768: below 2^29
   }
-  s2 %= ADLER;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s1 += __shfl_down(s1, o, 64);                                     // at most 255 x 32768 in all
-    s2 += __shfl_down(s2, o, 64);                                     // at most 1024 x 65520 in all
-  }
+  s1 = wave_sum(s1);                                                  // at most 255 x 32768 in all
+  s2 = wave_sum(s2 % ADLER);                                          // at most 1024 x 65520 in all
   if (lane == 0) { red_s[wave][0] = s1; red_s[wave][1] = s2; }
   __syncthreads();
   unsigned* rec = records + (long long)blockIdx.x * TT_PNG_RECORD_WORDS;
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(BLOCK) void png_emit_kernel(const unsigned char* __
   __shared__ unsigned tab_s[TT_PNG_TABLE_WORDS];
   __shared__ int wmax_s[WAVES], wmin_s[WAVES];
   __shared__ unsigned wsum_s[WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, base = tid * PER;
+  const int tid = threadIdx.x, base = tid * PER;
   int len;
   const unsigned char* p = stripe_of(filtered, blockIdx.x, stripes, stream, stride, len);
   if (tid < TT_PNG_TABLE_WORDS) tab_s[tid] = tables[(long long)blockIdx.x * TT_PNG_TABLE_WORDS + tid];
@@ -270,19 +265,8 @@ __global__ __launch_bounds__(BLOCK) void png_emit_kernel(const unsigned char* __
       mine += (unsigned)nbits;
     }
   }
-  unsigned incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned a = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += a;
-  }
-  if (lane == 63) wsum_s[wave] = incl;
-  __syncthreads();
-  unsigned before = incl - mine, total = 0u;
-  for (int wv = 0; wv < WAVES; ++wv) {
-    if (wv < wave) before += wsum_s[wv];
-    total += wsum_s[wv];
-  }
+  unsigned total;
+  const unsigned before = block_scan_excl<WAVES>(mine, wsum_s, total);
   const long long off = (long long)(((unsigned long long)tab_s[287] << 32) | tab_s[286]);
   const long long window = off & ~15ll;                               // the 16-byte unit of `out` the stripe starts in
   const int first = (int)(off & 15);                                  // the stripe's first byte in the window

@@ -3,59 +3,12 @@
 // call, with the code tables and byte offsets tt_png_emit reads).  include/ttvdm.h states them rule by rule; integers only.
 #include "png_host.h"
 
+#include "huffman_host.h"
+
 #include <string.h>
-#include <algorithm>
 #include <vector>
 
-#define TT_FAIL(code, ...) do { tt_set_error(__VA_ARGS__); return (code); } while (0)
-
 namespace {
-
-struct Item {
-  uint64_t weight;
-  bool leaf;
-};
-
-// rule 4 of the header.  `used` symbols in ascending (count, symbol); lengths is zeroed by the caller.  false: 2^limit < used symbols
-bool package_merge(const uint32_t* counts, const std::vector<int>& used, int limit, uint8_t* lengths) {
-  const size_t u = used.size(), keep = 2 * u - 2;
-  std::vector<std::vector<Item>> lists((size_t)limit);
-  for (int s : used) lists[0].push_back({counts[s], true});
-  for (int l = 1; l < limit; ++l) {
-    const std::vector<Item>& prev = lists[l - 1];
-    std::vector<Item>& cur = lists[l];
-    cur.reserve(keep);
-    size_t leaf = 0, pack = 0;
-    const size_t packs = prev.size() / 2;
-    while (cur.size() < keep && (leaf < u || pack < packs)) {
-      const uint64_t pw = pack < packs ? prev[2 * pack].weight + prev[2 * pack + 1].weight : 0;
-      if (leaf < u && (pack >= packs || counts[used[leaf]] <= pw)) cur.push_back({counts[used[leaf++]], true});      // <=: a leaf before a package
-      else { cur.push_back({pw, false}); ++pack; }
-    }
-  }
-  size_t take = keep;
-  if (lists[limit - 1].size() < take) return false;
-  for (int l = limit - 1; l >= 0 && take > 0; --l) {
-    size_t leaves = 0;
-    for (size_t i = 0; i < take; ++i) leaves += lists[l][i].leaf;
-    for (size_t i = 0; i < leaves; ++i) ++lengths[used[i]];
-    take = 2 * (take - leaves);
-  }
-  return true;
-}
-
-int code_lengths(const char* who, const uint32_t* counts, int nsym, int limit, uint8_t* lengths) {
-  std::vector<int> used;
-  for (int s = 0; s < nsym; ++s)
-    if (counts[s]) used.push_back(s);
-  memset(lengths, 0, (size_t)nsym);
-  if (used.empty()) TT_FAIL(TT_EINVAL, "%s: no used symbol among %d", who, nsym);
-  if (used.size() == 1) { lengths[used[0]] = 1; return TT_OK; }
-  if (((size_t)1 << limit) < used.size()) TT_FAIL(TT_EINVAL, "%s: %d used symbols do not fit codes of at most %d bits", who, (int)used.size(), limit);
-  std::stable_sort(used.begin(), used.end(), [&](int a, int b) { return counts[a] < counts[b]; });       // stable: ascending symbol inside a count
-  if (!package_merge(counts, used, limit, lengths)) TT_FAIL(TT_EINVAL, "%s: package-merge ran out of items (limit %d)", who, limit);
-  return TT_OK;
-}
 
 // canonical codes (RFC 1951 3.2.2) with their bits reversed: ready to be ORed in from the least significant bit
 void reversed_codes(const uint8_t* lengths, int nsym, uint32_t* codes) {
@@ -128,7 +81,7 @@ int block_header(const char* who, const uint32_t* counts, const uint8_t* lengths
   uint32_t cl_counts[TT_PNG_CL_SYMS] = {0}, cl_codes[TT_PNG_CL_SYMS];
   uint8_t cl_len[TT_PNG_CL_SYMS];
   for (const ClToken& t : toks) ++cl_counts[t.sym];
-  const int rc = code_lengths(who, cl_counts, TT_PNG_CL_SYMS, TT_PNG_CL_LIMIT, cl_len);
+  const int rc = tt_code_lengths(who, cl_counts, TT_PNG_CL_SYMS, TT_PNG_CL_LIMIT, cl_len);
   if (rc != TT_OK) return rc;
   reversed_codes(cl_len, TT_PNG_CL_SYMS, cl_codes);
   int hclen = 4;
@@ -163,7 +116,7 @@ extern "C" int tt_png_code_lengths(const uint32_t* counts, int32_t nsym, int32_t
   if (!counts || !lengths) TT_FAIL(TT_EINVAL, "tt_png_code_lengths: null %s", !counts ? "counts" : "lengths");
   if (nsym < 1 || nsym > TT_PNG_SYMS) TT_FAIL(TT_EINVAL, "tt_png_code_lengths: nsym = %d (1 to %d)", nsym, TT_PNG_SYMS);
   if (limit < 1 || limit > TT_PNG_LIT_LIMIT) TT_FAIL(TT_EINVAL, "tt_png_code_lengths: limit = %d (1 to %d)", limit, TT_PNG_LIT_LIMIT);
-  return code_lengths("tt_png_code_lengths", counts, nsym, limit, lengths);
+  return tt_code_lengths("tt_png_code_lengths", counts, nsym, limit, lengths);
 }
 
 extern "C" int tt_png_block_header(const uint32_t* counts, const uint8_t* lengths, uint32_t* header, int32_t cap_words, int64_t* stripe_bits_out) {
@@ -185,7 +138,7 @@ extern "C" int tt_png_plan(const uint32_t* records, int64_t nstripes, uint32_t* 
     for (int s = 0; s < TT_PNG_SYMS; ++s) tokens += counts[s];
     if (counts[256] != 1 || tokens < 2 || tokens > TT_PNG_STRIPE + 1)
       TT_FAIL(TT_EINVAL, "tt_png_plan: record %lld is not a stripe's (end-of-block count %u, %llu tokens)", (long long)i, counts[256], (unsigned long long)tokens);
-    int rc = code_lengths("tt_png_plan", counts, TT_PNG_SYMS, TT_PNG_LIT_LIMIT, lengths);
+    int rc = tt_code_lengths("tt_png_plan", counts, TT_PNG_SYMS, TT_PNG_LIT_LIMIT, lengths);
     if (rc != TT_OK) return rc;
     int64_t bits = 0;
     rc = block_header("tt_png_plan", counts, lengths, headers + i * TT_PNG_HEADER_WORDS, TT_PNG_HEADER_WORDS, &bits);

@@ -2,8 +2,7 @@
 // (together with lib.cpp, which holds tt_set_error), which is how tests/test_png_export_cpu.py builds it under the sanitizers.
 #pragma once
 #include "ttvdm.h"
-
-void tt_set_error(const char* fmt, ...);           // lib.cpp
+#include "host_common.h"
 
 constexpr int TT_PNG_LIT_LIMIT = 15;               // DEFLATE's longest literal/length code ...
 constexpr int TT_PNG_CL_LIMIT = 7;                 // ... and its longest code-length code

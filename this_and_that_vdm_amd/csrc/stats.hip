@@ -2,6 +2,7 @@
 // Two launches, no hand-off inside either: stats_kernel leaves one partial record per workgroup in the workspace, stats_finalize_kernel
 // (one workgroup) merges them in a fixed, index-ordered shape into the caller's record.  A tensor one workgroup covers does both in stats_kernel.
 #include "common.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -89,11 +90,6 @@ template <int DT> __device__ __forceinline__ void acc_vec(LaneAcc& s, unsigned* 
   }
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ unsigned wave_max(unsigned v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_down(v, o, 64));
@@ -102,11 +98,6 @@ __device__ __forceinline__ unsigned wave_max(unsigned v) {
 __device__ __forceinline__ unsigned wave_min(unsigned v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {          // a fixed tree: the same bits every time
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
 }
 

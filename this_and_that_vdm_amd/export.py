@@ -172,6 +172,27 @@ def _table(palette: np.ndarray, ncolors: int):
     return bits, tab.tobytes()
 
 
+def _write(path_or_file, data: bytes) -> None:
+    """``data`` to a binary file object, or to a new file at a path"""
+    if hasattr(path_or_file, "write"):
+        path_or_file.write(data)
+    else:
+        with open(path_or_file, "wb") as fh:
+            fh.write(data)
+
+
+def _write_numbered(who: str, files: list, folder, pattern: str) -> list:
+    """``files`` as ``folder/pattern.format(idx=i)``; returns the paths.  The folder is made when it does not exist."""
+    import os
+    os.makedirs(folder, exist_ok=True)
+    paths = [os.path.join(folder, pattern.format(idx=i)) for i in range(len(files))]
+    if len(set(paths)) != len(paths):
+        raise ValueError(f"{who}: pattern {pattern!r} names two frames alike (use {{idx}})")
+    for path, data in zip(paths, files):
+        _write(path, data)
+    return paths
+
+
 def write_gif_indexed(indices, palettes, ncolors, path_or_file, duration: float = 0.05, loop=0, palette=None) -> None:
     """Host indices uint8 [F, H, W], palettes uint8 [F or 1, 256, 3] and ncolors [F or 1] -> a GIF89a file (a path or a binary file
     object).  ``duration``: seconds per frame, written in centiseconds, rounded and at least 1.  ``loop``: repetitions in the
@@ -218,12 +239,7 @@ def write_gif_indexed(indices, palettes, ncolors, path_or_file, duration: float 
             out += [b"\x2c" + struct.pack("<HHHHB", 0, 0, w, h, 0x80 | (bits - 1)), table]
         out.append(lzw_frame(indices[i], max(2, bits)))
     out.append(b"\x3b")
-    data = b"".join(out)
-    if hasattr(path_or_file, "write"):
-        path_or_file.write(data)
-    else:
-        with open(path_or_file, "wb") as fh:
-            fh.write(data)
+    _write(path_or_file, b"".join(out))
 
 
 def write_gif(frames, path_or_file, duration: float = 0.05, loop=0, **quantize_kwargs) -> QuantizedVideo:
@@ -355,16 +371,7 @@ def encode_png(frames, filter="adaptive") -> list:
 def write_pngs(frames, folder, pattern: str = "{idx}.png", filter="adaptive") -> list:
     """``encode_png`` written as ``folder/pattern.format(idx=i)`` -- 0.png, 1.png, ... by default -- ; returns the paths.  The folder is
     made when it does not exist."""
-    import os
-    files = encode_png(frames, filter)
-    os.makedirs(folder, exist_ok=True)
-    paths = [os.path.join(folder, pattern.format(idx=i)) for i in range(len(files))]
-    if len(set(paths)) != len(paths):
-        raise ValueError(f"write_pngs: pattern {pattern!r} names two frames alike (use {{idx}})")
-    for path, data in zip(paths, files):
-        with open(path, "wb") as fh:
-            fh.write(data)
-    return paths
+    return _write_numbered("write_pngs", encode_png(frames, filter), folder, pattern)
 
 
 def write_apng(frames, path_or_file, duration: float = 0.05, loop: int = 0, filter="adaptive") -> None:
@@ -386,12 +393,7 @@ def write_apng(frames, path_or_file, duration: float = 0.05, loop: int = 0, filt
             out.append(_png_chunk(b"fdAT", struct.pack(">I", seq), z))
             seq += 1
     out.append(_png_chunk(b"IEND"))
-    data = b"".join(out)
-    if hasattr(path_or_file, "write"):
-        path_or_file.write(data)
-    else:
-        with open(path_or_file, "wb") as fh:
-            fh.write(data)
+    _write(path_or_file, b"".join(out))
 
 
 # ---- frames -> baseline JPEG files and a Motion-JPEG AVI: colour conversion, chroma downsampling, the integer DCT, the quantiser, the
@@ -512,16 +514,7 @@ def encode_jpeg(frames, quality: int = 75, subsampling: str = "4:2:0", huffman: 
 def write_jpegs(frames, folder, pattern: str = "im_{idx}.jpg", **kw) -> list:
     """``encode_jpeg(frames, **kw)`` written as ``folder/pattern.format(idx=i)`` -- im_0.jpg, im_1.jpg, ...: the layout the data loaders
     read a clip from -- ; returns the paths.  The folder is made when it does not exist."""
-    import os
-    files = encode_jpeg(frames, **kw)
-    os.makedirs(folder, exist_ok=True)
-    paths = [os.path.join(folder, pattern.format(idx=i)) for i in range(len(files))]
-    if len(set(paths)) != len(paths):
-        raise ValueError(f"write_jpegs: pattern {pattern!r} names two frames alike (use {{idx}})")
-    for path, data in zip(paths, files):
-        with open(path, "wb") as fh:
-            fh.write(data)
-    return paths
+    return _write_numbered("write_jpegs", encode_jpeg(frames, **kw), folder, pattern)
 
 
 def _jpeg_size(data: bytes):
@@ -574,12 +567,7 @@ def mjpeg_avi(files: list, fps=4) -> bytes:
 def write_mjpeg(frames, path_or_file, fps=4, **kw) -> None:
     """``encode_jpeg(frames, **kw)`` as ONE Motion-JPEG AVI (``mjpeg_avi``) at ``fps`` frames a second (an integer, a float or a Fraction);
     a path or a binary file object.  NOT H.264 and not what a browser plays."""
-    data = mjpeg_avi(encode_jpeg(frames, **kw), fps)
-    if hasattr(path_or_file, "write"):
-        path_or_file.write(data)
-    else:
-        with open(path_or_file, "wb") as fh:
-            fh.write(data)
+    _write(path_or_file, mjpeg_avi(encode_jpeg(frames, **kw), fps))
 
 
 def read_mjpeg(path_or_bytes) -> dict:
