@@ -396,12 +396,14 @@ int tt_zero_sum_round(const float* w, int64_t ldw, int32_t n, int32_t k, int32_t
  *   y[r][n] = act_out( sum_k act_in(x[r][k]) * W[n][k] + bias[n] ),  act: 0 none, 1 SiLU.
  * W is `dtype`, x/y/bias fp32.  accumulate != 0 adds into y.  k % 8 == 0 and k <= 8192 (the activated rows of x are staged
  * in LDS four at a time: 4 x k fp32; TT_EUNSUPPORTED beyond -- the path's widest MLP input is 1280).
+ * x and w are read in 16-byte vectors: TT_EINVAL when either does not start on a 16-byte boundary, when ldx or ldw is below k or
+ * ldy below n (with more than one row / column behind the stride).
  * ---------------------------------------------------------------------------------------------- */
 int tt_small_linear(const float* x, int64_t ldx, int32_t rows, int32_t k, const void* w, int64_t ldw, int32_t n,
                     const float* bias, int32_t act_in, int32_t act_out, int32_t accumulate, float* y, int64_t ldy,
                     int32_t dtype, tt_stream_t stream);
 /* diffusers Timesteps(dim, flip_sin_to_cos=True, shift=0): out[r] = [cos(t_r*f_i) | sin(t_r*f_i)], fp32.
- * `t` device fp32 [rows]. */
+ * `t` device fp32 [rows].  TT_EINVAL: ldo < dim (more than one row), rows * dim / 2 beyond 32 bits (the kernel's element index). */
 int tt_timestep_embedding(const float* t, int32_t rows, int32_t dim, float* out, int64_t ldo, tt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -414,7 +416,7 @@ int tt_timestep_embedding(const float* t, int32_t rows, int32_t dim, float* out,
  * tt_cfg3_euler_step: the use_instructpix2pix variant (:698-702), eps batch of 3 in the reference's order
  *   (first-frame e1, cond c, uncond u):  v = u + g_f*(c-u) + image_guidance_scale*(c-e1), then the same Euler update.
  * sigma scalars live on the device (sigmas[step], sigmas[step+1]) so a captured graph can be replayed
- * for every step.
+ * for every step.  TT_EINVAL (all three): h or w <= 0, h * w beyond 32 bits (the kernels hold the pixel count in an int).
  * ---------------------------------------------------------------------------------------------- */
 int tt_prep_model_input(const float* latents, const float* image_latents, const float* cond, const float* sigmas,
                         int32_t step, int32_t batch, int32_t frames, int32_t h, int32_t w, int32_t cpad,
@@ -478,11 +480,13 @@ int tt_nchw_to_tokens(const void* src, int32_t src_f32, int32_t nimg, int32_t c,
                       int32_t dtype, tt_stream_t stream);
 int tt_tokens_to_nchw(const void* src, int32_t src_f32, int64_t ld_src, int32_t nimg, int32_t c, int32_t hw, void* dst,
                       int32_t dst_f32, int32_t dtype, tt_stream_t stream);
-/* y = a + b*scale (dtype, elementwise, n multiple of 8): ControlNet residual add, unet...:485-491,501-502. */
+/* y = a + b*scale (dtype, elementwise, n multiple of 8): ControlNet residual add, unet...:485-491,501-502.
+ * a, b and y are accessed in 16-byte vectors: TT_EINVAL when one does not start on a 16-byte boundary. */
 int tt_add_scaled(const void* a, const void* b, float scale, void* y, int64_t n, int32_t dtype, tt_stream_t stream);
 /* y[r][c] = x[r][c] + rowvec[(r / rows_per_vec) % nvec][c]: the frame-position embedding added to the hidden states before
  * the temporal transformer block (transformer_temporal.py:358-359; the block's norm_in is folded into its first GEMM).
- * x, y `dtype` [rows, c] (c multiple of 8), rowvec fp32 [nvec, c]. */
+ * x, y `dtype` [rows, c] (c multiple of 8), rowvec fp32 [nvec, c].  TT_EINVAL: x, y or rowvec off a 16-byte boundary (vector accesses);
+ * ldx or ldy below c with more than one row, ld_rowvec below c with more than one vector. */
 int tt_add_rowvec(const void* x, int64_t ldx, int32_t rows, int32_t c, const float* rowvec, int64_t ld_rowvec,
                   int32_t rows_per_vec, int32_t nvec, void* y, int64_t ldy, int32_t dtype, tt_stream_t stream);
 
@@ -490,7 +494,8 @@ int tt_add_rowvec(const void* x, int64_t ldx, int32_t rows, int32_t c, const flo
  * temporal VAE decoder's mid block (one head of 512 channels over h*w tokens per frame: diffusers
  * autoencoder_kl_temporal_decoder.py MidBlockTemporalDecoder, reached from
  * svd/pipeline_stable_video_diffusion_controlnet.py:257-283) runs as  scores = tt_gemm(Q, K, out_f32)  ->  tt_softmax_rows
- * ->  tt_gemm(P, V^T): head_dim 512 is outside tt_attention's 64 / 128. */
+ * ->  tt_gemm(P, V^T): head_dim 512 is outside tt_attention's 64 / 128.  Rows are read as float4 and written four elements at a time:
+ * TT_EINVAL when x is off a 16-byte boundary or y off a boundary of four of its elements (8 bytes for the 16-bit types, 16 for fp32). */
 int tt_softmax_rows(const float* x, int64_t ldx, int32_t rows, int32_t cols, void* y, int64_t ldy, int32_t cols_pad,
                     int32_t dtype, tt_stream_t stream);
 

@@ -3,6 +3,7 @@ request sharding, max-over-ranks timing).  The denoise step itself has no collec
 import os
 import socket
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -52,6 +53,20 @@ def test_weight_broadcast_sharding_and_max_timing():
     assert [r[1] for r in res] == [True, True], "every rank must hold rank 0's weights after the broadcast"
     assert all(r[3] == 2.0 for r in res)
     assert res[0][4] == [0, 2, 4] and res[1][4] == [1, 3]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_flat_param_buffer_keeps_every_parameter_on_a_16_byte_boundary(dtype):
+    """parameters of 15, 5, 35 and 7 elements back to back would start at 30, 40 and 110 bytes (bf16): tt_small_linear reads its weights in
+    place, in 16-byte vectors, and refuses a pointer off such a boundary"""
+    m = torch.nn.Sequential(torch.nn.Linear(3, 5), torch.nn.Linear(5, 7)).to(dtype)
+    before = [p.detach().clone() for p in m.parameters()]
+    flat = flat_param_buffer(m)
+    lo, hi = flat.data_ptr(), flat.data_ptr() + flat.numel() * flat.element_size()
+    assert all(p.data_ptr() % 16 == 0 and lo <= p.data_ptr() and p.data_ptr() + p.numel() * p.element_size() <= hi for p in m.parameters())
+    assert all(torch.equal(a, b) for a, b in zip(m.parameters(), before))
+    spans = sorted((p.data_ptr(), p.numel() * p.element_size()) for p in m.parameters())
+    assert all(a + n <= b for (a, n), (b, _) in zip(spans, spans[1:]))
 
 
 def test_single_process_is_a_no_op():

@@ -445,6 +445,15 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* x, long 
 
 
 // ---- the CLIP encoders' small kernels (tt_act_rows, tt_patch_tokens, tt_embed_rows)
+// x sigmoid(1.702 x) = x / (1 + e^t), t = -1.702 x.  __expf(t) is +inf from t = 88.73 on and the quotient then -0, while the answer, x e^-t,
+// stays a normal number down to t = 91.2 (x = -53.6: 1.2e-38).  From t = 80 on 1 + e^t is e^t to e^-80 relative, and the two half-size
+// factors e^(-t/2) are finite for every t; below t = 80 (any |x| < 47) the statement and its bits are what they were.
+__device__ __forceinline__ float quick_gelu_f(float x) {
+  const float t = -1.702f * x;
+  if (t > 80.0f) { const float h = __expf(-0.5f * t); return x * h * h; }
+  return x / (1.0f + __expf(t));
+}
+
 // y = act(x) over row views, 8 elements per lane; ACT 0: exact-erf GELU (gelu_erf_f, |erf error| <= 1.5e-7), 1: x sigmoid(1.702 x)
 template <typename Tag, int ACT>
 __global__ void act_rows_kernel(const char* x, long ldx, int rows, int cv, char* y, long ldy) {
@@ -455,7 +464,7 @@ __global__ void act_rows_kernel(const char* x, long ldx, int rows, int cv, char*
     float f[8];
     load8<Tag>(x + (row * ldx + ch) * Elem<Tag>::ES, f);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = ACT == 0 ? gelu_erf_f(f[e]) : f[e] / (1.0f + __expf(-1.702f * f[e]));
+    for (int e = 0; e < 8; ++e) f[e] = ACT == 0 ? gelu_erf_f(f[e]) : quick_gelu_f(f[e]);
     store8<Tag>(y + (row * ldy + ch) * Elem<Tag>::ES, f);
   }
 }
@@ -519,6 +528,8 @@ extern "C" int tt_add_rowvec(const void* x, int64_t ldx, int32_t rows, int32_t c
   if (rows <= 0 || c <= 0 || (c & 7) || (ldx & 7) || (ldy & 7) || (ld_rowvec & 3) || rows_per_vec <= 0 || nvec <= 0)
     TT_FAIL(TT_EINVAL, "tt_add_rowvec: c and strides must be multiples of 8 (rowvec stride of 4), rows_per_vec / nvec positive");
   if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_add_rowvec: bad dtype");
+  if ((rows > 1 && (ldx < c || ldy < c)) || (nvec > 1 && ld_rowvec < c)) TT_FAIL(TT_EINVAL, "tt_add_rowvec: strides must be >= c");
+  if ((((size_t)x | (size_t)y | (size_t)rowvec) & 15)) TT_FAIL(TT_EINVAL, "tt_add_rowvec: x, y and rowvec must start on 16-byte boundaries");
   const long total = (long)rows * (c >> 3);
   long blocks = (total + 255) / 256; if (blocks > 4096) blocks = 4096;
   hipStream_t st = (hipStream_t)stream;
@@ -536,6 +547,8 @@ extern "C" int tt_softmax_rows(const float* x, int64_t ldx, int32_t rows, int32_
   if (rows <= 0 || cols <= 0 || cols_pad < cols || (cols_pad & 3) || (ldx & 3) || ldx < cols_pad || (ldy & 3) || ldy < cols_pad)
     TT_FAIL(TT_EINVAL, "tt_softmax_rows: cols_pad >= cols, cols_pad / ldx / ldy multiples of 4 and >= cols_pad (rows are read in float4)");
   if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_softmax_rows: bad dtype");
+  if (((size_t)x & 15) || ((size_t)y & (dtype == TT_F32 ? 15 : 7)))
+    TT_FAIL(TT_EINVAL, "tt_softmax_rows: x must start on a 16-byte boundary, y on one of four of its elements");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((rows + 3) / 4), block(256);
 #define TT_SM(TAG) hipLaunchKernelGGL(softmax_rows_kernel<TAG>, grid, block, 0, st, x, (long)ldx, rows, cols, (char*)y, (long)ldy, cols_pad)
@@ -551,6 +564,8 @@ extern "C" int tt_small_linear(const float* x, int64_t ldx, int32_t rows, int32_
   if (!x || !w || !y) TT_FAIL(TT_EINVAL, "tt_small_linear: null operand");
   if (rows <= 0 || rows > 32 || n <= 0 || k <= 0 || (k & 7) || (ldx & 3) || (ldw & 7)) TT_FAIL(TT_EINVAL, "tt_small_linear: rows 1..32, k %% 8 == 0, ldx %% 4 == 0");
   if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_small_linear: bad dtype");
+  if ((rows > 1 && (ldx < k || ldy < n)) || (n > 1 && ldw < k)) TT_FAIL(TT_EINVAL, "tt_small_linear: ldx and ldw must be >= k, ldy >= n");
+  if ((((size_t)x | (size_t)w) & 15)) TT_FAIL(TT_EINVAL, "tt_small_linear: x and w must start on 16-byte boundaries");
   hipStream_t st = (hipStream_t)stream;
   if (k > 8192) TT_FAIL(TT_EUNSUPPORTED, "tt_small_linear: k = %d > 8192 (four fp32 rows of x are staged in 128 KiB of LDS)", k);
   const int nb = (n + 3) / 4;
@@ -591,6 +606,8 @@ extern "C" int tt_zero_sum_round(const float* w, int64_t ldw, int32_t n, int32_t
 
 extern "C" int tt_timestep_embedding(const float* t, int32_t rows, int32_t dim, float* out, int64_t ldo, tt_stream_t stream) {
   if (!t || !out || rows <= 0 || dim <= 0 || (dim & 1)) TT_FAIL(TT_EINVAL, "tt_timestep_embedding: bad arguments");
+  if (rows > 1 && ldo < dim) TT_FAIL(TT_EINVAL, "tt_timestep_embedding: ldo must be >= dim");
+  if ((long)rows * (dim / 2) > 0x7fffffffL) TT_FAIL(TT_EINVAL, "tt_timestep_embedding: rows * dim / 2 must fit 32 bits");
   const int total = rows * (dim / 2);
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, rows, dim, out, (long)ldo);
   TT_CHECK_LAUNCH("tt_timestep_embedding");
@@ -603,6 +620,7 @@ extern "C" int tt_prep_model_input(const float* latents, const float* image_late
   if (!latents || !image_latents || !sigmas || !x) TT_FAIL(TT_EINVAL, "tt_prep_model_input: null operand");
   if (cpad < (cond ? 12 : 8) || (cpad & 7) || batch <= 0 || frames <= 0 || step < 0) TT_FAIL(TT_EINVAL, "tt_prep_model_input: cpad/batch/frames");
   if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_prep_model_input: bad dtype");
+  if (h <= 0 || w <= 0 || (long)h * w > 0x7fffffffL) TT_FAIL(TT_EINVAL, "tt_prep_model_input: h and w must be positive and h * w fit 32 bits");
   const long total = (long)batch * frames * h * w;
   long blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;
   hipStream_t st = (hipStream_t)stream;
@@ -617,6 +635,7 @@ extern "C" int tt_cfg_euler_step(const float* eps, int32_t ld_eps, float* latent
                                  int32_t step, int32_t batch, int32_t frames, int32_t h, int32_t w, tt_stream_t stream) {
   if (!eps || !latents || !sigmas) TT_FAIL(TT_EINVAL, "tt_cfg_euler_step: null operand");
   if (batch < 1 || batch > 2 || frames <= 0 || ld_eps < 4 || step < 0) TT_FAIL(TT_EINVAL, "tt_cfg_euler_step: batch must be 1 (no CFG) or 2 (uncond, cond)");
+  if (h <= 0 || w <= 0 || (long)h * w > 0x7fffffffL) TT_FAIL(TT_EINVAL, "tt_cfg_euler_step: h and w must be positive and h * w fit 32 bits");
   const long total = (long)frames * h * w;
   long blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, eps, ld_eps, latents, guidance, sigmas, step, batch, frames, h * w, 0.0f);
@@ -628,6 +647,7 @@ extern "C" int tt_cfg3_euler_step(const float* eps, int32_t ld_eps, float* laten
                                   const float* sigmas, int32_t step, int32_t frames, int32_t h, int32_t w, tt_stream_t stream) {
   if (!eps || !latents || !sigmas || !guidance) TT_FAIL(TT_EINVAL, "tt_cfg3_euler_step: null operand");
   if (frames <= 0 || h <= 0 || w <= 0 || ld_eps < 4 || step < 0) TT_FAIL(TT_EINVAL, "tt_cfg3_euler_step: bad shape");
+  if ((long)h * w > 0x7fffffffL) TT_FAIL(TT_EINVAL, "tt_cfg3_euler_step: h * w must fit 32 bits");
   const long total = (long)frames * h * w;
   long blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, eps, ld_eps, latents, guidance, sigmas, step, 3, frames, h * w, image_guidance_scale);
@@ -729,6 +749,7 @@ extern "C" int tt_tokens_to_nchw(const void* src, int32_t src_f32, int64_t ld_sr
 extern "C" int tt_add_scaled(const void* a, const void* b, float scale, void* y, int64_t n, int32_t dtype, tt_stream_t stream) {
   if (!a || !b || !y || n <= 0 || (n & 7)) TT_FAIL(TT_EINVAL, "tt_add_scaled: n must be a positive multiple of 8");
   if (dtype != TT_BF16 && dtype != TT_F16 && dtype != TT_F32) TT_FAIL(TT_EINVAL, "tt_add_scaled: bad dtype");
+  if ((((size_t)a | (size_t)b | (size_t)y) & 15)) TT_FAIL(TT_EINVAL, "tt_add_scaled: a, b and y must start on 16-byte boundaries");
   const long nvec = n >> 3;
   long blocks = (nvec + 255) / 256; if (blocks > 4096) blocks = 4096;
   hipStream_t st = (hipStream_t)stream;

@@ -93,18 +93,24 @@ def gather_floats(values, device) -> list:
 
 def flat_param_buffer(model: torch.nn.Module) -> torch.Tensor:
     """Re-home all parameters as views of ONE flat buffer (same dtype) so a model is broadcast by a single,
-    large collective (3 GB for the UNet in bf16) instead of ~1400 small ones."""
+    large collective (3 GB for the UNet in bf16) instead of ~1400 small ones.  Every parameter starts on a 16-byte boundary of the
+    buffer, as a tensor of its own would: the kernels that read a parameter in place (tt_small_linear's weights) use 16-byte vector
+    loads and refuse anything else; the few padding elements are zero."""
     params = list(model.parameters())
     dt, dev = params[0].dtype, params[0].device
     if any(p.dtype != dt or p.device != dev for p in params):
         raise ValueError("flat_param_buffer needs all parameters on one device in one dtype")
-    flat = torch.empty(sum(p.numel() for p in params), dtype=dt, device=dev)
-    off = 0
+    quantum = max(1, 16 // params[0].element_size())
+    offs, off = [], 0
     for p in params:
+        off = (off + quantum - 1) // quantum * quantum
+        offs.append(off)
+        off += p.numel()
+    flat = torch.zeros(off, dtype=dt, device=dev)
+    for p, off in zip(params, offs):
         n = p.numel()
         flat[off:off + n].copy_(p.data.reshape(-1))
         p.data = flat[off:off + n].view_as(p)
-        off += n
     if hasattr(model, "invalidate_packs"):
         model.invalidate_packs()             # kernel-ready weight packs were built from the old storage
     return flat
