@@ -893,6 +893,67 @@ int tt_gif_lzw(const uint8_t* indices /* host */, int64_t npix, int32_t min_code
                int64_t* nbytes_out /* host */);
 
 /* ------------------------------------------------------------------------------------------------
+ * GIF LZW on the device: tt_gif_lzw_frames writes the image data of every frame of a video from index maps that are already on the
+ * device (tt_palette_map's), coding each frame in independent SEGMENTS.  LZW is sequential only within one dictionary; a clear code
+ * starts a new one, and a stream may hold as many clear codes as it likes -- so a frame cut into segments, each with its own
+ * dictionary, is ordinary GIF, and the segments are coded side by side.  Opt-in (this_and_that_vdm_amd/export.py: lzw="device");
+ * tt_gif_lzw is untouched.  Integers only: the same bytes every call.  Additive: the ABI version is unchanged.
+ *
+ * The format:
+ * 1. A frame's npix indices, in raster order, are cut into segments of `segment` pixels; the last may be shorter.  `segment` is 1 ..
+ *    TT_LZW_SEGMENT_MAX; segment = 0 selects TT_LZW_SEGMENT, the built default.
+ * 2. The frame's code stream is: clear, codes of segment 0, clear, codes of segment 1, ..., clear, codes of the last segment,
+ *    end-of-information.
+ * 3. The codes of a segment are exactly what tt_gif_lzw writes for those pixels alone, between its leading clear code and its
+ *    end-of-information code: table and width start fresh (width min_code_size + 1, next entry 2^min_code_size + 2); matching is
+ *    greedy longest-match; when entry 4095 has been made, the next code is followed by a clear code and the table starts over.
+ * 4. The clear (or end-of-information) code that closes a segment is written at the width in force after the segment's last code --
+ *    one more when that code made entry 2^width, the rule tt_gif_lzw applies to its end-of-information code.  (A code's width is thus
+ *    a function of its place r behind the last clear code alone: min(12, bit length of 2^min_code_size + 1 + r).)
+ * 5. Codes are packed from the least significant bit; the last byte is padded with zeros.
+ * 6. The image data of a frame: the min-code-size byte; sub-blocks of 255 bytes, then one shorter sub-block if bytes remain (no empty
+ *    sub-block when the data is a multiple of 255); the terminator 0.  Data byte k lies at 2 + k + k / 255.
+ * 7. The stream is a function of (indices, min_code_size, segment) only; the hash function and probing are free, because greedy LZW
+ *    has one answer.
+ * 8. Hence with segment >= npix the image data equals tt_gif_lzw's byte for byte.
+ *
+ * tt_gif_lzw_frames_bound(npix, segment): a frame's stride in out, a multiple of 16, enough for any indices (12 bits per index, per
+ * clear code of a full table, per closing code of a segment and for the first clear code, plus the framing); 0 for arguments the
+ * entry point refuses.  tt_gif_lzw_frames_ws_bytes(n, npix, segment): the workspace (per segment its code count, its bit offset and
+ * its codes as uint16); 0 likewise.
+ *
+ * tt_gif_lzw_frames: indices [n][npix] uint8 and min_code_size [nmcs] int32 on the device (nmcs == 1: one value for all frames;
+ * nmcs == n: one per frame) -> frame f's finished image data at out + f * bound, its byte count in lengths[f], and status[f]: 0, or
+ * TT_GIF_LZW_STATUS_INDEX (an index does not fit the frame's min_code_size) | TT_GIF_LZW_STATUS_MCS (a min_code_size outside 2 .. 8).
+ * The kernels clamp both, so whatever the data hold nothing is written outside out[f * bound, (f + 1) * bound) and ws; a frame with a
+ * non-zero status has a meaningless stream, its neighbours are unaffected.  Bytes of out behind a frame's length are not written.
+ * Four launches on the stream and a memset of status; no workgroup waits on another, no host readback in between, and every loop's
+ * trip count is known before it starts:
+ *   codes   -- grid (segments, n), one wave per segment: all lanes stage the segment's indices in LDS (4 KiB at a time) and clear the
+ *              string table (8192 slots of key << 12 | code, 32 KiB, never more than half full); the walk through the pixels is one
+ *              dependent chain of LDS probes, run by every lane alike on wave-uniform (scalar) values; lane 0 stores the 16-bit codes
+ *              and the segment's code count; at a full table every lane clears;
+ *   offsets -- grid (n): a segment's bit length is a closed form of its code count (rule 4); an exclusive scan over the frame's
+ *              segments gives their bit offsets, the frame's data bytes and lengths[f];
+ *   fill    -- the frame's bytes 0 .. length - 1 zeroed, with the min-code-size byte, the sub-blocks' length bytes and the terminator;
+ *   pack    -- per tile of 2048 codes: every code ORed into LDS at its bit offset (a closed form of its ordinal), the tile's bytes
+ *              ORed into the frame at their framed places (atomic OR of aligned words: neighbouring tiles share bytes at their ends).
+ * TT_EINVAL: a null pointer; n or npix <= 0; nmcs neither 1 nor n; segment < 0 or above TT_LZW_SEGMENT_MAX; out or ws off a 16-byte,
+ * lengths, status or min_code_size off a 4-byte boundary; cap < n * bound ("cap too small"); ws_bytes below
+ * tt_gif_lzw_frames_ws_bytes ("ws too small").  TT_EUNSUPPORTED: more than 65 535 frames; a frame's stride of 2^29 bytes or more (bit
+ * offsets inside a frame are 32-bit); 2^31 codes or more in the workspace (code offsets are 32-bit).  All are refused before the
+ * first HIP call; no allocation, no synchronisation. */
+#define TT_LZW_SEGMENT 16384
+#define TT_LZW_SEGMENT_MAX 65536
+#define TT_GIF_LZW_STATUS_INDEX 1
+#define TT_GIF_LZW_STATUS_MCS 2
+int64_t tt_gif_lzw_frames_bound(int64_t npix, int32_t segment);
+int64_t tt_gif_lzw_frames_ws_bytes(int32_t n, int64_t npix, int32_t segment);
+int tt_gif_lzw_frames(const uint8_t* indices /* device [n][npix] */, int32_t n, int64_t npix,
+                      const int32_t* min_code_size /* device [nmcs], nmcs 1 or n */, int32_t nmcs, int32_t segment, uint8_t* out, int64_t cap,
+                      uint32_t* lengths /* device [n] */, uint32_t* status /* device [n] */, void* ws, int64_t ws_bytes, tt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PNG export: frames written as standard 8-bit PNG files whose row filter, tokens and Huffman-coded bits are made on the device
  * (this_and_that_vdm_amd/export.py drives it).  Three kernels (tt_png_filter, tt_png_tokens, tt_png_emit) and three host routines
  * (tt_png_code_lengths, tt_png_block_header, tt_png_plan; plain C++, they touch no device).  Integers only: the same frames give the

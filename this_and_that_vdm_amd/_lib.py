@@ -104,6 +104,8 @@ class TtColorBin(C.Structure):
 
 
 TT_GIF_BINS = 32768
+TT_LZW_SEGMENT, TT_LZW_SEGMENT_MAX = 16384, 65536
+TT_GIF_LZW_STATUS = {1: "an index that does not fit min_code_size", 2: "a min_code_size outside 2 .. 8"}
 TT_PNG_STRIPE, TT_PNG_SYMS, TT_PNG_RECORD_WORDS, TT_PNG_TABLE_WORDS, TT_PNG_HEADER_WORDS = 32768, 286, 288, 288, 72
 TT_JPEG_444, TT_JPEG_420, TT_JPEG_TABLE_WORDS, TT_JPEG_COUNT_WORDS = 0, 2, 256, 1024
 TT_JPEG_CHUNK, TT_JPEG_DECODE_WORDS, TT_JPEG_DECODE_SET_WORDS = 4096, 256, 1028
@@ -207,6 +209,10 @@ SIGNATURES = {
     "tt_palette_median_cut": (C.c_int, [_vp, _i32, _vp, C.POINTER(C.c_int32), _vp]),
     "tt_gif_lzw_bound": (_i64, [_i64]),
     "tt_gif_lzw": (C.c_int, [_vp, _i64, _i32, _vp, _i64, C.POINTER(C.c_int64)]),
+    # ... and the LZW stage on the device, in independent segments (additive as well)
+    "tt_gif_lzw_frames_bound": (_i64, [_i64, _i32]),
+    "tt_gif_lzw_frames_ws_bytes": (_i64, [_i32, _i64, _i32]),
+    "tt_gif_lzw_frames": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     # the PNG export: filter, tokens and emit on the device, code lengths and block headers on the host (additive as well)
     "tt_png_stream_bytes": (_i64, [_i32, _i32, _i32]),
     "tt_png_frame_stride": (_i64, [_i32, _i32, _i32]),

@@ -1156,6 +1156,45 @@ def palette_map(frames: torch.Tensor, palettes: torch.Tensor, ncolors, stats: bo
     return indices, sse, rec
 
 
+def gif_lzw(indices: torch.Tensor, min_code_size, segment: Optional[int] = None):
+    """Device uint8 indices [N, H, W] or [N, npix] and ``min_code_size`` (an int, or one per frame: a sequence or an int32 device tensor
+    [N]) -> (data uint8 [N, bound], lengths int32 [N], status int32 [N]), all on the device: frame f's finished GIF image data -- the
+    min-code-size byte, the sub-blocks, the terminator -- is ``data[f, :lengths[f]]``, coded in independent segments of ``segment`` pixels
+    (None: the built default, TT_LZW_SEGMENT; with ``segment >= npix`` the bytes are tt_gif_lzw's).  ``status[f]`` is 0, or says that the
+    frame held an index that does not fit its min_code_size (1) or a min_code_size outside 2 .. 8 (2): its stream is then meaningless.
+    Bytes behind a frame's length are not written (tt_gif_lzw_frames).  Asynchronous on the current stream."""
+    lib = _lib.load()
+    _p(indices)
+    if indices.dtype != torch.uint8 or indices.dim() not in (2, 3) or not indices.is_contiguous() or indices.numel() == 0:
+        raise RuntimeError(f"gif_lzw: contiguous uint8 indices [N, H, W] or [N, npix], got {tuple(indices.shape)} {indices.dtype}")
+    n, npix = indices.shape[0], indices[0].numel()
+    seg = 0 if segment is None else int(segment)
+    if segment is not None and not 1 <= seg <= _lib.TT_LZW_SEGMENT_MAX:
+        raise RuntimeError(f"gif_lzw: segment = {segment!r} (1 to {_lib.TT_LZW_SEGMENT_MAX}, or None for the default {_lib.TT_LZW_SEGMENT})")
+    if torch.is_tensor(min_code_size):
+        mcs = min_code_size
+        _p(mcs)
+        if mcs.dtype != torch.int32 or mcs.dim() != 1 or mcs.numel() not in (1, n) or not mcs.is_contiguous() or mcs.device != indices.device:
+            raise RuntimeError(f"gif_lzw: min_code_size must be a contiguous int32 tensor [1 or {n}] on {indices.device}, got "
+                               f"{tuple(mcs.shape)} {mcs.dtype}")
+    else:
+        values = [int(min_code_size)] if isinstance(min_code_size, int) else [int(v) for v in min_code_size]
+        if len(values) not in (1, n):
+            raise RuntimeError(f"gif_lzw: {len(values)} min_code_size values for {n} frames (one, or one per frame)")
+        mcs = torch.tensor(values, dtype=torch.int32).to(indices.device)
+    bound = lib.tt_gif_lzw_frames_bound(npix, seg)
+    ws_bytes = lib.tt_gif_lzw_frames_ws_bytes(n, npix, seg)
+    data = torch.empty((n, max(int(bound), 16)), dtype=torch.uint8, device=indices.device)
+    lengths = torch.empty((n,), dtype=torch.int32, device=indices.device)
+    status = torch.empty((n,), dtype=torch.int32, device=indices.device)
+    ws = torch.empty((max(int(ws_bytes), 16),), dtype=torch.uint8, device=indices.device)
+    check(lib.tt_gif_lzw_frames(_p(indices), n, npix, _p(mcs), mcs.numel(), seg, _p(data), data.numel(), _p(lengths), _p(status), _p(ws), ws.numel(),
+                                _stream()), "tt_gif_lzw_frames")
+    for t in (data, lengths, status):
+        _wrote(t, "gif_lzw")
+    return data, lengths, status
+
+
 # ---- the PNG export's device half (tt_png_filter / tt_png_tokens / tt_png_emit; export.py drives them and holds the host half)
 PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
 

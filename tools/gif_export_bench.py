@@ -12,7 +12,17 @@
   psnr               each path's per-video PSNR to the source (Pillow's from its decoded file)
   refine4            write_gif with refine=4: time, size, PSNR
 
-A record, not a gate.  Prints one JSON line and writes it to --out (default profiles/gif_export_bench.json)."""
+With ``--lzw device`` the tool measures the LZW stage's device route instead (tt_gif_lzw_frames; export.write_gif(lzw="device")), next
+to the host coder timed in the same process, on the noisy frames above and on the smooth field without noise, once per ``--segment``
+(default 4096, 8192, 16384, 32768):
+
+  host               lzw_ms (tt_gif_lzw over the frames, host clock), write_gif_ms and the file's bytes on the host route
+  per segment        lzw_device_ms (device events around the launches of ops.gif_lzw, median), readback_ms (lengths, then the bytes in
+                     use), write_gif_ms (the whole call, lzw="device"), bytes_to_host (what those two readbacks move), bytes (the
+                     file) and its growth over the host route's file
+
+A record, not a gate.  Prints one JSON line and writes it to --out (default profiles/gif_export_bench.json, or
+profiles/gif_lzw_device_bench.json with ``--lzw device``)."""
 import argparse
 import io
 import json
@@ -105,14 +115,70 @@ def stages(dev, host, iters):
     return {k: round(v, 3) for k, v in out.items()}
 
 
+def lzw_device_rows(iters, segments):
+    """the device route of the LZW stage per input and segment size, next to the host coder in the same process"""
+    from tests import gif_reference as ref
+    from this_and_that_vdm_amd import export, ops
+    rows = []
+    for n, h, w in SIZES:
+        for name, sigma in (("noisy", SIGMA), ("smooth", 0.0)):
+            rng = np.random.default_rng(0)
+            dev = torch.from_numpy(np.stack([ref.field_frame(h, w, f, sigma, rng) for f in range(n)], 0)).cuda()
+            buf = io.BytesIO()
+            q = export.write_gif(dev, buf, duration=0.05)
+            sizes = [max(2, int(c - 1).bit_length()) for c in q.ncolors]
+            idx = torch.from_numpy(q.indices).cuda()
+
+            def host_lzw():
+                for f, m in zip(q.indices, sizes):
+                    export.lzw_frame(f, m)
+
+            row = dict(frames=[n, h, w, 3], input=name,
+                       host=dict(lzw_ms=round(wall_ms(host_lzw, iters), 3), write_gif_ms=round(wall_ms(lambda: export.write_gif(dev, io.BytesIO()), iters), 2),
+                                 bytes=len(buf.getvalue())), segments=[])
+            for seg in segments:
+                out = io.BytesIO()
+                export.write_gif(dev, out, duration=0.05, lzw="device", segment=seg)
+                data, lengths, _ = ops.gif_lzw(idx, sizes, seg)
+                used = int(lengths.max())
+
+                def readback():
+                    top = int(lengths.cpu().max())
+                    data[:, :top].cpu()
+
+                row["segments"].append(dict(
+                    segment=seg, lzw_device_ms=round(events_us(lambda: ops.gif_lzw(idx, sizes, seg), iters) / 1e3, 3), readback_ms=round(wall_ms(readback, iters), 3),
+                    write_gif_ms=round(wall_ms(lambda: export.write_gif(dev, io.BytesIO(), lzw="device", segment=seg), iters), 2),
+                    bytes_to_host=8 * n + n * used, bytes=len(out.getvalue()),
+                    growth_percent=round(100.0 * (len(out.getvalue()) - len(buf.getvalue())) / len(buf.getvalue()), 2)))
+            rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--no-pillow", action="store_true", help="skip Pillow's side")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "gif_export_bench.json"))
+    ap.add_argument("--lzw", choices=("host", "device"), default="host", help="device: measure the LZW stage's device route (see above)")
+    ap.add_argument("--segment", type=int, action="append", help="with --lzw device: a segment size to measure (repeatable)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "gif_lzw_device_bench.json" if a.lzw == "device" else "gif_export_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("gif_export_bench: needs a GPU (there is no CPU fallback)")
+    if a.lzw == "device":
+        res = dict(tool="gif_export_bench --lzw device", device=torch.cuda.get_device_name(0), cpu_threads=torch.get_num_threads(), iters=a.iters,
+                   inputs=f"the colour field of tests/gif_reference.py, frames 0 .. 13: noisy = plus N(0, {SIGMA:g}^2) noise, smooth = without",
+                   rows=lzw_device_rows(a.iters, a.segment or [4096, 8192, 16384, 32768]),
+                   says="a record, not a gate; lzw_device_ms is device events around ops.gif_lzw (allocations and the launches), the rest the host "
+                        "clock around synchronised calls; the host coder is timed in the same process")
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps(res))
+        return
     from tests import gif_reference as ref
     from this_and_that_vdm_amd import export
     rows = []
