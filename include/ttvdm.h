@@ -1064,8 +1064,8 @@ int tt_png_plan(const uint32_t* records /* host */, int64_t nstripes, uint32_t* 
  * tt_jpeg_optimized_table; plain C++, they touch no device).  Baseline JPEG as libjpeg writes it is integers from end to end: the same
  * frames give the same bytes every time, and with the standard tables the scan equals libjpeg's ("islow" DCT) byte for byte.
  * Additive: the ABI version is unchanged.  Only the finished scans and their lengths (and, for optimized tables, 4 KiB of counts per
- * frame) reach the host.  Not here: progressive and arithmetic coding, 4:2:2, restart markers, EXIF / ICC, CMYK, 12-bit samples,
- * trellis quantisation, a decoder.
+ * frame) reach the host.  Restart intervals are rule 6a.  Not here: progressive and arithmetic coding, 4:2:2, EXIF / ICC, CMYK, 12-bit
+ * samples, trellis quantisation.
  *
  * Input: frames [n, h, w, ch] uint8 NHWC on the device, ch 1 (grey) or 3 (RGB).  subsampling: TT_JPEG_444 (0) or TT_JPEG_420 (2);
  * a grey frame has one component and ignores it.
@@ -1096,11 +1096,27 @@ int tt_png_plan(const uint32_t* records /* host */, int64_t nstripes, uint32_t* 
  *    luminance, DC chrominance, AC chrominance, indexed by symbol.
  *    TT_EINVAL: null frames / coeffs; n, h or w <= 0; ch not 1 or 3; quality outside 1 .. 100; subsampling not 0 or 2; coeffs or
  *    counts off a 16-byte boundary.  TT_EUNSUPPORTED: a frame of 2^31 bytes or more; a scan bound of 2^31 bytes or more; n > 65535.
- * 6. Entropy coding: baseline sequential Huffman, one interleaved scan, no restart markers.  DC: the difference to the previous
+ * 6. Entropy coding: baseline sequential Huffman, one interleaved scan, no restart markers (6a adds them).  DC: the difference to the previous
  *    block of the same component in scan order (0 before the first), as its size category (the bits of |diff|) and that many
  *    magnitude bits (diff, or diff - 1 when negative, low bits).  AC: over zig-zag 1 .. 63, symbol (run of zeros << 4 | size) with the
  *    magnitude bits; 0xF0 stands for 16 zeros; 0x00 (EOB) only when the block ends in zeros.  Codes go MSB first, a 0x00 follows
  *    every 0xFF byte, the last byte is filled with one-bits.
+ * 6a. Restart intervals, as libjpeg writes them (restart_interval = Ri MCUs, 1 .. 65535; 0: none, rule 6 as it stands).  The scan is cut
+ *    into ceil(MCUs / Ri) intervals of Ri MCUs (the last may be shorter).  (i) The DC predictor of every component is 0 at the first MCU
+ *    of an interval.  (ii) Behind the last block of every interval but the frame's last the byte is filled with one-bits; a filled byte
+ *    that comes out as 0xFF IS stuffed; then FF D0 + (k mod 8) follows for the k-th marker (k from 0), NOT stuffed.  (iii) No marker
+ *    stands behind the last interval, also when the MCU count is a multiple of Ri: ceil(MCUs / Ri) - 1 markers; Ri >= MCUs writes none.
+ *    (iv) The file carries FF DD 00 04 Ri directly before SOS (rule 8).  (v) The symbol counts of an optimized table are taken with the
+ *    same predictor resets: tt_jpeg_counts_restart recounts tt_jpeg_coeffs' coefficients (counts zeroed, one launch).
+ *    tt_jpeg_scan_restart is tt_jpeg_scan with the interval; tt_jpeg_scan IS its restart_interval = 0: the same kernels.  The offsets
+ *    scan, still one workgroup per frame, then takes per interval the bits its pad and marker add (pad to a byte + 16) and scans those;
+ *    the lane of an interval's last block writes pad and marker and sets the bit of the marker's FF byte in a per-frame bitmap of the
+ *    unstuffed bytes (one more memset); the stuffing passes skip the bytes whose bit is set -- a marker is known by its POSITION, never
+ *    by its value: a data FF followed by D0 .. D7 is legal in the unstuffed stream.  No host round trip with standard tables.
+ *    tt_jpeg_scan_bound_restart: tt_jpeg_scan_bound plus, per marker, pad 1 + marker 2 bytes, the pad doubled when stuffed (4), taken as
+ *    6 so that half the bound still holds the unstuffed stream; rounded up to 16; 0 for refused arguments; restart_interval 0 gives
+ *    tt_jpeg_scan_bound.  It is the frame stride of out; ws: tt_jpeg_scan_restart_ws_bytes.  TT_EINVAL as tt_jpeg_scan, and
+ *    restart_interval outside 0 .. 65535.
  * 7. Huffman tables.  A table is BITS[16] (codes per length), HUFFVAL (symbols by ascending code) and, for the device, 256 uint32:
  *    per symbol its canonical code (T.81 Annex C) | length << 16.  tt_jpeg_standard_table (host): `which` 0 .. 3 (DC luminance, AC
  *    luminance, DC chrominance, AC chrominance) -> the Annex K.3 table.  tt_jpeg_optimized_table (host): counts[256] -> the table of
@@ -1120,7 +1136,7 @@ int tt_png_plan(const uint32_t* records /* host */, int64_t nstripes, uint32_t* 
  *    coeffs, tables, out or ws off a 16-byte boundary; cap < n tt_jpeg_scan_bound ("cap too small"); ws_bytes too small.
  *    TT_EUNSUPPORTED: as for tt_jpeg_coeffs.  Both entry points refuse before the first HIP call; no allocation, no synchronisation.
  * 8. File (export.py): SOI; APP0 JFIF 1.01, units 0, density 1 x 1; one DQT marker per table (8-bit, zig-zag order); SOF0 (sampling
- *    2 x 2 for Y in 4:2:0, else 1 x 1); one DHT marker per table; SOS; the scan; EOI. */
+ *    2 x 2 for Y in 4:2:0, else 1 x 1); one DHT marker per table; with a restart interval DRI (FF DD 00 04 Ri); SOS; the scan; EOI. */
 #define TT_JPEG_444 0
 #define TT_JPEG_420 2
 #define TT_JPEG_TABLE_WORDS 256
@@ -1139,6 +1155,14 @@ int tt_jpeg_coeffs(const void* frames, int32_t n, int32_t h, int32_t w, int32_t 
                    uint32_t* counts /* or NULL */, tt_stream_t stream);
 int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables,
                  int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream);
+/* rule 6a: restart intervals (additive; restart_interval 0 is the entry points above) */
+int64_t tt_jpeg_scan_bound_restart(int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval);
+int64_t tt_jpeg_scan_restart_ws_bytes(int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval);
+int tt_jpeg_counts_restart(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval,
+                           uint32_t* counts, tt_stream_t stream);
+int tt_jpeg_scan_restart(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval,
+                         const uint32_t* tables, int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes,
+                         tt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * JPEG import: baseline JPEG files decoded on the device to uint8 [n, h, w, ch] NHWC frames, byte for byte what libjpeg ("islow"
@@ -1147,8 +1171,8 @@ int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t
  * (tt_jpeg_entropy, tt_jpeg_pixels) and two size queries.  Integers from end to end: equality is the bound.  Additive: the ABI version
  * is unchanged.  Accepted: SOF0, 8-bit samples, one interleaved scan, one component (any sampling factor, taken as 1 x 1) or three
  * (YCbCr, sampling 1x1 / 1x1 / 1x1 or 2x2 / 1x1 / 1x1), 8-bit DQT, up to two DC and two AC Huffman tables, any component -> table map;
- * APPn and COM segments are skipped.  Not here: progressive, arithmetic and 12-bit files, restart markers, several scans, 4:2:2, CMYK /
- * Adobe files, EXIF orientation (not applied).  Coefficients whose inverse DCT leaves 0 .. 255 clamp to 0 / 255; libjpeg's range-limit
+ * APPn and COM segments are skipped; restart intervals through tt_jpeg_parse_spans / tt_jpeg_entropy_spans (rules 1a, 4a).  Not here:
+ * progressive, arithmetic and 12-bit files, several scans, 4:2:2, CMYK / Adobe files, EXIF orientation (not applied).  Coefficients whose inverse DCT leaves 0 .. 255 clamp to 0 / 255; libjpeg's range-limit
  * table wraps there, so such crafted files are not held to it.
  *
  * 1. Parse -- tt_jpeg_parse (host): one file -> TtJpegHeader: the geometry, the subsampling, the byte range of the entropy-coded
@@ -1159,6 +1183,14 @@ int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t
  *    12-bit samples; a non-zero DRI ("restart"); a second SOS ("several scans"); sampling other than the above ("sampling"); 16-bit
  *    DQT; four components or an Adobe APP14 segment; a table a component names but no DQT / DHT defines ("missing"); a Huffman table
  *    index above 1; a scan that does not hold every component in order or has Ss / Se / Ah / Al other than 0 / 63 / 0 / 0.
+ * 1a. Parse with restart intervals -- tt_jpeg_parse_spans (host): accepts what tt_jpeg_parse accepts, plus DRI segments (the last one
+ *    counts) and the RSTn markers inside the scan; tt_jpeg_parse itself keeps refusing both.  -> the header (scan_offset / scan_bytes:
+ *    the whole entropy-coded segment, markers included), *restart_interval = Ri (0: none) and the scan's SPANS: per interval its byte
+ *    offset in the file and its stuffed length, markers excluded; *nspans = markers + 1.  span_offsets / span_lengths NULL (both): only
+ *    the count is taken; else span_cap >= *nspans entries are filled.  A file without DRI (or with DRI 0) gives ONE span, equal to
+ *    tt_jpeg_parse's scan range.  Rule 1's refusals come with rule 1's texts, "tt_jpeg_parse: ..." included.  TT_EINVAL, each by name: a marker RSTm where RST(k mod 8) is due for the k-th ("is due"); a marker
+ *    count other than ceil(MCUs / Ri) - 1 ("restart markers where"); a marker in a file with no DRI segment or with DRI 0 ("in a file");
+ *    two DRI segments that disagree ("disagree"); span_cap too small; null restart_interval / nspans.
  * 2. Decode tables -- tt_jpeg_decode_table (host): BITS / HUFFVAL -> TT_JPEG_DECODE_WORDS = 256 uint32 the kernel reads: words 0 ..
  *    127: 256 uint16 indexed by the next 8 bits, length << 8 | symbol for a code of at most 8 bits, else 0; words 128 + l, l = 1 .. 16:
  *    the largest code of length l as int32, -1 for none (T.81 F.2.2.3 MAXCODE); words 145 + l: (index into HUFFVAL of the first code of
@@ -1193,6 +1225,19 @@ int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t
  *    TT_EINVAL: null pointer; n, h, w, max_bytes or scans_bytes <= 0; ch not 1 or 3; subsampling not 0 or 2; ntables not 1 or n;
  *    tables, coeffs or ws off a 16-byte boundary; offsets off 8, lengths or status off 4; ws_bytes too small.  TT_EUNSUPPORTED: as
  *    tt_jpeg_coeffs; max_bytes of 2^28 or more.
+ * 4a. Spans -- tt_jpeg_entropy_spans (device): rules 3 and 4 per SPAN instead of per frame.  Behind a restart marker the stream is at a
+ *    byte, block 0 of an MCU begins and the DC predictors are zero: every span starts from the true state (0, 0, 0) and needs nobody
+ *    else's result.  ONE workgroup per span: a clip of F frames with one interval per MCU row runs F x (MCU rows) workgroups where
+ *    tt_jpeg_entropy runs F.  Span s is offsets[s] / lengths[s] of scans, belongs to frame span_frame[s] (int32) and holds
+ *    span_blocks[s] blocks from block span_first[s] of that frame (uint32; all device arrays of nspans entries); max_bytes >= every
+ *    span's length; ws: tt_jpeg_entropy_ws_bytes(nspans, max_bytes).  The span's values go to its blocks of the frame's coeffs, guarded
+ *    by block < span_blocks[s]; the DC prefix sum restarts at every span.  status stays per FRAME [n]: a span whose block count is wrong
+ *    sets its frame's TT_JPEG_STATUS_BLOCKS, one whose tail is wrong TT_JPEG_STATUS_TAIL, and so on; a span whose frame, first block or
+ *    count lies outside its frame is taken as empty and sets TT_JPEG_STATUS_SPAN (its frame index is clamped into 0 .. n - 1).  Every
+ *    property of rule 4 stays: no workgroup waits on another, every loop's bound is computed before it, lanes write nothing until the
+ *    states are final, every index is masked or guarded.  tt_jpeg_entropy IS the case "one span per frame, whole": the same kernels.
+ *    nspans <= TT_JPEG_MAX_SPANS = 65535 (a grid dimension): more is TT_EUNSUPPORTED ("spans"), refused before any HIP call.
+ *    TT_EINVAL as tt_jpeg_entropy, and null or misaligned span arrays, nspans <= 0.
  * 5. Reconstruct -- tt_jpeg_pixels (device), one launch: per block coef x Q, then jidctint: columns first, then rows, 32-bit integers.
  *    Even part: z1 = (in2 + in6) 4433, tmp2 = z1 - in6 15137, tmp3 = z1 + in2 6270, tmp0 = (in0 + in4) << 13, tmp1 = (in0 - in4) << 13;
  *    odd part: the multipliers 2446 16819 25172 12299 7373 20995 16069 3196 9633 of the export's rule 4 in jidctint's order; descale
@@ -1215,6 +1260,7 @@ int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t
 #define TT_JPEG_STATUS_BLOCKS 4u
 #define TT_JPEG_STATUS_TAIL 8u
 #define TT_JPEG_STATUS_SPAN 16u
+#define TT_JPEG_MAX_SPANS 65535
 typedef struct {
   int32_t h, w, ch, subsampling;
   int64_t scan_offset, scan_bytes;
@@ -1232,6 +1278,14 @@ int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const int64_t* of
                     uint32_t* status, void* ws, int64_t ws_bytes, tt_stream_t stream);
 int tt_jpeg_pixels(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint8_t* quant,
                    int32_t ntables, void* frames, tt_stream_t stream);
+/* rules 1a and 4a: restart intervals (additive) */
+int tt_jpeg_parse_spans(const uint8_t* data /* host */, int64_t size, TtJpegHeader* header /* host */, int32_t* restart_interval /* host */,
+                        int64_t* span_offsets /* host [span_cap] or NULL */, int64_t* span_lengths /* host [span_cap] or NULL */, int64_t span_cap,
+                        int64_t* nspans /* host */);
+int tt_jpeg_entropy_spans(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, const int32_t* span_frame,
+                          const uint32_t* span_first, const uint32_t* span_blocks, int64_t max_bytes, int32_t nspans, int32_t n, int32_t h, int32_t w,
+                          int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs, uint32_t* status, void* ws,
+                          int64_t ws_bytes, tt_stream_t stream);
 
 #ifdef __cplusplus
 }

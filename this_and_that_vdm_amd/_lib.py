@@ -109,6 +109,7 @@ TT_GIF_LZW_STATUS = {1: "an index that does not fit min_code_size", 2: "a min_co
 TT_PNG_STRIPE, TT_PNG_SYMS, TT_PNG_RECORD_WORDS, TT_PNG_TABLE_WORDS, TT_PNG_HEADER_WORDS = 32768, 286, 288, 288, 72
 TT_JPEG_444, TT_JPEG_420, TT_JPEG_TABLE_WORDS, TT_JPEG_COUNT_WORDS = 0, 2, 256, 1024
 TT_JPEG_CHUNK, TT_JPEG_DECODE_WORDS, TT_JPEG_DECODE_SET_WORDS = 4096, 256, 1028
+TT_JPEG_MAX_SPANS = 65535
 TT_JPEG_STATUS = {1: "a marker inside the scan", 2: "an invalid Huffman code", 4: "the wrong number of blocks", 8: "bits left over behind the last block",
                   16: "a scan outside the buffer"}
 
@@ -232,6 +233,11 @@ SIGNATURES = {
     "tt_jpeg_optimized_table": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp]),
     "tt_jpeg_coeffs": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "tt_jpeg_scan": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    # ... with restart intervals (additive as well)
+    "tt_jpeg_scan_bound_restart": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "tt_jpeg_scan_restart_ws_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "tt_jpeg_counts_restart": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "tt_jpeg_scan_restart": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     # the JPEG import: header and decode tables on the host, unstuffing, entropy decode and reconstruction on the device (additive as well)
     "tt_jpeg_parse": (C.c_int, [_vp, _i64, C.POINTER(TtJpegHeader)]),
     "tt_jpeg_decode_table": (C.c_int, [_vp, _vp, _vp]),
@@ -239,6 +245,9 @@ SIGNATURES = {
     "tt_jpeg_entropy_ws_bytes": (_i64, [_i32, _i64]),
     "tt_jpeg_entropy": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "tt_jpeg_pixels": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp]),
+    # ... with restart intervals: the scan's spans on the host, one workgroup per span on the device (additive as well)
+    "tt_jpeg_parse_spans": (C.c_int, [_vp, _i64, C.POINTER(TtJpegHeader), C.POINTER(C.c_int32), _vp, _vp, _i64, C.POINTER(C.c_int64)]),
+    "tt_jpeg_entropy_spans": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // libttvdm: the device half of the JPEG export (include/ttvdm.h): tt_jpeg_coeffs -- colour conversion, 4:2:0 cell sums, the 8 x 8 integer
 // DCT, the quantiser and the zig-zag of every block of uint8 NHWC frames, in scan order, with the frames' symbol counts -- and
-// tt_jpeg_scan -- the Huffman-coded, byte-stuffed scan of every frame from those coefficients and a code table.
+// tt_jpeg_scan -- the Huffman-coded, byte-stuffed scan of every frame from those coefficients and a code table; tt_jpeg_scan_restart and
+// tt_jpeg_counts_restart -- the same with restart intervals (rule 6a), of which tt_jpeg_scan is the interval 0.
 // Integer arithmetic only; atomics are integer adds and ORs, which commute: every call gives the same bytes.
 #include "common.h"
 #include "block_scan.h"
@@ -174,12 +175,14 @@ template <bool SUB> __global__ __launch_bounds__(CBLOCK) void jpeg_coeffs_kernel
 }
 
 // ---------------------------------------------------------------- rule 6: a block's symbols
-// which component block b of a frame's scan belongs to (0 Y, else chroma), and the block whose DC it is coded against (-1: none)
-__device__ __forceinline__ void block_place(long long b, int bpm, int& chroma, long long& pred) {
+// which component block b of a frame's scan belongs to (0 Y, else chroma), and the block whose DC it is coded against (-1: none).
+// ri_blocks: the blocks of a restart interval (0: none): the first MCU of an interval is coded against no block, like the frame's first
+__device__ __forceinline__ void block_place(long long b, int bpm, long long ri_blocks, int& chroma, long long& pred) {
   const int k = (int)(b % bpm);
   chroma = bpm == 6 ? k >= 4 : k > 0;
   const long long back = bpm == 6 ? (k >= 4 ? 6 : (k == 0 ? 3 : 1)) : bpm;
-  pred = (bpm == 6 && k > 0 && k < 4) ? b - 1 : (b >= bpm ? b - back : -1);
+  const bool fresh = b < bpm || (ri_blocks > 0 && b % ri_blocks < bpm);
+  pred = (bpm == 6 && k > 0 && k < 4) ? b - 1 : (fresh ? -1 : b - back);
 }
 __device__ __forceinline__ int category(int v) { return 32 - __clz(abs(v)); }
 __device__ __forceinline__ unsigned magnitude(int v, int n) { return (unsigned)(v < 0 ? v - 1 : v) & ((1u << n) - 1u); }
@@ -211,7 +214,8 @@ template <typename F> __device__ __forceinline__ void walk_block(const short* __
 __device__ __forceinline__ int pred_of(const short* __restrict__ frame_coeffs, long long pred) { return pred < 0 ? 0 : (int)frame_coeffs[pred * 64]; }
 
 // grid (ceil(blocks / SBLOCK), n): one lane per block; the frame's counts are summed in LDS first
-__global__ __launch_bounds__(SBLOCK) void jpeg_counts_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, unsigned* __restrict__ counts) {
+__global__ __launch_bounds__(SBLOCK) void jpeg_counts_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, long long ri_blocks,
+                                                             unsigned* __restrict__ counts) {
   __shared__ unsigned cnt_s[TT_JPEG_COUNT_WORDS];
   for (int i = threadIdx.x; i < TT_JPEG_COUNT_WORDS; i += SBLOCK) cnt_s[i] = 0u;
   __syncthreads();
@@ -220,7 +224,7 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_counts_kernel(const short* __rest
   if (b < blocks) {
     int chroma;
     long long pred;
-    block_place(b, bpm, chroma, pred);
+    block_place(b, bpm, ri_blocks, chroma, pred);
     unsigned* t = cnt_s + (chroma ? 2 * TT_JPEG_TABLE_WORDS : 0);
     walk_block(fc + b * 64, pred_of(fc, pred), [&](int ac, int sym, unsigned, int) { atomicAdd(&t[ac * TT_JPEG_TABLE_WORDS + (sym & 0xff)], 1u); });
   }
@@ -243,8 +247,8 @@ __device__ __forceinline__ void code_of(const unsigned* t, int ac, int sym, unsi
 }
 
 // the bits of every block: grid as jpeg_counts_kernel
-__global__ __launch_bounds__(SBLOCK) void jpeg_bits_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, const unsigned* __restrict__ tables,
-                                                           int ntables, unsigned* __restrict__ bits) {
+__global__ __launch_bounds__(SBLOCK) void jpeg_bits_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, long long ri_blocks,
+                                                           const unsigned* __restrict__ tables, int ntables, unsigned* __restrict__ bits) {
   __shared__ unsigned tab_s[TT_JPEG_COUNT_WORDS];
   load_tables(tab_s, tables, ntables);
   const long long b = (long long)blockIdx.x * SBLOCK + threadIdx.x;
@@ -252,7 +256,7 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_bits_kernel(const short* __restri
   const short* __restrict__ fc = coeffs + (long long)blockIdx.y * blocks * 64;
   int chroma;
   long long pred;
-  block_place(b, bpm, chroma, pred);
+  block_place(b, bpm, ri_blocks, chroma, pred);
   const unsigned* t = tab_s + (chroma ? 2 * TT_JPEG_TABLE_WORDS : 0);
   unsigned total = 0u;
   walk_block(fc + b * 64, pred_of(fc, pred), [&](int ac, int sym, unsigned, int n) {
@@ -265,10 +269,28 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_bits_kernel(const short* __restri
 }
 
 // grid (n): the blocks' bit offsets inside their frame, and the frame's unstuffed bytes
-__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_offsets_kernel(unsigned* __restrict__ bits, long long blocks, unsigned* __restrict__ plain_bytes) {
+// With restart intervals of ri_blocks blocks (0: none) every interval but the last is filled to a whole byte and followed by a marker of
+// 16 bits: extra[i] gets the bits that adds before interval i, so block b of interval i starts at bit bits[b] + extra[i].
+__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_offsets_kernel(unsigned* __restrict__ bits, long long blocks, unsigned* __restrict__ plain_bytes,
+                                                                  long long ri_blocks, long long intervals, unsigned* __restrict__ extra) {
   __shared__ unsigned red_s[SCAN_WAVES + 1];
-  const unsigned total = scan_in_place<SCAN_WAVES>(bits + (long long)blockIdx.x * blocks, blocks, red_s);
-  if (threadIdx.x == 0) plain_bytes[blockIdx.x] = (total + 7u) >> 3;
+  unsigned* __restrict__ fb = bits + (long long)blockIdx.x * blocks;
+  const unsigned total = scan_in_place<SCAN_WAVES>(fb, blocks, red_s);
+  unsigned carry = 0u;
+  if (ri_blocks > 0) {                                               // uniform; scan_in_place ended on a barrier: fb is final
+    unsigned* __restrict__ fx = extra + (long long)blockIdx.x * intervals;
+    for (long long at = 0; at < intervals; at += SCAN_BLOCK) {
+      const long long i = at + threadIdx.x;
+      unsigned mine = 0u;
+      if (i < intervals - 1 && (i + 1) * ri_blocks < blocks) mine =((0u - (fb[(i + 1) * ri_blocks] - fb[i * ri_blocks])) & 7u) + 16u;       // (i + 1) ri_blocks < blocks
+      unsigned all;
+      const unsigned before = carry + block_scan_excl<SCAN_WAVES>(mine, red_s, all);
+      if (i < intervals) fx[i] = before;
+      carry += all;
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) plain_bytes[blockIdx.x] = (total + carry + 7u) >> 3;
 }
 
 // the bits themselves, MSB first, into 32-bit words whose most significant byte is the stream's first: one lane per block.  A lane's
@@ -298,8 +320,13 @@ struct BitWriter {
   }
 };
 
-__global__ __launch_bounds__(SBLOCK) void jpeg_emit_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, const unsigned* __restrict__ tables,
-                                                           int ntables, const unsigned* __restrict__ offsets, unsigned* __restrict__ plain, long long plain_stride) {
+// With restart intervals (ri_blocks > 0) the lane of an interval's last block fills the byte with one-bits like the frame's last lane, writes
+// the marker FF D0 + (interval mod 8) behind it unless the frame ends there, and sets the bit of the marker's FF byte in the frame's
+// bitmap `marks` (zeroed before): the stuffing passes tell it from a data FF by that position, never by its value.
+__global__ __launch_bounds__(SBLOCK) void jpeg_emit_kernel(const short* __restrict__ coeffs, long long blocks, int bpm, long long ri_blocks,
+                                                           const unsigned* __restrict__ tables, int ntables, const unsigned* __restrict__ offsets,
+                                                           const unsigned* __restrict__ extra, long long intervals, unsigned* __restrict__ plain,
+                                                           long long plain_stride, unsigned* __restrict__ marks, long long mark_words) {
   __shared__ unsigned tab_s[TT_JPEG_COUNT_WORDS];
   load_tables(tab_s, tables, ntables);
   const long long b = (long long)blockIdx.x * SBLOCK + threadIdx.x;
@@ -307,9 +334,10 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_emit_kernel(const short* __restri
   const short* __restrict__ fc = coeffs + (long long)blockIdx.y * blocks * 64;
   int chroma;
   long long pred;
-  block_place(b, bpm, chroma, pred);
+  block_place(b, bpm, ri_blocks, chroma, pred);
   const unsigned* t = tab_s + (chroma ? 2 * TT_JPEG_TABLE_WORDS : 0);
-  const unsigned at = offsets[(long long)blockIdx.y * blocks + b];
+  const long long interval = ri_blocks > 0 ? min(b / ri_blocks, intervals - 1) : 0;
+  const unsigned at = offsets[(long long)blockIdx.y * blocks + b] + (ri_blocks > 0 ? extra[(long long)blockIdx.y * intervals + interval] : 0u);
   BitWriter bw{plain + (long long)blockIdx.y * (plain_stride / 4), plain_stride / 4, 0ull, (int)(at & 31u), (long long)(at >> 5), true};
   unsigned pos = at;
   walk_block(fc + b * 64, pred_of(fc, pred), [&](int ac, int sym, unsigned mag, int n) {
@@ -320,9 +348,16 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_emit_kernel(const short* __restri
     bw.put((code << n) | (mag & ((1u << n) - 1u)), len + n);
     pos += (unsigned)(len + n);
   });
-  if (b == blocks - 1 && (pos & 7u)) {                               // the frame's last byte is filled with one-bits
+  const bool closes = ri_blocks > 0 && b != blocks - 1 && (b + 1) % ri_blocks == 0;
+  if ((b == blocks - 1 || closes) && (pos & 7u)) {                   // the frame's (the interval's) last byte is filled with one-bits
     const int pad = 8 - (int)(pos & 7u);
     bw.put((1u << pad) - 1u, pad);
+    pos += (unsigned)pad;
+  }
+  if (closes) {
+    bw.put(0xffd0u + (unsigned)(interval & 7), 16);
+    const long long byte = (long long)(pos >> 3);
+    if (byte < plain_stride && (byte >> 5) < mark_words) atomicOr(&marks[(long long)blockIdx.y * mark_words + (byte >> 5)], 1u << (byte & 31));
   }
   bw.flush();
 }
@@ -341,18 +376,25 @@ __device__ __forceinline__ void chunk_bytes(const unsigned* __restrict__ plain, 
   }
 }
 __device__ __forceinline__ unsigned byte_at(const unsigned by[4], int j) { return (by[j >> 2] >> (24 - 8 * (j & 3))) & 0xffu; }
+// bit j: byte j of the lane's 16 is a restart marker's FF and is not stuffed (marks NULL: no restart intervals, none is)
+__device__ __forceinline__ unsigned chunk_marks(const unsigned* __restrict__ marks, long long mark_words, long long at, int have) {
+  if (!marks || have <= 0 || (at >> 5) >= mark_words) return 0u;
+  return (marks[(long long)blockIdx.y * mark_words + (at >> 5)] >> (at & 16)) & 0xffffu;
+}
 
 // grid (chunks, n)
 __global__ __launch_bounds__(SBLOCK) void jpeg_ff_count_kernel(const unsigned* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
-                                                               unsigned* __restrict__ chunk_ff, int chunks) {
+                                                               unsigned* __restrict__ chunk_ff, int chunks, const unsigned* __restrict__ marks,
+                                                               long long mark_words) {
   __shared__ unsigned red_s[SBLOCK / 64];
   unsigned by[4];
   int have;
   long long at;
   chunk_bytes(plain, plain_stride, plain_bytes, by, have, at);
+  const unsigned mk = chunk_marks(marks, mark_words, at, have);
   unsigned ff = 0u;
 #pragma unroll
-  for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu;
+  for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu && !((mk >> j) & 1u);
   const unsigned all = block_sum<SBLOCK / 64>(ff, red_s);
   if (threadIdx.x == 0) chunk_ff[(long long)blockIdx.y * chunks + blockIdx.x] = all;
 }
@@ -367,15 +409,17 @@ __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_ff_scan_kernel(unsigned* __re
 
 // grid (chunks, n)
 __global__ __launch_bounds__(SBLOCK) void jpeg_stuff_kernel(const unsigned* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
-                                                            const unsigned* __restrict__ chunk_ff, int chunks, unsigned char* __restrict__ out, long long stride) {
+                                                            const unsigned* __restrict__ chunk_ff, int chunks, unsigned char* __restrict__ out, long long stride,
+                                                            const unsigned* __restrict__ marks, long long mark_words) {
   __shared__ unsigned red_s[SBLOCK / 64];
   unsigned by[4];
   int have;
   long long at;
   chunk_bytes(plain, plain_stride, plain_bytes, by, have, at);
+  const unsigned mk = chunk_marks(marks, mark_words, at, have);
   unsigned ff = 0u;
 #pragma unroll
-  for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu;
+  for (int j = 0; j < 16; ++j) ff += j < have && byte_at(by, j) == 0xffu && !((mk >> j) & 1u);
   unsigned all;
   const unsigned before = block_scan_excl<SBLOCK / 64>(ff, red_s, all);
   long long pos = at + chunk_ff[(long long)blockIdx.y * chunks + blockIdx.x] + before;
@@ -386,7 +430,7 @@ __global__ __launch_bounds__(SBLOCK) void jpeg_stuff_kernel(const unsigned* __re
       const unsigned v = byte_at(by, j);
       if (pos < stride) dst[pos] = (unsigned char)v;
       ++pos;
-      if (v == 0xffu) {
+      if (v == 0xffu && !((mk >> j) & 1u)) {
         if (pos < stride) dst[pos] = 0;
         ++pos;
       }
@@ -421,30 +465,51 @@ extern "C" int tt_jpeg_coeffs(const void* frames, int32_t n, int32_t h, int32_t 
     const hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * TT_JPEG_COUNT_WORDS * sizeof(uint32_t), (hipStream_t)stream);
     if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "tt_jpeg_coeffs: zeroing counts: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(jpeg_counts_kernel, dim3((unsigned)((blocks + SBLOCK - 1) / SBLOCK), (unsigned)n), dim3(SBLOCK), 0, (hipStream_t)stream,
-                       (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, (unsigned*)counts);
+                       (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, 0ll, (unsigned*)counts);
   }
   TT_CHECK_LAUNCH("tt_jpeg_coeffs");
   return TT_OK;
 }
 
-extern "C" int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables,
-                            int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream) {
-  if (!coeffs || !tables || !out || !lengths || !ws)
-    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: null %s", !coeffs ? "coeffs" : (!tables ? "tables" : (!out ? "out" : (!lengths ? "lengths" : "ws"))));
-  const int rc = tt_jpeg_refuse_shape("tt_jpeg_scan", n, h, w, ch, subsampling, "; JPEG has no alpha");
+extern "C" int tt_jpeg_counts_restart(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval,
+                                      uint32_t* counts, tt_stream_t stream) {
+  if (!coeffs || !counts) TT_FAIL(TT_EINVAL, "tt_jpeg_counts_restart: null %s", !coeffs ? "coeffs" : "counts");
+  const int rc = tt_jpeg_refuse_shape("tt_jpeg_counts_restart", n, h, w, ch, subsampling, "; JPEG has no alpha");
   if (rc != TT_OK) return rc;
-  if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ntables = %d (1, or one set per frame: %d)", ntables, n);
-  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: coeffs is not 16-byte aligned");
-  if ((uintptr_t)tables & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: tables is not 16-byte aligned");
-  if ((uintptr_t)out & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: out is not 16-byte aligned");
-  if ((uintptr_t)lengths & 3) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: lengths is not 4-byte aligned");
-  if ((uintptr_t)ws & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ws is not 16-byte aligned");
-  const long long stride = tt_jpeg_scan_bound(h, w, ch, subsampling);
+  if (restart_interval < 0 || restart_interval > 65535) TT_FAIL(TT_EINVAL, "tt_jpeg_counts_restart: restart_interval = %d (0: none, to 65535 MCUs)", restart_interval);
+  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_counts_restart: coeffs is not 16-byte aligned");
+  if ((uintptr_t)counts & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_counts_restart: counts is not 16-byte aligned");
+  const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
+  const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
+  const hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * TT_JPEG_COUNT_WORDS * sizeof(uint32_t), (hipStream_t)stream);
+  if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "tt_jpeg_counts_restart: zeroing counts: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(jpeg_counts_kernel, dim3((unsigned)((blocks + SBLOCK - 1) / SBLOCK), (unsigned)n), dim3(SBLOCK), 0, (hipStream_t)stream, (const short*)coeffs,
+                     blocks, (int)geo.blocks_per_mcu, (long long)restart_interval * geo.blocks_per_mcu, (unsigned*)counts);
+  TT_CHECK_LAUNCH("tt_jpeg_counts_restart");
+  return TT_OK;
+}
+
+// tt_jpeg_scan is the restart interval 0 of tt_jpeg_scan_restart: the same kernels, with no interval to close and no bitmap to read
+static int scan_frames(const char* who, const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t ri,
+                       const uint32_t* tables, int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  if (!coeffs || !tables || !out || !lengths || !ws)
+    TT_FAIL(TT_EINVAL, "%s: null %s", who, !coeffs ? "coeffs" : (!tables ? "tables" : (!out ? "out" : (!lengths ? "lengths" : "ws"))));
+  const int rc = tt_jpeg_refuse_shape(who, n, h, w, ch, subsampling, "; JPEG has no alpha");
+  if (rc != TT_OK) return rc;
+  if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "%s: ntables = %d (1, or one set per frame: %d)", who, ntables, n);
+  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "%s: coeffs is not 16-byte aligned", who);
+  if ((uintptr_t)tables & 15) TT_FAIL(TT_EINVAL, "%s: tables is not 16-byte aligned", who);
+  if ((uintptr_t)out & 15) TT_FAIL(TT_EINVAL, "%s: out is not 16-byte aligned", who);
+  if ((uintptr_t)lengths & 3) TT_FAIL(TT_EINVAL, "%s: lengths is not 4-byte aligned", who);
+  if ((uintptr_t)ws & 15) TT_FAIL(TT_EINVAL, "%s: ws is not 16-byte aligned", who);
+  if (ri < 0 || ri > 65535) TT_FAIL(TT_EINVAL, "%s: restart_interval = %d (0: none, to 65535 MCUs)", who, ri);
+  const long long stride = tt_jpeg_scan_bound_restart(h, w, ch, subsampling, ri);
+  if (stride >= (1ll << 31)) TT_FAIL(TT_EUNSUPPORTED, "%s: a scan bound of %lld bytes per frame (below 2^31)", who, stride);
   if (cap < (long long)n * stride)
-    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: cap too small: %lld bytes, %d frames at tt_jpeg_scan_bound = %lld take %lld", (long long)cap, n, stride, (long long)n * stride);
-  const TtJpegScanWs lay(n, h, w, ch, subsampling);
+    TT_FAIL(TT_EINVAL, "%s: cap too small: %lld bytes, %d frames at the scan bound = %lld take %lld", who, (long long)cap, n, stride, (long long)n * stride);
+  const TtJpegScanWs lay(n, h, w, ch, subsampling, ri);
   if (ws_bytes < lay.total)
-    TT_FAIL(TT_EINVAL, "tt_jpeg_scan: ws too small: %lld bytes, tt_jpeg_scan_ws_bytes = %lld", (long long)ws_bytes, (long long)lay.total);
+    TT_FAIL(TT_EINVAL, "%s: ws too small: %lld bytes, the size query gives %lld", who, (long long)ws_bytes, (long long)lay.total);
   const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
   const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
   const long long plain_stride = lay.plain_stride;
@@ -453,19 +518,34 @@ extern "C" int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t
   unsigned* plain_bytes = (unsigned*)((char*)ws + lay.plain_bytes);
   unsigned* chunk_ff = (unsigned*)((char*)ws + lay.chunk_ff);
   unsigned* plain = (unsigned*)((char*)ws + lay.plain);
+  unsigned* extra = ri ? (unsigned*)((char*)ws + lay.extra) : nullptr;
+  unsigned* marks = ri ? (unsigned*)((char*)ws + lay.marks) : nullptr;
+  const long long ri_blocks = (long long)ri * geo.blocks_per_mcu, intervals = lay.intervals, mark_words = lay.mark_words;
   const hipStream_t s = (hipStream_t)stream;
   const dim3 per_block((unsigned)((blocks + SBLOCK - 1) / SBLOCK), (unsigned)n), per_chunk((unsigned)chunks, (unsigned)n);
-  const hipError_t e = hipMemsetAsync(plain, 0, (size_t)(n * plain_stride), s);
-  if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "tt_jpeg_scan: zeroing ws: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(jpeg_bits_kernel, per_block, dim3(SBLOCK), 0, s, (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, (const unsigned*)tables,
-                     (int)ntables, bits);
-  hipLaunchKernelGGL(jpeg_offsets_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, bits, blocks, plain_bytes);
-  hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(SBLOCK), 0, s, (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, (const unsigned*)tables,
-                     (int)ntables, (const unsigned*)bits, plain, plain_stride);
-  hipLaunchKernelGGL(jpeg_ff_count_kernel, per_chunk, dim3(SBLOCK), 0, s, (const unsigned*)plain, plain_stride, (const unsigned*)plain_bytes, chunk_ff, chunks);
+  hipError_t e = hipMemsetAsync(plain, 0, (size_t)(n * plain_stride), s);
+  if (e == hipSuccess && ri) e = hipMemsetAsync(marks, 0, (size_t)(n * mark_words) * sizeof(unsigned), s);
+  if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "%s: zeroing ws: %s", who, hipGetErrorString(e));
+  hipLaunchKernelGGL(jpeg_bits_kernel, per_block, dim3(SBLOCK), 0, s, (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, ri_blocks,
+                     (const unsigned*)tables, (int)ntables, bits);
+  hipLaunchKernelGGL(jpeg_offsets_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, bits, blocks, plain_bytes, ri_blocks, intervals, extra);
+  hipLaunchKernelGGL(jpeg_emit_kernel, per_block, dim3(SBLOCK), 0, s, (const short*)coeffs, blocks, (int)geo.blocks_per_mcu, ri_blocks,
+                     (const unsigned*)tables, (int)ntables, (const unsigned*)bits, (const unsigned*)extra, intervals, plain, plain_stride, marks, mark_words);
+  hipLaunchKernelGGL(jpeg_ff_count_kernel, per_chunk, dim3(SBLOCK), 0, s, (const unsigned*)plain, plain_stride, (const unsigned*)plain_bytes, chunk_ff, chunks, (const unsigned*)marks, mark_words);
   hipLaunchKernelGGL(jpeg_ff_scan_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, chunk_ff, chunks, (const unsigned*)plain_bytes, (unsigned*)lengths);
   hipLaunchKernelGGL(jpeg_stuff_kernel, per_chunk, dim3(SBLOCK), 0, s, (const unsigned*)plain, plain_stride, (const unsigned*)plain_bytes,
-                     (const unsigned*)chunk_ff, chunks, (unsigned char*)out, stride);
-  TT_CHECK_LAUNCH("tt_jpeg_scan");
+                     (const unsigned*)chunk_ff, chunks, (unsigned char*)out, stride, (const unsigned*)marks, mark_words);
+  TT_CHECK_LAUNCH(who);
   return TT_OK;
+}
+
+extern "C" int tt_jpeg_scan(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables,
+                            int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  return scan_frames("tt_jpeg_scan", coeffs, n, h, w, ch, subsampling, 0, tables, ntables, out, cap, lengths, ws, ws_bytes, stream);
+}
+
+extern "C" int tt_jpeg_scan_restart(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval,
+                                    const uint32_t* tables, int32_t ntables, uint8_t* out, int64_t cap, uint32_t* lengths, void* ws, int64_t ws_bytes,
+                                    tt_stream_t stream) {
+  return scan_frames("tt_jpeg_scan_restart", coeffs, n, h, w, ch, subsampling, restart_interval, tables, ntables, out, cap, lengths, ws, ws_bytes, stream);
 }

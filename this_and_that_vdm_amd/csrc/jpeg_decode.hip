@@ -1,5 +1,6 @@
 // libttvdm: the device half of the JPEG import (include/ttvdm.h, "JPEG import"): tt_jpeg_entropy -- byte unstuffing, the
-// self-synchronising Huffman decode of every frame's scan into tt_jpeg_coeffs' coefficient layout, the DC prefix sums -- and
+// self-synchronising Huffman decode of every frame's scan into tt_jpeg_coeffs' coefficient layout, the DC prefix sums --,
+// tt_jpeg_entropy_spans -- the same per span between restart markers (rule 4a), of which tt_jpeg_entropy is "one span a frame" -- and
 // tt_jpeg_pixels -- dequantiser, the jidctint inverse DCT, fancy 4:2:0 chroma upsampling and the colour conversion in one launch.
 // Integer arithmetic only; the one atomic is an OR into a frame's status word: every call gives the same bytes.
 #include "common.h"
@@ -35,6 +36,19 @@ __device__ __forceinline__ const unsigned char* frame_span(const unsigned char* 
   return scans + span_of(scans_bytes, offsets, lengths, max_bytes, f, len, bad);
 }
 
+// Items.  tt_jpeg_entropy's items are frames; tt_jpeg_entropy_spans' are the spans between restart markers, each with its frame, its
+// first block there and its block count (device arrays).  A span whose place is not inside its frame is taken as empty (`bad`), and its
+// frame index is held inside the call's frames.  span_frame NULL: item i is frame i, whole.
+struct ItemPlace { int frame; unsigned first, count; bool bad; };
+__device__ __forceinline__ ItemPlace item_place(const int* __restrict__ span_frame, const unsigned* __restrict__ span_first, const unsigned* __restrict__ span_blocks,
+                                                int item, int nframes, unsigned blocks) {
+  if (!span_frame) return {item, 0u, blocks, false};
+  const int f = span_frame[item];
+  const unsigned first = span_first[item], count = span_blocks[item];
+  const bool bad = f < 0 || f >= nframes || first > blocks || count > blocks - first;
+  return {min(max(f, 0), nframes - 1), bad ? 0u : first, bad ? 0u : count, bad};
+}
+
 // the chunk's bytes (and the one before them) into LDS, then per lane: the 0x00 bytes behind an 0xFF among its 16, as a bit mask
 __device__ __forceinline__ unsigned chunk_drops(const unsigned char* __restrict__ src, unsigned len, unsigned char* raw_s, bool& marker) {
   const unsigned c0 = blockIdx.x * (unsigned)CHUNK;
@@ -60,7 +74,7 @@ __device__ __forceinline__ unsigned chunk_drops(const unsigned char* __restrict_
 // grid (chunks, n)
 __global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_count_kernel(const unsigned char* __restrict__ scans, long long scans_bytes, const long long* __restrict__ offsets,
                                                                    const unsigned* __restrict__ lengths, long long max_bytes, unsigned* __restrict__ chunk_drop,
-                                                                   int chunks, unsigned* __restrict__ status) {
+                                                                   int chunks, unsigned* __restrict__ status, const int* __restrict__ span_frame, int nframes) {
   __shared__ unsigned char raw_s[CHUNK + 16];
   __shared__ unsigned red_s[UBLOCK / 64];
   unsigned len;
@@ -68,7 +82,7 @@ __global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_count_kernel(const unsign
   const unsigned char* src = frame_span(scans, scans_bytes, offsets, lengths, max_bytes, blockIdx.y, len, bad);
   const unsigned drops = __popc(chunk_drops(src, len, raw_s, marker));
   const unsigned flags = (marker ? TT_JPEG_STATUS_MARKER : 0u) | ((bad && blockIdx.x == 0 && threadIdx.x == 0) ? TT_JPEG_STATUS_SPAN : 0u);
-  if (flags) atomicOr(&status[blockIdx.y], flags);
+  if (flags) atomicOr(&status[span_frame ? min(max(span_frame[blockIdx.y], 0), nframes - 1) : (int)blockIdx.y], flags);
   const unsigned all = block_sum<UBLOCK / 64>(drops, red_s);
   if (threadIdx.x == 0) chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x] = all;
 }
@@ -196,30 +210,33 @@ __device__ __forceinline__ unsigned decode_span(const unsigned* win_s, unsigned 
   return done;
 }
 
-// grid (n), ELANES lanes: ONE workgroup walks its frame's sequences in order.  Nothing another workgroup writes is read.
+// grid (items), ELANES lanes: ONE workgroup walks its item's sequences in order, from the true state (0, 0, 0): a frame's scan, or the span
+// behind a restart marker, where the stream is at a byte, an MCU begins and the DC predictors are zero.  Nothing another workgroup writes is read.
 __global__ __launch_bounds__(ELANES) void jpeg_entropy_kernel(const unsigned char* __restrict__ plain, long long plain_stride, const unsigned* __restrict__ plain_bytes,
                                                             long long max_bytes, const unsigned* __restrict__ tables, int ntables, int bpm, unsigned blocks,
-                                                            short* __restrict__ coeffs, unsigned* __restrict__ status) {
+                                                            short* __restrict__ coeffs, unsigned* __restrict__ status, const int* __restrict__ span_frame,
+                                                            const unsigned* __restrict__ span_first, const unsigned* __restrict__ span_blocks, int nframes) {
   __shared__ unsigned win_s[SEQ_WORDS + 2];
   __shared__ unsigned tab_s[TT_JPEG_DECODE_SET_WORDS];
   __shared__ unsigned ex_p[ELANES], ex_mz[ELANES];
   __shared__ unsigned red_s[EWAVES];
   const int tid = threadIdx.x;
-  const unsigned* __restrict__ tset = tables + (ntables > 1 ? (long long)blockIdx.x * TT_JPEG_DECODE_SET_WORDS : 0);
+  const ItemPlace it = item_place(span_frame, span_first, span_blocks, (int)blockIdx.x, nframes, blocks);
+  const unsigned* __restrict__ tset = tables + (ntables > 1 ? (long long)it.frame * TT_JPEG_DECODE_SET_WORDS : 0);
   for (int i = tid; i < TT_JPEG_DECODE_SET_WORDS; i += ELANES) tab_s[i] = tset[i];
   const unsigned nbytes = (unsigned)min((long long)plain_bytes[blockIdx.x], max_bytes);
   const unsigned char* __restrict__ stream = plain + (long long)blockIdx.x * plain_stride;
   const unsigned* __restrict__ words = (const unsigned*)stream;
   const long long stride_words = plain_stride / 4;
-  short* __restrict__ out = coeffs + (long long)blockIdx.x * blocks * 64;
+  short* __restrict__ out = coeffs + ((long long)it.frame * blocks + it.first) * 64;
   __syncthreads();
   DecFrame fr;
   fr.L = nbytes * 8u;                                // max_bytes < 2^28: below 2^31
   fr.map = tab_s[4 * TT_JPEG_DECODE_WORDS];
   fr.bpm = bpm;
-  fr.blocks = blocks;
+  fr.blocks = it.count;
   DecState carried = {0u, 0u};                       // the true state at the head of the sequence
-  unsigned base = 0u, err = 0u;                      // blocks completed before the sequence
+  unsigned base = 0u, err = (it.bad && tid == 0) ? TT_JPEG_STATUS_SPAN : 0u;       // blocks completed before the sequence
   const unsigned nseq = (fr.L + SEQ_BITS - 1u) / SEQ_BITS;
   for (unsigned q = 0; q < nseq; ++q) {
     const unsigned win0 = q * SEQ_BITS;
@@ -267,20 +284,23 @@ __global__ __launch_bounds__(ELANES) void jpeg_entropy_kernel(const unsigned cha
     base += all;
   }
   if (tid == 0) {
-    if (base != blocks) err |= TT_JPEG_STATUS_BLOCKS;
+    if (base != it.count) err |= TT_JPEG_STATUS_BLOCKS;
     const unsigned left = fr.L - min(carried.p, fr.L);
     const unsigned ones = left ? (1u << min(left, 8u)) - 1u : 0u;
     if (left >= 8u || (left && ((unsigned)stream[nbytes - 1] & ones) != ones)) err |= TT_JPEG_STATUS_TAIL;
   }
-  if (err) atomicOr(&status[blockIdx.x], err);
+  if (err) atomicOr(&status[it.frame], err);
 }
 
-// grid (n), SCAN_BLOCK lanes: one lane per MCU, a prefix sum per component over the DC differences (int32), stored as int16
-__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_dc_kernel(short* __restrict__ coeffs, long long blocks, int bpm) {
+// grid (items), SCAN_BLOCK lanes: one lane per MCU, a prefix sum per component over the DC differences (int32), stored as int16; it
+// starts from zero at every item: a frame, or the span behind a restart marker
+__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_dc_kernel(short* __restrict__ coeffs, long long blocks, int bpm, const int* __restrict__ span_frame,
+                                                             const unsigned* __restrict__ span_first, const unsigned* __restrict__ span_blocks, int nframes) {
   __shared__ int red_s[SCAN_WAVES];
   const int tid = threadIdx.x;
-  short* __restrict__ fc = coeffs + (long long)blockIdx.x * blocks * 64;
-  const long long mcus = blocks / bpm;
+  const ItemPlace it = item_place(span_frame, span_first, span_blocks, (int)blockIdx.x, nframes, (unsigned)blocks);
+  short* __restrict__ fc = coeffs + ((long long)it.frame * blocks + it.first) * 64;
+  const long long mcus = it.count / bpm;
   const int ncomp = bpm == 1 ? 1 : 3, ny = bpm == 6 ? 4 : 1;
   int carry[3] = {0, 0, 0};
   for (long long at = 0; at < mcus; at += SCAN_BLOCK) {
@@ -423,26 +443,28 @@ template <bool SUB> __global__ __launch_bounds__(PBLOCK) void jpeg_pixels_kernel
 
 }  // namespace
 
-extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, int64_t max_bytes, int32_t n,
-                               int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs,
-                               uint32_t* status, void* ws, int64_t ws_bytes, tt_stream_t stream) {
+// tt_jpeg_entropy (items = n frames, span_frame NULL) and tt_jpeg_entropy_spans (items = the spans of n frames) are the same launches
+static int entropy_items(const char* who, const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, const int32_t* span_frame,
+                         const uint32_t* span_first, const uint32_t* span_blocks, int64_t max_bytes, int32_t items, int32_t n, int32_t h, int32_t w, int32_t ch,
+                         int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs, uint32_t* status, void* ws, int64_t ws_bytes,
+                         tt_stream_t stream) {
   if (!scans || !offsets || !lengths || !tables || !coeffs || !status || !ws)
-    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: null %s",
+    TT_FAIL(TT_EINVAL, "%s: null %s", who,
             !scans ? "scans" : (!offsets ? "offsets" : (!lengths ? "lengths" : (!tables ? "tables" : (!coeffs ? "coeffs" : (!status ? "status" : "ws"))))));
-  const int rc = tt_jpeg_refuse_shape("tt_jpeg_entropy", n, h, w, ch, subsampling, "");
+  const int rc = tt_jpeg_refuse_shape(who, n, h, w, ch, subsampling, "");
   if (rc != TT_OK) return rc;
-  if (scans_bytes <= 0 || max_bytes <= 0) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: empty scans (scans_bytes = %lld, max_bytes = %lld)", (long long)scans_bytes, (long long)max_bytes);
-  if (max_bytes >= (1ll << 28)) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_entropy: max_bytes = %lld (a scan below 2^28 bytes)", (long long)max_bytes);
-  if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ntables = %d (1, or one set per frame: %d)", ntables, n);
-  if ((uintptr_t)offsets & 7) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: offsets is not 8-byte aligned");
-  if ((uintptr_t)lengths & 3) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: lengths is not 4-byte aligned");
-  if ((uintptr_t)tables & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: tables is not 16-byte aligned");
-  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: coeffs is not 16-byte aligned");
-  if ((uintptr_t)status & 3) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: status is not 4-byte aligned");
-  if ((uintptr_t)ws & 15) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ws is not 16-byte aligned");
-  const TtJpegEntropyWs lay(n, max_bytes);
+  if (scans_bytes <= 0 || max_bytes <= 0) TT_FAIL(TT_EINVAL, "%s: empty scans (scans_bytes = %lld, max_bytes = %lld)", who, (long long)scans_bytes, (long long)max_bytes);
+  if (max_bytes >= (1ll << 28)) TT_FAIL(TT_EUNSUPPORTED, "%s: max_bytes = %lld (a scan below 2^28 bytes)", who, (long long)max_bytes);
+  if (ntables != 1 && ntables != n) TT_FAIL(TT_EINVAL, "%s: ntables = %d (1, or one set per frame: %d)", who, ntables, n);
+  if ((uintptr_t)offsets & 7) TT_FAIL(TT_EINVAL, "%s: offsets is not 8-byte aligned", who);
+  if ((uintptr_t)lengths & 3) TT_FAIL(TT_EINVAL, "%s: lengths is not 4-byte aligned", who);
+  if ((uintptr_t)tables & 15) TT_FAIL(TT_EINVAL, "%s: tables is not 16-byte aligned", who);
+  if ((uintptr_t)coeffs & 15) TT_FAIL(TT_EINVAL, "%s: coeffs is not 16-byte aligned", who);
+  if ((uintptr_t)status & 3) TT_FAIL(TT_EINVAL, "%s: status is not 4-byte aligned", who);
+  if ((uintptr_t)ws & 15) TT_FAIL(TT_EINVAL, "%s: ws is not 16-byte aligned", who);
+  const TtJpegEntropyWs lay(items, max_bytes);
   if (ws_bytes < lay.total)
-    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy: ws too small: %lld bytes, tt_jpeg_entropy_ws_bytes = %lld", (long long)ws_bytes, (long long)lay.total);
+    TT_FAIL(TT_EINVAL, "%s: ws too small: %lld bytes, tt_jpeg_entropy_ws_bytes = %lld", who, (long long)ws_bytes, (long long)lay.total);
   const TtJpegGeometry geo = tt_jpeg_geometry(h, w, ch, subsampling);
   const long long blocks = tt_jpeg_blocks(h, w, ch, subsampling);
   const int chunks = (int)lay.chunks;
@@ -453,19 +475,42 @@ extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const 
   const hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(status, 0, sizeof(uint32_t) * (size_t)n, s);
   if (e == hipSuccess) e = hipMemsetAsync(coeffs, 0, (size_t)n * (size_t)blocks * 128, s);
-  if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "tt_jpeg_entropy: zeroing coeffs and status: %s", hipGetErrorString(e));
-  const dim3 per_chunk((unsigned)chunks, (unsigned)n);
+  if (e != hipSuccess) TT_FAIL(TT_ELAUNCH, "%s: zeroing coeffs and status: %s", who, hipGetErrorString(e));
+  const dim3 per_chunk((unsigned)chunks, (unsigned)items);
   hipLaunchKernelGGL(jpeg_unstuff_count_kernel, per_chunk, dim3(UBLOCK), 0, s, (const unsigned char*)scans, (long long)scans_bytes, (const long long*)offsets,
-                     (const unsigned*)lengths, (long long)max_bytes, chunk_drop, chunks, (unsigned*)status);
-  hipLaunchKernelGGL(jpeg_unstuff_scan_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, chunk_drop, chunks, (const long long*)offsets, (const unsigned*)lengths,
+                     (const unsigned*)lengths, (long long)max_bytes, chunk_drop, chunks, (unsigned*)status, (const int*)span_frame, (int)n);
+  hipLaunchKernelGGL(jpeg_unstuff_scan_kernel, dim3((unsigned)items), dim3(SCAN_BLOCK), 0, s, chunk_drop, chunks, (const long long*)offsets, (const unsigned*)lengths,
                      (long long)scans_bytes, (long long)max_bytes, plain_bytes);
   hipLaunchKernelGGL(jpeg_unstuff_gather_kernel, per_chunk, dim3(UBLOCK), 0, s, (const unsigned char*)scans, (long long)scans_bytes, (const long long*)offsets,
                      (const unsigned*)lengths, (long long)max_bytes, (const unsigned*)chunk_drop, chunks, plain, plain_stride);
-  hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(ELANES), 0, s, (const unsigned char*)plain, plain_stride, (const unsigned*)plain_bytes,
-                     (long long)max_bytes, (const unsigned*)tables, (int)ntables, (int)geo.blocks_per_mcu, (unsigned)blocks, (short*)coeffs, (unsigned*)status);
-  hipLaunchKernelGGL(jpeg_dc_kernel, dim3((unsigned)n), dim3(SCAN_BLOCK), 0, s, (short*)coeffs, blocks, (int)geo.blocks_per_mcu);
-  TT_CHECK_LAUNCH("tt_jpeg_entropy");
+  hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)items), dim3(ELANES), 0, s, (const unsigned char*)plain, plain_stride, (const unsigned*)plain_bytes,
+                     (long long)max_bytes, (const unsigned*)tables, (int)ntables, (int)geo.blocks_per_mcu, (unsigned)blocks, (short*)coeffs, (unsigned*)status,
+                     (const int*)span_frame, (const unsigned*)span_first, (const unsigned*)span_blocks, (int)n);
+  hipLaunchKernelGGL(jpeg_dc_kernel, dim3((unsigned)items), dim3(SCAN_BLOCK), 0, s, (short*)coeffs, blocks, (int)geo.blocks_per_mcu, (const int*)span_frame,
+                     (const unsigned*)span_first, (const unsigned*)span_blocks, (int)n);
+  TT_CHECK_LAUNCH(who);
   return TT_OK;
+}
+
+extern "C" int tt_jpeg_entropy(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, int64_t max_bytes, int32_t n,
+                               int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs,
+                               uint32_t* status, void* ws, int64_t ws_bytes, tt_stream_t stream) {
+  return entropy_items("tt_jpeg_entropy", scans, scans_bytes, offsets, lengths, nullptr, nullptr, nullptr, max_bytes, n, n, h, w, ch, subsampling, tables, ntables,
+                       coeffs, status, ws, ws_bytes, stream);
+}
+
+extern "C" int tt_jpeg_entropy_spans(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, const int32_t* span_frame,
+                                     const uint32_t* span_first, const uint32_t* span_blocks, int64_t max_bytes, int32_t nspans, int32_t n, int32_t h, int32_t w,
+                                     int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs, uint32_t* status, void* ws,
+                                     int64_t ws_bytes, tt_stream_t stream) {
+  if (!span_frame || !span_first || !span_blocks)
+    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy_spans: null %s", !span_frame ? "span_frame" : (!span_first ? "span_first" : "span_blocks"));
+  if (nspans <= 0) TT_FAIL(TT_EINVAL, "tt_jpeg_entropy_spans: nspans = %d", nspans);
+  if (nspans > TT_JPEG_MAX_SPANS) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_entropy_spans: %d spans: more than one grid covers (%d)", nspans, TT_JPEG_MAX_SPANS);
+  if (((uintptr_t)span_frame | (uintptr_t)span_first | (uintptr_t)span_blocks) & 3)
+    TT_FAIL(TT_EINVAL, "tt_jpeg_entropy_spans: span_frame, span_first or span_blocks is not 4-byte aligned");
+  return entropy_items("tt_jpeg_entropy_spans", scans, scans_bytes, offsets, lengths, span_frame, span_first, span_blocks, max_bytes, nspans, n, h, w, ch, subsampling,
+                       tables, ntables, coeffs, status, ws, ws_bytes, stream);
 }
 
 extern "C" int tt_jpeg_pixels(const int16_t* coeffs, int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, const uint8_t* quant, int32_t ntables,

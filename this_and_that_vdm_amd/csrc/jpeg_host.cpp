@@ -76,6 +76,20 @@ extern "C" int64_t tt_jpeg_scan_ws_bytes(int32_t n, int32_t h, int32_t w, int32_
   return TtJpegScanWs(n, h, w, ch, subsampling).total;
 }
 
+extern "C" int64_t tt_jpeg_scan_bound_restart(int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval) {
+  const int64_t plain = tt_jpeg_scan_bound(h, w, ch, subsampling);
+  if (!plain || restart_interval < 0 || restart_interval > 65535) return 0;
+  if (!restart_interval) return plain;
+  // per marker: the pad byte, which may be 0xFF and then doubles, and the marker's two bytes, never stuffed -- 4 bytes.  6 are taken, so
+  // that HALF the bound still holds the unstuffed stream (pad 1 + marker 2), which is what the workspace is cut by
+  return tt_jpeg_up16(plain + 6 * (tt_jpeg_intervals(h, w, ch, subsampling, restart_interval) - 1));
+}
+
+extern "C" int64_t tt_jpeg_scan_restart_ws_bytes(int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t restart_interval) {
+  if (restart_interval < 0 || restart_interval > 65535) return 0;
+  return TtJpegScanWs(n, h, w, ch, subsampling, restart_interval).total;
+}
+
 extern "C" int tt_jpeg_quant_tables(int32_t quality, uint8_t* tables) {
   if (!tables) TT_FAIL(TT_EINVAL, "tt_jpeg_quant_tables: null tables");
   if (quality < 1 || quality > 100) TT_FAIL(TT_EINVAL, "tt_jpeg_quant_tables: quality = %d (1 to 100)", quality);
@@ -142,63 +156,70 @@ const char* frame_kind(int marker) {
 
 }  // namespace
 
-extern "C" int tt_jpeg_parse(const uint8_t* data, int64_t size, TtJpegHeader* header) {
-  if (!data || !header) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: null %s", !data ? "data" : "header");
-  if (size <= 0) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: size = %lld", (long long)size);
-  if (size < 2 || data[0] != 0xff || data[1] != 0xd8) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: no SOI marker: not a JPEG file");
+// One parser behind both entry points.  ri == NULL: tt_jpeg_parse, which refuses restart intervals by name.  Else tt_jpeg_parse_spans:
+// *ri gets the interval of the last DRI segment, and the scan is walked marker by marker into spans (rule 1a of the import).
+static int parse_file(const uint8_t* data, int64_t size, TtJpegHeader* header, int32_t* ri, int64_t* span_offsets, int64_t* span_lengths,
+                      int64_t span_cap, int64_t* nspans) {
+  // rule 1's refusals carry tt_jpeg_parse's name from either entry point (callers match on them); rule 1a's carry tt_jpeg_parse_spans'
+  const char* who = "tt_jpeg_parse";
+  const char* who_spans = "tt_jpeg_parse_spans";
+  if (!data || !header) TT_FAIL(TT_EINVAL, "%s: null %s", who, !data ? "data" : "header");
+  if (size <= 0) TT_FAIL(TT_EINVAL, "%s: size = %lld", who, (long long)size);
+  if (size < 2 || data[0] != 0xff || data[1] != 0xd8) TT_FAIL(TT_EINVAL, "%s: no SOI marker: not a JPEG file", who);
   TtJpegHeader hd;
   memset(&hd, 0, sizeof(hd));
   uint8_t quant[4][64];
-  bool have_quant[4] = {false, false, false, false}, have_huff[4] = {false, false, false, false}, have_frame = false;
+  bool have_quant[4] = {false, false, false, false}, have_huff[4] = {false, false, false, false}, have_frame = false, have_dri = false;
+  int interval = 0;
   int comp_id[3] = {0, 0, 0}, comp_quant[3] = {0, 0, 0};
   int64_t at = 2;
   for (;;) {
-    if (at + 4 > size) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before its scan (a marker segment at byte %lld)", (long long)at);
-    if (data[at] != 0xff) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: byte %lld is 0x%02x where a marker begins", (long long)at, data[at]);
+    if (at + 4 > size) TT_FAIL(TT_EINVAL, "%s: the file ends before its scan (a marker segment at byte %lld)", who, (long long)at);
+    if (data[at] != 0xff) TT_FAIL(TT_EINVAL, "%s: byte %lld is 0x%02x where a marker begins", who, (long long)at, data[at]);
     const int marker = data[at + 1];
     if (marker == 0xff) { ++at; continue; }                          // fill bytes before a marker
-    if (marker == 0xd9) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before its scan (EOI at byte %lld)", (long long)at);
-    if (marker == 0x01 || (marker >= 0xd0 && marker <= 0xd8)) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: marker 0x%02x at byte %lld, before the scan", marker, (long long)at);
+    if (marker == 0xd9) TT_FAIL(TT_EINVAL, "%s: the file ends before its scan (EOI at byte %lld)", who, (long long)at);
+    if (marker == 0x01 || (marker >= 0xd0 && marker <= 0xd8)) TT_FAIL(TT_EINVAL, "%s: marker 0x%02x at byte %lld, before the scan", who, marker, (long long)at);
     const int64_t len = ((int64_t)data[at + 2] << 8) | data[at + 3];
-    if (len < 2 || at + 2 + len > size) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of segment 0x%02x at byte %lld", marker, (long long)at);
+    if (len < 2 || at + 2 + len > size) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of segment 0x%02x at byte %lld", who, marker, (long long)at);
     const uint8_t* p = data + at + 4;
     const int64_t n = len - 2;
     if (marker == 0xc0) {
-      if (have_frame) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a second frame header");
-      if (n < 6) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of its SOF0 segment");
-      if (p[0] != 8) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: %d-bit samples (8-bit only; 12-bit files are not decoded)", p[0]);
+      if (have_frame) TT_FAIL(TT_EUNSUPPORTED, "%s: a second frame header", who);
+      if (n < 6) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of its SOF0 segment", who);
+      if (p[0] != 8) TT_FAIL(TT_EUNSUPPORTED, "%s: %d-bit samples (8-bit only; 12-bit files are not decoded)", who, p[0]);
       hd.h = (p[1] << 8) | p[2];
       hd.w = (p[3] << 8) | p[4];
       const int nc = p[5];
-      if (nc == 4) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: four components (CMYK / YCCK files are not decoded)");
-      if (nc != 1 && nc != 3) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: %d components (1: grey, or 3: YCbCr)", nc);
-      if (n < 6 + 3 * nc) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of its SOF0 segment");
-      if (hd.h <= 0 || hd.w <= 0) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a frame of %d x %d (a height of 0 waits for a DNL marker)", hd.h, hd.w);
+      if (nc == 4) TT_FAIL(TT_EUNSUPPORTED, "%s: four components (CMYK / YCCK files are not decoded)", who);
+      if (nc != 1 && nc != 3) TT_FAIL(TT_EUNSUPPORTED, "%s: %d components (1: grey, or 3: YCbCr)", who, nc);
+      if (n < 6 + 3 * nc) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of its SOF0 segment", who);
+      if (hd.h <= 0 || hd.w <= 0) TT_FAIL(TT_EUNSUPPORTED, "%s: a frame of %d x %d (a height of 0 waits for a DNL marker)", who, hd.h, hd.w);
       hd.ch = nc;
       int samp[3] = {0x11, 0x11, 0x11};
       for (int c = 0; c < nc; ++c) {
         comp_id[c] = p[6 + 3 * c];
         samp[c] = p[7 + 3 * c];
         comp_quant[c] = p[8 + 3 * c];
-        if (comp_quant[c] > 3) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: component %d names quantiser table %d (0 to 3)", c, comp_quant[c]);
+        if (comp_quant[c] > 3) TT_FAIL(TT_EINVAL, "%s: component %d names quantiser table %d (0 to 3)", who, c, comp_quant[c]);
       }
       if (nc == 1) hd.subsampling = TT_JPEG_444;                     // one component: whatever its sampling factors say, 1 x 1
       else if (samp[0] == 0x11 && samp[1] == 0x11 && samp[2] == 0x11) hd.subsampling = TT_JPEG_444;
       else if (samp[0] == 0x22 && samp[1] == 0x11 && samp[2] == 0x11) hd.subsampling = TT_JPEG_420;
-      else TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: sampling %dx%d / %dx%d / %dx%d (4:4:4 or 4:2:0; 4:2:2 and others are not decoded)", samp[0] >> 4,
+      else TT_FAIL(TT_EUNSUPPORTED, "%s: sampling %dx%d / %dx%d / %dx%d (4:4:4 or 4:2:0; 4:2:2 and others are not decoded)", who, samp[0] >> 4,
                    samp[0] & 15, samp[1] >> 4, samp[1] & 15, samp[2] >> 4, samp[2] & 15);
       have_frame = true;
     } else if ((marker >= 0xc1 && marker <= 0xcf) && marker != 0xc4 && marker != 0xc8 && marker != 0xcc) {
-      TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: %s (baseline SOF0 only)", frame_kind(marker));
+      TT_FAIL(TT_EUNSUPPORTED, "%s: %s (baseline SOF0 only)", who, frame_kind(marker));
     } else if (marker == 0xcc) {
-      TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: arithmetic coding (a DAC segment)");
+      TT_FAIL(TT_EUNSUPPORTED, "%s: arithmetic coding (a DAC segment)", who);
     } else if (marker == 0xdb) {
       int64_t k = 0;
       while (k < n) {
         const int pq = p[k] >> 4, tq = p[k] & 15;
-        if (pq != 0) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a 16-bit DQT (8-bit quantiser tables only)");
-        if (tq > 3) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: DQT defines table %d (0 to 3)", tq);
-        if (k + 65 > n) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of a DQT table");
+        if (pq != 0) TT_FAIL(TT_EUNSUPPORTED, "%s: a 16-bit DQT (8-bit quantiser tables only)", who);
+        if (tq > 3) TT_FAIL(TT_EINVAL, "%s: DQT defines table %d (0 to 3)", who, tq);
+        if (k + 65 > n) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of a DQT table", who);
         for (int z = 0; z < 64; ++z) quant[tq][ZIGZAG[z]] = p[k + 1 + z];
         have_quant[tq] = true;
         k += 65;
@@ -207,13 +228,13 @@ extern "C" int tt_jpeg_parse(const uint8_t* data, int64_t size, TtJpegHeader* he
       int64_t k = 0;
       while (k < n) {
         const int tc = p[k] >> 4, th = p[k] & 15;
-        if (tc > 1) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: DHT table class %d (0: DC, or 1: AC)", tc);
-        if (th > 1) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: Huffman table index %d (baseline: 0 or 1)", th);
-        if (k + 17 > n) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of a DHT table");
+        if (tc > 1) TT_FAIL(TT_EINVAL, "%s: DHT table class %d (0: DC, or 1: AC)", who, tc);
+        if (th > 1) TT_FAIL(TT_EUNSUPPORTED, "%s: Huffman table index %d (baseline: 0 or 1)", who, th);
+        if (k + 17 > n) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of a DHT table", who);
         int total = 0;
         for (int l = 0; l < 16; ++l) total += p[k + 1 + l];
-        if (total > 256) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: a DHT table of %d codes (256 at most)", total);
-        if (k + 17 + total > n) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of a DHT table");
+        if (total > 256) TT_FAIL(TT_EINVAL, "%s: a DHT table of %d codes (256 at most)", who, total);
+        if (k + 17 + total > n) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of a DHT table", who);
         const int slot = th * 2 + tc;                                // DC 0, AC 0, DC 1, AC 1
         memcpy(hd.bits[slot], p + k + 1, 16);
         memset(hd.huffval[slot], 0, 256);
@@ -222,47 +243,89 @@ extern "C" int tt_jpeg_parse(const uint8_t* data, int64_t size, TtJpegHeader* he
         k += 17 + total;
       }
     } else if (marker == 0xdd) {
-      if (n < 2) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before the end of its DRI segment");
-      if (p[0] || p[1]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a restart interval of %d MCUs (files with restart markers are not decoded)", (p[0] << 8) | p[1]);
+      if (n < 2) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of its DRI segment", who);
+      const int v = (p[0] << 8) | p[1];
+      if (!ri && v) TT_FAIL(TT_EUNSUPPORTED, "%s: a restart interval of %d MCUs (files with restart markers are not decoded)", who, v);
+      if (have_dri && v != interval) TT_FAIL(TT_EINVAL, "%s: two DRI segments that disagree (restart intervals of %d and %d MCUs)", who_spans, interval, v);
+      have_dri = true;
+      interval = v;
     } else if (marker == 0xee) {
-      if (n >= 5 && memcmp(p, "Adobe", 5) == 0) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: an Adobe APP14 segment (Adobe colour transforms are not decoded)");
+      if (n >= 5 && memcmp(p, "Adobe", 5) == 0) TT_FAIL(TT_EUNSUPPORTED, "%s: an Adobe APP14 segment (Adobe colour transforms are not decoded)", who);
     } else if (marker == 0xda) {
-      if (!have_frame) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: SOS before SOF0");
-      if (n < 1 || n != 4 + 2 * p[0]) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: an SOS segment of %lld bytes for %d components", (long long)n, n < 1 ? 0 : p[0]);
-      if (p[0] != hd.ch) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: several scans: the first holds %d of %d components (one interleaved scan only)", p[0], hd.ch);
+      if (!have_frame) TT_FAIL(TT_EINVAL, "%s: SOS before SOF0", who);
+      if (n < 1 || n != 4 + 2 * p[0]) TT_FAIL(TT_EINVAL, "%s: an SOS segment of %lld bytes for %d components", who, (long long)n, n < 1 ? 0 : p[0]);
+      if (p[0] != hd.ch) TT_FAIL(TT_EUNSUPPORTED, "%s: several scans: the first holds %d of %d components (one interleaved scan only)", who, p[0], hd.ch);
       for (int c = 0; c < hd.ch; ++c) {
-        if (p[1 + 2 * c] != comp_id[c]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: the scan's component %d is not the frame's (components in frame order only)", c);
+        if (p[1 + 2 * c] != comp_id[c]) TT_FAIL(TT_EUNSUPPORTED, "%s: the scan's component %d is not the frame's (components in frame order only)", who, c);
         const int td = p[2 + 2 * c] >> 4, ta = p[2 + 2 * c] & 15;
-        if (td > 1 || ta > 1) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: Huffman table index %d (baseline: 0 or 1)", td > 1 ? td : ta);
-        if (!have_huff[td * 2]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: missing DC Huffman table %d (component %d)", td, c);
-        if (!have_huff[ta * 2 + 1]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: missing AC Huffman table %d (component %d)", ta, c);
-        if (!have_quant[comp_quant[c]]) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: missing quantiser table %d (component %d)", comp_quant[c], c);
+        if (td > 1 || ta > 1) TT_FAIL(TT_EUNSUPPORTED, "%s: Huffman table index %d (baseline: 0 or 1)", who, td > 1 ? td : ta);
+        if (!have_huff[td * 2]) TT_FAIL(TT_EUNSUPPORTED, "%s: missing DC Huffman table %d (component %d)", who, td, c);
+        if (!have_huff[ta * 2 + 1]) TT_FAIL(TT_EUNSUPPORTED, "%s: missing AC Huffman table %d (component %d)", who, ta, c);
+        if (!have_quant[comp_quant[c]]) TT_FAIL(TT_EUNSUPPORTED, "%s: missing quantiser table %d (component %d)", who, comp_quant[c], c);
         hd.dc_table[c] = td;
         hd.ac_table[c] = ta;
         memcpy(hd.quant[c], quant[comp_quant[c]], 64);
       }
       const uint8_t* t = p + 1 + 2 * hd.ch;
       if (t[0] != 0 || t[1] != 63 || t[2] != 0)
-        TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a scan of coefficients %d to %d, approximation 0x%02x (progressive; sequential 0 to 63 only)", t[0], t[1], t[2]);
+        TT_FAIL(TT_EUNSUPPORTED, "%s: a scan of coefficients %d to %d, approximation 0x%02x (progressive; sequential 0 to 63 only)", who, t[0], t[1], t[2]);
       hd.scan_offset = at + 2 + len;
       break;
     }                                                               // APPn, COM and anything else with a length: skipped
     at += 2 + len;
   }
   // the entropy-coded segment ends at the first marker that is neither a stuffed FF 00 nor fill
-  int64_t i = hd.scan_offset;
+  // ... and, for tt_jpeg_parse_spans, is cut into spans at the RSTn markers, which must come in the order 0 .. 7, 0 ..
+  int64_t i = hd.scan_offset, first = hd.scan_offset, markers = 0;
   for (;; ++i) {
-    if (i + 1 >= size) TT_FAIL(TT_EINVAL, "tt_jpeg_parse: the file ends before EOI (%lld bytes)", (long long)size);
+    if (i + 1 >= size) TT_FAIL(TT_EINVAL, "%s: the file ends before EOI (%lld bytes)", who, (long long)size);
     if (data[i] != 0xff || data[i + 1] == 0x00) continue;
     const int m = data[i + 1];
     if (m == 0xd9) break;
-    if (m >= 0xd0 && m <= 0xd7) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: a restart marker in the scan (files with restart markers are not decoded)");
-    if (m == 0xda || m == 0xc4 || m == 0xdb) TT_FAIL(TT_EUNSUPPORTED, "tt_jpeg_parse: several scans (marker 0x%02x behind the first; one interleaved scan only)", m);
-    TT_FAIL(TT_EINVAL, "tt_jpeg_parse: marker 0x%02x inside the scan at byte %lld", m, (long long)i);
+    if (m >= 0xd0 && m <= 0xd7 && ri) {
+      if (interval == 0)
+        TT_FAIL(TT_EINVAL, "%s: a restart marker (RST%d at byte %lld) in a file %s", who_spans, m - 0xd0, (long long)i, have_dri ? "whose DRI segment says 0" : "with no DRI segment");
+      if (m - 0xd0 != (int)(markers & 7))
+        TT_FAIL(TT_EINVAL, "%s: restart marker %lld at byte %lld is RST%d where RST%d is due", who_spans, (long long)markers, (long long)i, m - 0xd0, (int)(markers & 7));
+      if (span_offsets && span_lengths && markers < span_cap) { span_offsets[markers] = first; span_lengths[markers] = i - first; }
+      ++markers;
+      first = i + 2;
+      ++i;
+      continue;
+    }
+    if (m >= 0xd0 && m <= 0xd7) TT_FAIL(TT_EUNSUPPORTED, "%s: a restart marker in the scan (files with restart markers are not decoded)", who);
+    if (m == 0xda || m == 0xc4 || m == 0xdb) TT_FAIL(TT_EUNSUPPORTED, "%s: several scans (marker 0x%02x behind the first; one interleaved scan only)", who, m);
+    TT_FAIL(TT_EINVAL, "%s: marker 0x%02x inside the scan at byte %lld", who, m, (long long)i);
   }
   hd.scan_bytes = i - hd.scan_offset;
+  if (ri) {
+    const TtJpegGeometry geo = tt_jpeg_geometry(hd.h, hd.w, hd.ch, hd.subsampling);
+    const int64_t mcus = (int64_t)geo.mcus_x * geo.mcus_y, due = interval ? (mcus + interval - 1) / interval - 1 : 0;
+    if (markers != due)
+      TT_FAIL(TT_EINVAL, "%s: %lld restart markers where a restart interval of %d over %lld MCUs has %lld", who_spans, (long long)markers, interval, (long long)mcus,
+              (long long)due);
+    if (span_offsets && span_lengths) {
+      if (span_cap < markers + 1) TT_FAIL(TT_EINVAL, "%s: span_cap too small: %lld for %lld spans", who_spans, (long long)span_cap, (long long)(markers + 1));
+      span_offsets[markers] = first;
+      span_lengths[markers] = i - first;
+    }
+    *ri = interval;
+    *nspans = markers + 1;
+  }
   *header = hd;
   return TT_OK;
+}
+
+extern "C" int tt_jpeg_parse(const uint8_t* data, int64_t size, TtJpegHeader* header) {
+  return parse_file(data, size, header, nullptr, nullptr, nullptr, 0, nullptr);
+}
+
+extern "C" int tt_jpeg_parse_spans(const uint8_t* data, int64_t size, TtJpegHeader* header, int32_t* restart_interval, int64_t* span_offsets,
+                                   int64_t* span_lengths, int64_t span_cap, int64_t* nspans) {
+  if (!restart_interval || !nspans) TT_FAIL(TT_EINVAL, "tt_jpeg_parse_spans: null %s", !restart_interval ? "restart_interval" : "nspans");
+  if ((span_offsets == nullptr) != (span_lengths == nullptr)) TT_FAIL(TT_EINVAL, "tt_jpeg_parse_spans: span_offsets and span_lengths go together (both, or neither to count)");
+  if (span_offsets && span_cap < 1) TT_FAIL(TT_EINVAL, "tt_jpeg_parse_spans: span_cap = %lld (1 or more)", (long long)span_cap);
+  return parse_file(data, size, header, restart_interval, span_offsets, span_lengths, span_cap, nspans);
 }
 
 extern "C" int tt_jpeg_decode_table(const uint8_t* bits, const uint8_t* huffval, uint32_t* table) {

@@ -33,6 +33,12 @@ inline TtJpegGeometry tt_jpeg_geometry(int32_t h, int32_t w, int32_t ch, int32_t
   const int32_t side = sub ? 16 : 8;
   return {(w + side - 1) / side, (h + side - 1) / side, ch == 1 ? 1 : (sub ? 6 : 3), ch == 1 ? 1 : 3};
 }
+// restart intervals (export rule 6a): how many a frame's scan has with an interval of `ri` MCUs -- 1 without (ri = 0) --, one marker fewer
+inline int64_t tt_jpeg_intervals(int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t ri) {
+  const TtJpegGeometry g = tt_jpeg_geometry(h, w, ch, subsampling);
+  const int64_t mcus = (int64_t)g.mcus_x * g.mcus_y;
+  return ri > 0 ? (mcus + ri - 1) / ri : 1;
+}
 // the quantiser tables as the kernels take them: a kernel argument, read through scalar loads
 struct TtJpegQuant { uint8_t q[2][64]; };
 void tt_jpeg_fill_quant(int32_t quality, TtJpegQuant* out);
@@ -44,21 +50,33 @@ inline int64_t tt_jpeg_plain_stride(int64_t max_bytes) { return (max_bytes + 15)
 // The workspaces' layouts: byte offsets of the sub-buffers, each a multiple of 16, and the total the size query returns (0: a problem
 // the entry point refuses).  The size queries and the entry points both read these, and nothing else carves a workspace.
 inline int64_t tt_jpeg_up16(int64_t v) { return (v + 15) / 16 * 16; }
-// tt_jpeg_scan: a frame's unstuffed scan is at most half its tt_jpeg_scan_bound (a multiple of 8 bytes), stuffed in chunks of TT_JPEG_CHUNK
+// tt_jpeg_scan: a frame's unstuffed scan is at most half its tt_jpeg_scan_bound (a multiple of 8 bytes), stuffed in chunks of TT_JPEG_CHUNK.
+// With a restart interval (ri > 0; tt_jpeg_scan_restart) the bound is tt_jpeg_scan_bound_restart, and two sub-buffers follow the streams:
+// per interval the bits its pad and marker and those of the intervals before it add, and per frame a bitmap of its unstuffed bytes whose
+// set bits are the markers' 0xFF bytes.  ri = 0 is tt_jpeg_scan's layout, byte for byte.
 struct TtJpegScanWs {
   int64_t plain_stride, chunks;                    // per frame: bytes of its region of `plain`, stuffing chunks
   int64_t bits, plain_bytes, chunk_ff, plain;      // uint32 per block; uint32 per frame; uint32 per chunk; the unstuffed streams
+  int64_t intervals, mark_words, extra, marks;     // ri > 0: per frame its intervals and bitmap words; uint32 per interval; the bitmaps
   int64_t total;
-  TtJpegScanWs(int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling) : plain_stride(0), chunks(0), bits(0), plain_bytes(0), chunk_ff(0), plain(0), total(0) {
+  TtJpegScanWs(int32_t n, int32_t h, int32_t w, int32_t ch, int32_t subsampling, int32_t ri = 0)
+      : plain_stride(0), chunks(0), bits(0), plain_bytes(0), chunk_ff(0), plain(0), intervals(0), mark_words(0), extra(0), marks(0), total(0) {
     const int64_t blocks = tt_jpeg_blocks(h, w, ch, subsampling);
     if (!blocks || n <= 0) return;
-    const int64_t bytes = tt_jpeg_scan_bound(h, w, ch, subsampling) / 2;
+    const int64_t bytes = (ri > 0 ? tt_jpeg_scan_bound_restart(h, w, ch, subsampling, ri) : tt_jpeg_scan_bound(h, w, ch, subsampling)) / 2;
     plain_stride = tt_jpeg_up16(bytes);
     chunks = (bytes + TT_JPEG_CHUNK - 1) / TT_JPEG_CHUNK;
     plain_bytes = bits + tt_jpeg_up16(4 * n * blocks);
     chunk_ff = plain_bytes + tt_jpeg_up16(4 * (int64_t)n);
     plain = chunk_ff + tt_jpeg_up16(4 * n * chunks);
     total = plain + n * plain_stride;
+    if (ri > 0) {
+      intervals = tt_jpeg_intervals(h, w, ch, subsampling, ri);
+      mark_words = (plain_stride + 31) / 32;
+      extra = total;
+      marks = extra + tt_jpeg_up16(4 * n * intervals);
+      total = marks + tt_jpeg_up16(4 * n * mark_words);
+    }
   }
 };
 // tt_jpeg_entropy: scans of at most max_bytes each, unstuffed in chunks of TT_JPEG_CHUNK

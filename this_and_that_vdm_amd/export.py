@@ -34,7 +34,8 @@ routines of the library):
 ``encode_jpeg``: ONE launch from pixels to zig-zag coefficients for all frames, then the bits of every block, a scan for their
 positions, the bits themselves and the byte stuffing, with no host round trip in between when the standard Huffman tables are used;
 the lengths and the finished scans are read back.  With the standard tables the scan equals libjpeg's (Pillow's) byte for byte.
-Not here: progressive or arithmetic coding, 4:2:2, restart markers, EXIF / ICC, CMYK, 12 bits, trellis quantisation, a decoder."""
+Restart intervals: ``restart_interval`` / ``restart_rows``.  Not here: progressive or arithmetic coding, 4:2:2, EXIF / ICC, CMYK, 12 bits,
+trellis quantisation (the decoder is ingest.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -495,9 +496,9 @@ def _jpeg_segment(marker: int, payload: bytes) -> bytes:
     return b"\xff" + bytes([marker]) + struct.pack(">H", len(payload) + 2) + payload
 
 
-def jpeg_file(scan: bytes, height: int, width: int, channels: int, quality: int, subsampling: str, tables: list) -> bytes:
+def jpeg_file(scan: bytes, height: int, width: int, channels: int, quality: int, subsampling: str, tables: list, restart_interval: int = 0) -> bytes:
     """one frame's entropy-coded scan -> its file (rule 8): SOI, APP0 JFIF 1.01, a DQT marker per quantiser table, SOF0, a DHT marker
-    per Huffman table, SOS, the scan, EOI -- the layout libjpeg writes"""
+    per Huffman table, with a ``restart_interval`` DRI, SOS, the scan, EOI -- the layout libjpeg writes"""
     qt = jpeg_quant_tables(quality)
     grey = channels == 1
     out = [b"\xff\xd8", _jpeg_segment(0xe0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
@@ -508,6 +509,8 @@ def jpeg_file(scan: bytes, height: int, width: int, channels: int, quality: int,
     out.append(_jpeg_segment(0xc0, sof))
     for i in range(2 if grey else 4):
         out.append(_jpeg_segment(0xc4, bytes([((i & 1) << 4) | (i >> 1)]) + bytes(tables[i].bits) + bytes(tables[i].huffval)))
+    if restart_interval:
+        out.append(_jpeg_segment(0xdd, struct.pack(">H", restart_interval)))
     sos = bytes([1 if grey else 3, 1, 0x00]) + (b"" if grey else bytes([2, 0x11, 3, 0x11])) + bytes([0, 63, 0])
     out += [_jpeg_segment(0xda, sos), scan, b"\xff\xd9"]
     return b"".join(out)
@@ -523,13 +526,30 @@ def _jpeg_args(quality, subsampling, huffman, who: str):
     return int(quality)
 
 
-def encode_jpeg(frames, quality: int = 75, subsampling: str = "4:2:0", huffman: str = "standard") -> list:
+def _jpeg_restart_interval(restart_interval, restart_rows, height: int, width: int, channels: int, subsampling: str, who: str) -> int:
+    """Pillow's two options -> the interval in MCUs (0: none); rows are counted in the frame's MCUs per row"""
+    for name, v in (("restart_interval", restart_interval), ("restart_rows", restart_rows)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+            raise ValueError(f"{who}: {name} {v!r} (an integer, 0 or more)")
+    if restart_interval and restart_rows:
+        raise ValueError(f"{who}: restart_interval {restart_interval} and restart_rows {restart_rows}: at most one of the two")
+    side = 16 if (channels == 3 and subsampling == "4:2:0") else 8
+    ri = int(restart_interval) or int(restart_rows) * -(-width // side)
+    if ri > 65535:
+        raise ValueError(f"{who}: a restart interval of {ri} MCUs (DRI holds 65535 at most; it is not clipped)")
+    return ri
+
+
+def encode_jpeg(frames, quality: int = 75, subsampling: str = "4:2:0", huffman: str = "standard", restart_interval: int = 0, restart_rows: int = 0) -> list:
     """Frames -> one baseline JPEG file (bytes) per frame.  ``frames``: what ``write_gif`` takes, with 1 channel (grey, [F, H, W, 1]) or
     3 (RGB) -- a device uint8 / float32 NHWC tensor, ``DevicePixels``, numpy, a list of PIL images or a pipeline's "pil" / "np" /
     "device" output for ONE video; floating-point frames are rounded as for ``write_gif``.  ``quality`` 1 .. 100 scales the Annex K
     quantiser tables as libjpeg does; ``subsampling`` "4:2:0" or "4:4:4" (a grey frame has no chroma and ignores it); ``huffman``
     "standard" (the Annex K.3 tables: no host round trip between the first launch and the readback, and the scan equals libjpeg's
     byte for byte) or "optimized" (per-frame tables from symbol counts taken on the device: one more readback of 4 KiB per frame).
+    ``restart_interval`` (in MCUs) or ``restart_rows`` (in MCU rows; at most one of the two, Pillow's ``restart_marker_blocks`` /
+    ``restart_marker_rows``) writes a DRI segment and a restart marker every that many MCUs, as libjpeg does: a decoder may then take
+    every interval on its own (``ingest.decode_jpeg`` gives each its own workgroup); the default 0 writes none, today's bytes.
     Only the finished scans and their lengths cross to the host.  The same frames give the same bytes from host and device copies."""
     from . import ops
     quality = _jpeg_args(quality, subsampling, huffman, "encode_jpeg")
@@ -538,10 +558,13 @@ def encode_jpeg(frames, quality: int = 75, subsampling: str = "4:2:0", huffman: 
         raise ValueError(f"encode_jpeg: 1 (grey) or 3 (RGB) channels -- JPEG has no alpha --, got {shape[-1]} in {shape}")
     if shape[-3] > 65535 or shape[-2] > 65535:
         raise ValueError(f"encode_jpeg: a JPEG is at most 65535 pixels a side, got {shape[-3]} x {shape[-2]}")
+    ri = _jpeg_restart_interval(restart_interval, restart_rows, shape[-3], shape[-2], shape[-1], subsampling, "encode_jpeg")      # before any upload
     x = _frames_u8(src, "encode_jpeg", rgb=False)
     f, h, w, ch = x.shape
     optimized = huffman == "optimized"
-    coeffs, counts = ops.jpeg_coeffs(x, quality, subsampling, counts=optimized)
+    coeffs, counts = ops.jpeg_coeffs(x, quality, subsampling, counts=optimized and not ri)
+    if optimized and ri:
+        counts = ops.jpeg_counts_restart(coeffs, (h, w, ch), subsampling, ri)                  # the predictors reset where the scan's do
     if optimized:
         cnt = counts.cpu().numpy().view(np.uint32)                                             # the extra readback: 4 KiB per frame
         per_frame = [[jpeg_optimized_table(cnt[i, k]) for k in range(4)] for i in range(f)]
@@ -552,11 +575,11 @@ def encode_jpeg(frames, quality: int = 75, subsampling: str = "4:2:0", huffman: 
         tables = _JPEG_STANDARD.get(x.device)
         if tables is None:
             tables = _JPEG_STANDARD[x.device] = torch.from_numpy(np.stack([t.codes for t in standard]).view(np.int32)[None]).to(x.device)
-    out, lengths = ops.jpeg_scan(coeffs, (h, w, ch), subsampling, tables)
+    out, lengths = ops.jpeg_scan(coeffs, (h, w, ch), subsampling, tables, restart_interval=ri)
     lens = lengths.cpu().numpy().astype(np.int64)                                              # readback 1: one length per frame
     packed = torch.cat([out[i, :int(lens[i])] for i in range(f)]).cpu().numpy()                # readback 2: the finished scans, no padding
     ends = np.cumsum(lens)
-    return [jpeg_file(packed[int(e - n):int(e)].tobytes(), h, w, ch, quality, subsampling, per_frame[i]) for i, (e, n) in enumerate(zip(ends, lens))]
+    return [jpeg_file(packed[int(e - n):int(e)].tobytes(), h, w, ch, quality, subsampling, per_frame[i], ri) for i, (e, n) in enumerate(zip(ends, lens))]
 
 
 def write_jpegs(frames, folder, pattern: str = "im_{idx}.jpg", **kw) -> list:

@@ -1,11 +1,15 @@
 """Baseline JPEG files decoded on the device (include/ttvdm.h, "JPEG import"): a clip folder im_0.jpg .. im_{F-1}.jpg, a folder
 ``export.write_jpegs`` wrote, a Motion-JPEG AVI or a request's image become uint8 [F, H, W, ch] NHWC device tensors holding byte for
-byte what ``np.asarray(PIL.Image.open(f))`` holds.  The host reads the files' headers (tt_jpeg_parse) and builds the decode tables
+byte what ``np.asarray(PIL.Image.open(f))`` holds.  The host reads the files' headers (tt_jpeg_parse_spans) and builds the decode tables
 (tt_jpeg_decode_table); only the compressed scans cross to the device, where they are unstuffed, entropy-decoded, dequantised,
 inverted, upsampled and converted.  There is no CPU fallback and no Pillow here.
 
+Restart intervals: a file with a DRI segment and RSTn markers (``export.write_jpegs(..., restart_rows=1)``'s, a camera's) is cut into
+the spans between its markers, and the entropy decoder gives every span a workgroup of its own instead of one per frame.  A file
+without them is one span and decodes through the same launches as before; the reference dataset's own im_0.jpg files carry none.
+
 Not applied: EXIF orientation (``load_image`` of the reference applies it; rotate the result when the files carry one).  Refused by
-name: progressive, arithmetic and 12-bit files, restart markers, several scans, 4:2:2, CMYK / Adobe files."""
+name: progressive, arithmetic and 12-bit files, several scans, 4:2:2, CMYK / Adobe files, restart markers out of order or count."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,7 +29,9 @@ _SUBSAMPLING = {_lib.TT_JPEG_444: "4:4:4", _lib.TT_JPEG_420: "4:2:0"}
 class JpegHeader:
     """What ``parse_jpeg`` reads from one file: the geometry, ``subsampling`` ("4:4:4" / "4:2:0"; grey files are "4:4:4"), the byte range
     of the entropy-coded scan, ``quant`` uint8 [3, 64] (per component, natural order), ``dc_table`` / ``ac_table`` (per component, 0 or
-    1) and the Huffman tables DC 0, AC 0, DC 1, AC 1 as ``bits`` uint8 [4, 16] and ``huffval`` uint8 [4, 256]."""
+    1), the Huffman tables DC 0, AC 0, DC 1, AC 1 as ``bits`` uint8 [4, 16] and ``huffval`` uint8 [4, 256], ``restart_interval`` (MCUs; 0:
+    none) and ``spans``: int64 [S, 2], per restart interval of the scan its byte offset in the file and its stuffed length, markers
+    excluded -- one row, the scan's range, for a file without markers."""
     height: int
     width: int
     channels: int
@@ -37,19 +43,27 @@ class JpegHeader:
     ac_table: list
     bits: np.ndarray
     huffval: np.ndarray
+    restart_interval: int = 0
+    spans: np.ndarray = None
 
 
 def parse_jpeg(data: bytes) -> JpegHeader:
-    """One baseline JPEG file -> its header (tt_jpeg_parse); ValueError with the library's text for what is refused."""
+    """One baseline JPEG file -> its header and the spans of its scan (tt_jpeg_parse_spans: once to count the spans, once to take
+    them); ValueError with the library's text for what is refused."""
     lib = _lib.load()
     hd = _lib.TtJpegHeader()
     buf = np.frombuffer(data, dtype=np.uint8)
-    rc = lib.tt_jpeg_parse(buf.ctypes.data if buf.size else None, buf.size, C.byref(hd))
+    at = buf.ctypes.data if buf.size else None
+    ri, count = C.c_int32(0), C.c_int64(0)
+    rc = lib.tt_jpeg_parse_spans(at, buf.size, C.byref(hd), C.byref(ri), None, None, 0, C.byref(count))
+    if rc == 0:
+        offs, lens = np.zeros(count.value, dtype=np.int64), np.zeros(count.value, dtype=np.int64)
+        rc = lib.tt_jpeg_parse_spans(at, buf.size, C.byref(hd), C.byref(ri), offs.ctypes.data, lens.ctypes.data, offs.size, C.byref(count))
     if rc != 0:
         raise ValueError(lib.tt_last_error().decode(errors="replace"))
     return JpegHeader(hd.h, hd.w, hd.ch, _SUBSAMPLING[hd.subsampling], hd.scan_offset, hd.scan_bytes,
                       np.ctypeslib.as_array(hd.quant).copy(), list(hd.dc_table)[:hd.ch], list(hd.ac_table)[:hd.ch],
-                      np.ctypeslib.as_array(hd.bits).copy(), np.ctypeslib.as_array(hd.huffval).copy())
+                      np.ctypeslib.as_array(hd.bits).copy(), np.ctypeslib.as_array(hd.huffval).copy(), ri.value, np.stack([offs, lens], axis=1))
 
 
 def jpeg_decode_table(bits, huffval) -> np.ndarray:
@@ -92,8 +106,9 @@ def _read(f) -> bytes:
 def decode_jpeg(files, device) -> torch.Tensor:
     """Baseline JPEG files of ONE geometry and subsampling -- bytes or paths, one or a list -- -> uint8 [F, H, W, ch] on ``device``, ch 1
     (grey) or 3 (RGB): Pillow's decoded pixels, byte for byte.  One upload (the scans, end to end), one readback (a status word per
-    frame).  ValueError: a file the parser refuses (its text names the cause), files that differ in size or subsampling, a frame whose
-    scan is corrupt or truncated (the frame is named)."""
+    frame).  Files with restart markers are decoded span by span, one workgroup each; the files of a call may carry different restart
+    intervals, or none.  ValueError: a file the parser refuses (its text names the cause), files that differ in size or subsampling,
+    more than 65535 spans in all, a frame whose scan is corrupt or truncated (the frame is named)."""
     from . import ops
     items = list(files) if isinstance(files, (list, tuple)) else [files]
     if not items:
@@ -118,6 +133,22 @@ def decode_jpeg(files, device) -> torch.Tensor:
     h0 = heads[0]
     lens = np.array([len(b) for b in blobs], dtype=np.int64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    marked = any(len(h.spans) > 1 for h in heads)
+    if marked:                                                                                     # before any upload
+        # every span: where it lies in the uploaded scans, its frame, its first block there and its blocks (Ri MCUs; the last may be shorter)
+        blocks = _lib.load().tt_jpeg_blocks(h0.height, h0.width, h0.channels, ops.JPEG_SUBSAMPLING[h0.subsampling])
+        bpm = 1 if h0.channels == 1 else (6 if h0.subsampling == "4:2:0" else 3)
+        rows = []
+        for i, h in enumerate(heads):
+            per = h.restart_interval * bpm if len(h.spans) > 1 else blocks
+            for k, (o, n) in enumerate(h.spans.tolist()):
+                rows.append((offs[i] + o - h.scan_offset, n, i, k * per, min(per, blocks - k * per)))
+        if len(rows) > _lib.TT_JPEG_MAX_SPANS:
+            raise ValueError(f"decode_jpeg: {len(rows)} restart intervals in {len(heads)} files: more spans than one call decodes ({_lib.TT_JPEG_MAX_SPANS})")
+        rows = np.array(rows, dtype=np.int64)
+        if rows[:, 1].min() < 1:
+            i = int(rows[int(rows[:, 1].argmin()), 2])
+            raise ValueError(f"decode_jpeg: file {i}: an empty restart interval")
     same_tables = all(np.array_equal(h.bits, h0.bits) and np.array_equal(h.huffval, h0.huffval) and h.dc_table == h0.dc_table and h.ac_table == h0.ac_table
                       for h in heads[1:])
     same_quant = all(np.array_equal(h.quant, h0.quant) for h in heads[1:])
@@ -130,8 +161,14 @@ def decode_jpeg(files, device) -> torch.Tensor:
     quant = np.stack([h.quant for h in (heads[:1] if same_quant else heads)])
     scans = torch.from_numpy(np.frombuffer(b"".join(blobs), dtype=np.uint8).copy()).to(device)
     shape = (h0.height, h0.width, h0.channels)
-    coeffs, status = ops.jpeg_entropy(scans, torch.from_numpy(offs).to(device), torch.from_numpy(lens.astype(np.int32)).to(device), int(lens.max()), shape,
-                                      h0.subsampling, torch.from_numpy(sets.view(np.int32)).to(device))
+    tables = torch.from_numpy(sets.view(np.int32)).to(device)
+    if marked:
+        cols = torch.from_numpy(np.ascontiguousarray(rows.T)).to(device)                       # one more small upload: five numbers a span
+        coeffs, status = ops.jpeg_entropy_spans(scans, cols[0].contiguous(), cols[1].to(torch.int32), cols[2].to(torch.int32), cols[3].to(torch.int32),
+                                                cols[4].to(torch.int32), int(rows[:, 1].max()), len(heads), shape, h0.subsampling, tables)
+    else:
+        coeffs, status = ops.jpeg_entropy(scans, torch.from_numpy(offs).to(device), torch.from_numpy(lens.astype(np.int32)).to(device), int(lens.max()), shape,
+                                          h0.subsampling, tables)
     frames = ops.jpeg_pixels(coeffs, shape, h0.subsampling, torch.from_numpy(quant).to(device))
     for i, s in enumerate(status.cpu().tolist()):
         if s:

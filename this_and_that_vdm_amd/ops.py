@@ -1298,12 +1298,37 @@ def jpeg_coeffs(frames: torch.Tensor, quality: int = 75, subsampling="4:2:0", co
     return coeffs, cnt
 
 
-def jpeg_scan(coeffs: torch.Tensor, shape, subsampling, tables: torch.Tensor):
+def _jpeg_restart(restart_interval, what: str) -> int:
+    if isinstance(restart_interval, bool) or not isinstance(restart_interval, int) or not 0 <= restart_interval <= 65535:
+        raise RuntimeError(f"{what}: restart_interval {restart_interval!r} (an integer: 0 for none, to 65535 MCUs)")
+    return restart_interval
+
+
+def jpeg_counts_restart(coeffs: torch.Tensor, shape, subsampling, restart_interval: int) -> torch.Tensor:
+    """``jpeg_coeffs``' coefficients -> int32 device tensor [N, 4, 256] (uint32 bits): the frames' symbol counts with the DC predictors
+    reset every ``restart_interval`` MCUs (tt_jpeg_counts_restart); 0 gives ``jpeg_coeffs``' own counts."""
+    lib = _lib.load()
+    h, w, ch, sub = _jpeg_shape(shape, subsampling, "jpeg_counts_restart")
+    ri = _jpeg_restart(restart_interval, "jpeg_counts_restart")
+    _p(coeffs)
+    blocks = lib.tt_jpeg_blocks(h, w, ch, sub)
+    if coeffs.dtype != torch.int16 or coeffs.dim() != 3 or tuple(coeffs.shape[1:]) != (blocks, 64) or not coeffs.is_contiguous() or coeffs.shape[0] < 1:
+        raise RuntimeError(f"jpeg_counts_restart: coeffs must be a contiguous int16 tensor [N, {blocks}, 64] (jpeg_coeffs'), got {tuple(coeffs.shape)} {coeffs.dtype}")
+    n = coeffs.shape[0]
+    cnt = torch.empty((n, 4, _lib.TT_JPEG_TABLE_WORDS), dtype=torch.int32, device=coeffs.device)
+    check(lib.tt_jpeg_counts_restart(_p(coeffs), n, h, w, ch, sub, ri, _p(cnt), _stream()), "tt_jpeg_counts_restart")
+    _wrote(cnt, "jpeg_counts_restart")
+    return cnt
+
+
+def jpeg_scan(coeffs: torch.Tensor, shape, subsampling, tables: torch.Tensor, restart_interval: int = 0):
     """``jpeg_coeffs``' coefficients for frames of ``shape`` (h, w, ch) and code tables [1 or N, 4, 256] (int32 device tensor: per symbol
     code | length << 16, what export.jpeg_standard_tables / jpeg_optimized_tables make) -> (uint8 device tensor [N, stride]: every
-    frame's finished, byte-stuffed scan; int32 device tensor [N]: its length; bytes behind it are not written) (tt_jpeg_scan)."""
+    frame's finished, byte-stuffed scan; int32 device tensor [N]: its length; bytes behind it are not written) (tt_jpeg_scan).  With
+    ``restart_interval`` > 0 the scan carries a restart marker every that many MCUs (tt_jpeg_scan_restart; the stride grows by them)."""
     lib = _lib.load()
     h, w, ch, sub = _jpeg_shape(shape, subsampling, "jpeg_scan")
+    ri = _jpeg_restart(restart_interval, "jpeg_scan")
     _p(coeffs)
     blocks = lib.tt_jpeg_blocks(h, w, ch, sub)
     if coeffs.dtype != torch.int16 or coeffs.dim() != 3 or tuple(coeffs.shape[1:]) != (blocks, 64) or not coeffs.is_contiguous() or coeffs.shape[0] < 1:
@@ -1314,12 +1339,17 @@ def jpeg_scan(coeffs: torch.Tensor, shape, subsampling, tables: torch.Tensor):
             or not tables.is_contiguous() or tables.device != coeffs.device:
         raise RuntimeError(f"jpeg_scan: tables must be a contiguous int32 tensor [1 or {n}, 4, {_lib.TT_JPEG_TABLE_WORDS}] on {coeffs.device}, got "
                            f"{tuple(tables.shape)} {tables.dtype}")
-    stride = lib.tt_jpeg_scan_bound(h, w, ch, sub)
+    stride = lib.tt_jpeg_scan_bound_restart(h, w, ch, sub, ri) if ri else lib.tt_jpeg_scan_bound(h, w, ch, sub)
     out = torch.empty((n, stride), dtype=torch.uint8, device=coeffs.device)
     lengths = torch.empty((n,), dtype=torch.int32, device=coeffs.device)
-    ws = torch.empty((lib.tt_jpeg_scan_ws_bytes(n, h, w, ch, sub),), dtype=torch.uint8, device=coeffs.device)
-    check(lib.tt_jpeg_scan(_p(coeffs), n, h, w, ch, sub, _p(tables), tables.shape[0], _p(out), out.numel(), _p(lengths), _p(ws), ws.numel(), _stream()),
-          "tt_jpeg_scan")
+    if ri:
+        ws = torch.empty((lib.tt_jpeg_scan_restart_ws_bytes(n, h, w, ch, sub, ri),), dtype=torch.uint8, device=coeffs.device)
+        check(lib.tt_jpeg_scan_restart(_p(coeffs), n, h, w, ch, sub, ri, _p(tables), tables.shape[0], _p(out), out.numel(), _p(lengths), _p(ws), ws.numel(),
+                                       _stream()), "tt_jpeg_scan_restart")
+    else:
+        ws = torch.empty((lib.tt_jpeg_scan_ws_bytes(n, h, w, ch, sub),), dtype=torch.uint8, device=coeffs.device)
+        check(lib.tt_jpeg_scan(_p(coeffs), n, h, w, ch, sub, _p(tables), tables.shape[0], _p(out), out.numel(), _p(lengths), _p(ws), ws.numel(), _stream()),
+              "tt_jpeg_scan")
     _wrote(out, "jpeg_scan")
     _wrote(lengths, "jpeg_scan")
     return out, lengths
@@ -1358,6 +1388,48 @@ def jpeg_entropy(scans: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tens
                               _p(status), _p(ws), ws.numel(), _stream()), "tt_jpeg_entropy")
     _wrote(coeffs, "jpeg_entropy")
     _wrote(status, "jpeg_entropy")
+    return coeffs, status
+
+
+def jpeg_entropy_spans(scans: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, span_frame: torch.Tensor, span_first: torch.Tensor,
+                       span_blocks: torch.Tensor, max_bytes: int, frames: int, shape, subsampling, tables: torch.Tensor):
+    """``jpeg_entropy`` per SPAN -- the stretch of a scan between two restart markers -- instead of per frame: one workgroup a span
+    (tt_jpeg_entropy_spans).  Span s is ``offsets[s]`` / ``lengths[s]`` of ``scans`` (int64 / int32 device tensors [S]), belongs to frame
+    ``span_frame[s]`` and holds ``span_blocks[s]`` blocks from block ``span_first[s]`` of it (int32 device tensors [S]); ``max_bytes``: a
+    host integer no span's length exceeds; ``frames``: N; ``tables``: int32 [1 or N, 1028].  -> (coeffs int16 [N, blocks, 64], status int32
+    [N], per FRAME).  At most 65535 spans a call."""
+    lib = _lib.load()
+    h, w, ch, sub = _jpeg_shape(shape, subsampling, "jpeg_entropy_spans")
+    for t in (scans, offsets, lengths, span_frame, span_first, span_blocks, tables):
+        _p(t)
+    if scans.dtype != torch.uint8 or not scans.is_contiguous() or scans.numel() < 1:
+        raise RuntimeError(f"jpeg_entropy_spans: scans must be a contiguous uint8 tensor, got {tuple(scans.shape)} {scans.dtype}")
+    s = offsets.numel()
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or s < 1 or not offsets.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy_spans: offsets int64 [S], got {tuple(offsets.shape)} {offsets.dtype}")
+    for name, t in (("lengths", lengths), ("span_frame", span_frame), ("span_first", span_first), ("span_blocks", span_blocks)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (s,) or not t.is_contiguous():
+            raise RuntimeError(f"jpeg_entropy_spans: {name} int32 [{s}], got {tuple(t.shape)} {t.dtype}")
+    if s > _lib.TT_JPEG_MAX_SPANS:
+        raise RuntimeError(f"jpeg_entropy_spans: {s} spans in one call (at most {_lib.TT_JPEG_MAX_SPANS})")
+    n = frames
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise RuntimeError(f"jpeg_entropy_spans: frames {frames!r} (a positive integer)")
+    if tables.dtype != torch.int32 or tables.dim() != 2 or tables.shape[1] != _lib.TT_JPEG_DECODE_SET_WORDS or tables.shape[0] not in (1, n) \
+            or not tables.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy_spans: tables must be a contiguous int32 tensor [1 or {n}, {_lib.TT_JPEG_DECODE_SET_WORDS}], got "
+                           f"{tuple(tables.shape)} {tables.dtype}")
+    if any(t.device != scans.device for t in (offsets, lengths, span_frame, span_first, span_blocks, tables)):
+        raise RuntimeError("jpeg_entropy_spans: scans, the span arrays and tables must be on one device")
+    if isinstance(max_bytes, bool) or not isinstance(max_bytes, int) or max_bytes < 1:
+        raise RuntimeError(f"jpeg_entropy_spans: max_bytes {max_bytes!r} (a positive integer)")
+    coeffs = torch.empty((n, lib.tt_jpeg_blocks(h, w, ch, sub), 64), dtype=torch.int16, device=scans.device)
+    status = torch.empty((n,), dtype=torch.int32, device=scans.device)
+    ws = torch.empty((max(lib.tt_jpeg_entropy_ws_bytes(s, max_bytes), 16),), dtype=torch.uint8, device=scans.device)
+    check(lib.tt_jpeg_entropy_spans(_p(scans), scans.numel(), _p(offsets), _p(lengths), _p(span_frame), _p(span_first), _p(span_blocks), max_bytes, s, n, h, w,
+                                    ch, sub, _p(tables), tables.shape[0], _p(coeffs), _p(status), _p(ws), ws.numel(), _stream()), "tt_jpeg_entropy_spans")
+    _wrote(coeffs, "jpeg_entropy_spans")
+    _wrote(status, "jpeg_entropy_spans")
     return coeffs, status
 
 

@@ -15,7 +15,12 @@ standard tables), and the 640 x 480 fixture tests/golden/bridge_task1_im_0.jpg, 
                    -DTT_JPEG_SUBSEQ_BITS=S (`make variant NAME=s512 DEFS=-DTT_JPEG_SUBSEQ_BITS=512`), each in a child process of its own
                    that loads it through TT_LIBTTVDM
 
-The last row is ONE file, a request's image: one workgroup decodes it, the case in which the scheme has the least to offer.
+  --restart-rows N  every input twice in ONE process: written without markers and with ``restart_rows=N`` (the fixture's pixels are
+                   re-encoded once for it, quality 75, 4:2:0): entropy_us and decode_jpeg_ms of both next to Pillow's time on the same
+                   files, and ``sooner``: whether the marked files' time is below the marker-less files' of the same run.  The result
+                   goes under "decode" of profiles/jpeg_restart_bench.json (tools/jpeg_export_bench.py fills "encode").
+
+The last row is ONE file, a request's image: without markers one workgroup decodes it, the case in which the scheme has the least to offer.
 
 A record, not a gate.  Prints one JSON line and writes it to --out (default profiles/jpeg_decode_bench.json)."""
 import argparse
@@ -68,6 +73,79 @@ def pillow_decode(files):
     return torch.from_numpy(np.stack(frames)).cuda()
 
 
+def restart_row(name, plain_files, marked_files, iters):
+    """the same frames without and with restart markers: the decoder's device stage and the whole call, next to Pillow's"""
+    from this_and_that_vdm_amd import _lib, ingest, ops
+
+    def measure(files):
+        heads = [ingest.parse_jpeg(d) for d in files]
+        h0 = heads[0]
+        shape = (h0.height, h0.width, h0.channels)
+        sets = torch.from_numpy(np.stack([ingest.jpeg_decode_set([(h0.bits[k], h0.huffval[k]) for k in range(4)], h0.dc_table, h0.ac_table)]).view(np.int32)).cuda()
+        blocks = _lib.load().tt_jpeg_blocks(*shape, ops.JPEG_SUBSAMPLING[h0.subsampling])
+        per = h0.restart_interval * 6 if len(h0.spans) > 1 else blocks                  # 4:2:0 RGB: 6 blocks an MCU
+        rows, base = [], 0
+        for i, (d, h) in enumerate(zip(files, heads)):
+            rows += [(base + o, n, i, k * per, min(per, blocks - k * per)) for k, (o, n) in enumerate(h.spans.tolist())]
+            base += len(d)
+        rows = np.array(rows, dtype=np.int64)
+        scans = torch.from_numpy(np.frombuffer(b"".join(files), dtype=np.uint8).copy()).cuda()
+        offs = torch.from_numpy(rows[:, 0].copy()).cuda()
+        cols = [torch.from_numpy(rows[:, c].astype(np.int32)).cuda() for c in range(1, 5)]
+        if len(rows) == len(files):                                                     # no markers: the per-frame entry point, as decode_jpeg takes it
+            entropy = lambda: ops.jpeg_entropy(scans, offs, cols[0], int(rows[:, 1].max()), shape, h0.subsampling, sets)
+        else:
+            entropy = lambda: ops.jpeg_entropy_spans(scans, offs, *cols, int(rows[:, 1].max()), len(files), shape, h0.subsampling, sets)
+        got = ingest.decode_jpeg(files, "cuda")
+        return dict(file_bytes=int(sum(len(d) for d in files)), spans=int(len(rows)), restart_interval=int(h0.restart_interval),
+                    equal=bool(torch.equal(got, pillow_decode(files))) and not bool(entropy()[1].any()),
+                    entropy_us=round(events_us(entropy, iters), 1), decode_jpeg_ms=round(wall_ms(lambda: ingest.decode_jpeg(files, "cuda"), iters), 2),
+                    pillow_ms=round(wall_ms(lambda: pillow_decode(files), iters), 2)), got
+
+    plain, a = measure(plain_files)
+    marked, b = measure(marked_files)
+    return dict(input=name, frames=[len(plain_files), *a.shape[1:]], same_pixels=bool(torch.equal(a, b)), plain=plain, marked=marked,
+                sooner=dict(entropy=bool(marked["entropy_us"] < plain["entropy_us"]), decode_jpeg=bool(marked["decode_jpeg_ms"] < plain["decode_jpeg_ms"])),
+                marked_faster_than_pillow=bool(marked["decode_jpeg_ms"] < marked["pillow_ms"]))
+
+
+def restart_main(a):
+    """--restart-rows: the rows of the issue's table -> profiles/jpeg_restart_bench.json, key "decode" """
+    from tests import png_reference as ref
+    from this_and_that_vdm_amd import export
+    rows = []
+    for n, h, w in [(14, 256, 384), (14, 576, 1024)]:
+        dev = torch.from_numpy(np.stack([ref.generator_frame(h, w, f) for f in range(n)], 0)).cuda()
+        for quality in (75, 95):
+            rows.append(restart_row(f"write_jpegs {h}x{w} quality {quality}", export.encode_jpeg(dev, quality=quality),
+                                    export.encode_jpeg(dev, quality=quality, restart_rows=a.restart_rows), a.iters))
+    with open(os.path.join(REPO, "tests", "golden", "bridge_task1_im_0.jpg"), "rb") as fh:
+        pixels = pillow_decode([fh.read()])
+    rows.append(restart_row("fixture bridge_task1_im_0.jpg's pixels re-encoded at quality 75 x 1 (a request's image)", export.encode_jpeg(pixels, quality=75),
+                            export.encode_jpeg(pixels, quality=75, restart_rows=a.restart_rows), a.iters))
+    import PIL
+    res = dict(tool="jpeg_decode_bench --restart-rows", restart_rows=a.restart_rows, device=torch.cuda.get_device_name(0), cpu_threads=torch.get_num_threads(),
+               pillow=PIL.__version__, iters=a.iters, rows=rows,
+               says="a record, not a gate; medians of --iters in one process after a warm-up; `plain` and `marked` are the same frames written without and "
+                    "with restart markers; entropy_us is unstuffing + entropy decode + DC sums by device events, decode_jpeg_ms the whole call by the host "
+                    "clock; Pillow (libjpeg-turbo) runs on this machine's CPU, one thread, and its time includes the upload of the raw pixels")
+    merge_out(a.out, "decode", res)
+    print(json.dumps(res))
+
+
+def merge_out(path, key, res):
+    """profiles/jpeg_restart_bench.json holds the decoder's and the encoder's record side by side: replace one, keep the other"""
+    both = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            both = json.load(f)
+    both[key] = res
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(both, f, indent=1)
+        f.write("\n")
+
+
 def row_of(name, files, iters, passes):
     from tests import jpeg_decode_reference as dec
     from this_and_that_vdm_amd import _lib, ingest, ops
@@ -111,10 +189,14 @@ def main():
     ap.add_argument("--passes", action="store_true", help="count frame 0's passes with the CPU emulation (slow: minutes for the large frames)")
     ap.add_argument("--variant", action="append", default=[], metavar="S=PATH", help="a library built with another TT_JPEG_SUBSEQ_BITS")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "jpeg_decode_bench.json"))
+    ap.add_argument("--restart-rows", type=int, default=0, metavar="N", help="compare files written with restart_rows=N against the marker-less ones")
+    ap.add_argument("--out", default=None, help="default profiles/jpeg_decode_bench.json; with --restart-rows profiles/jpeg_restart_bench.json")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(REPO, "profiles", "jpeg_restart_bench.json" if a.restart_rows else "jpeg_decode_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_decode_bench: needs a GPU (there is no CPU fallback)")
+    if a.restart_rows:
+        return restart_main(a)
     from tests import png_reference as ref
     from this_and_that_vdm_amd import export
     rows = []

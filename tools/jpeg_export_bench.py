@@ -13,6 +13,11 @@ defaults --, so both sides write the same bytes (checked once per size).
                         readback_ms (lengths, then the packed scans), files_ms (headers joined to the scans), file_write_ms: host clock
   bytes                 the 14 files' sizes (JPEG, optimized JPEG, Pillow's JPEG, this library's PNG) and what crosses to the host
 
+  --restart-rows N      instead: export.write_jpegs from the device frames without markers and with ``restart_rows=N`` in ONE process, the
+                        scan kernels of both by device events, and the files' sizes: the overhead is exact (DRI 6 bytes a file; per marker 2
+                        bytes, the pad to a byte, a stuffed pad now and then, and the DC differences that start again from 0).  The result
+                        goes under "encode" of profiles/jpeg_restart_bench.json (tools/jpeg_decode_bench.py fills "decode").
+
 A record, not a gate.  Prints one JSON line and writes it to --out (default profiles/jpeg_export_bench.json)."""
 import argparse
 import json
@@ -99,13 +104,48 @@ def stages(dev, folder, iters):
     return {k: round(v, 3) for k, v in out.items()}, int(lens.sum()) + 4 * n
 
 
+def restart_main(a):
+    from tests import png_reference as ref
+    from this_and_that_vdm_amd import export, ops
+    from tools.jpeg_decode_bench import merge_out
+    rows = []
+    tables = torch.from_numpy(np.stack([t.codes for t in export.jpeg_standard_tables()]).view(np.int32)[None]).cuda()
+    for n, h, w in SIZES:
+        dev = torch.from_numpy(np.stack([ref.generator_frame(h, w, f) for f in range(n)], 0)).cuda()
+        ri = a.restart_rows * ((w + 15) // 16)
+        coeffs, _ = ops.jpeg_coeffs(dev, 75, "4:2:0", counts=False)
+        with tempfile.TemporaryDirectory() as folder:
+            export.write_jpegs(dev, folder)                    # warm-up: library load, first launches
+            export.write_jpegs(dev, folder, restart_rows=a.restart_rows)
+            row = dict(frames=[n, h, w, 3], restart_interval=ri, markers_per_frame=((h + 15) // 16 * ((w + 15) // 16) + ri - 1) // ri - 1)
+            for name, kw in (("plain", {}), ("marked", dict(restart_rows=a.restart_rows))):
+                sizes = [len(d) for d in export.encode_jpeg(dev, **kw)]
+                row[name] = dict(write_jpegs_dev_ms=round(wall_ms(lambda: export.write_jpegs(dev, folder, **kw), a.iters), 2),
+                                 scan_kernels_us=round(events_us(lambda: ops.jpeg_scan(coeffs, (h, w, 3), "4:2:0", tables, restart_interval=ri if kw else 0), a.iters), 1),
+                                 file_bytes=int(sum(sizes)))
+            row["extra_bytes"] = row["marked"]["file_bytes"] - row["plain"]["file_bytes"]
+            row["extra_bytes_per_marker"] = round((row["extra_bytes"] - 6 * n) / max(1, n * row["markers_per_frame"]), 2)
+            row["slower"] = bool(row["marked"]["write_jpegs_dev_ms"] > row["plain"]["write_jpegs_dev_ms"])
+        rows.append(row)
+    res = dict(tool="jpeg_export_bench --restart-rows", restart_rows=a.restart_rows, device=torch.cuda.get_device_name(0), iters=a.iters,
+               inputs="the generator of tests/png_reference.py, seeds 0 .. 13; quality 75, 4:2:0, standard tables", rows=rows,
+               says="a record, not a gate; medians of --iters in one process after a warm-up; kernel times are device events, the rest the host clock; "
+                    "files go to a temporary folder; the sizes are exact")
+    merge_out(a.out, "encode", res)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "jpeg_export_bench.json"))
+    ap.add_argument("--restart-rows", type=int, default=0, metavar="N", help="compare write_jpegs(restart_rows=N) against the marker-less call")
+    ap.add_argument("--out", default=None, help="default profiles/jpeg_export_bench.json; with --restart-rows profiles/jpeg_restart_bench.json")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(REPO, "profiles", "jpeg_restart_bench.json" if a.restart_rows else "jpeg_export_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_export_bench: needs a GPU (there is no CPU fallback)")
+    if a.restart_rows:
+        return restart_main(a)
     from tests import png_reference as ref
     from this_and_that_vdm_amd import _lib, export
     rows = []
