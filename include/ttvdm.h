@@ -1287,6 +1287,116 @@ int tt_jpeg_entropy_spans(const uint8_t* scans, int64_t scans_bytes, const int64
                           int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs, uint32_t* status, void* ws,
                           int64_t ws_bytes, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GIF import: an animated GIF decoded on the device to uint8 [F, H, W, 3] RGB frames, each the canvas a viewer shows after drawing
+ * that frame (this_and_that_vdm_amd/ingest.py drives it: decode_gif / read_gif).  Only the compressed bytes cross to the device.  One
+ * host routine (tt_gif_parse; plain C++, it touches no device), two device entry points (tt_gif_decode_indices, tt_gif_compose) and one
+ * size query.  Integers only: the same bytes on every call and every stream.  Additive: the ABI version is unchanged.
+ *
+ * 1. Container -- tt_gif_parse (host).  GIF87a and GIF89a.  The logical screen W x H, the global colour table and the background
+ *    index; per image its rectangle (left, top, w, h), the interlace flag, its local colour table, and from the graphic control
+ *    extension before it the transparent index (-1: none), the disposal bits 0 .. 7 and the delay in 1/100 s (an image without one: -1,
+ *    0, 0); the loop count of the NETSCAPE2.0 block (-1: no such block).  Comment, plain-text and other application extensions are
+ *    skipped.  An image's data sub-blocks (any length 1 .. 255 each) are walked here and their payload is copied contiguously into
+ *    `upload`: frame f's LZW bytes are upload[data_offset, data_offset + data_bytes).  A frame's palette is its local table, else the
+ *    global one, padded with zeros to 256 entries.  A missing trailer behind a complete image is accepted.
+ *    Two calls, as tt_jpeg_parse_spans: frames == NULL and upload == NULL count (header->frames, header->data_bytes); else
+ *    frame_cap >= header->frames entries and upload_cap >= header->data_bytes bytes are filled, and nothing beyond either is written.
+ *    TT_EINVAL, the text names the cause and the frame: null data / header; size <= 0; a bad signature ("signature"); a file that
+ *    ends inside a header, table, extension or sub-block ("ends inside"); no image at all ("no image"); a rectangle of zero size ("zero
+ *    size") or one that leaves the logical screen ("leaves the logical screen"; Pillow grows the canvas, this library refuses); an
+ *    image with neither a local nor a global table ("no colour table"); a minimum code size outside 2 .. 8 ("minimum code size"); an
+ *    unknown block ("unknown block"); frames without upload or the reverse ("go together"); frame_cap or upload_cap too small.
+ *    TT_EUNSUPPORTED: more than 65 535 frames; a frame with 2^29 data bytes or more; a canvas above TT_GIF_MAX_PIXELS.
+ *    Every loop of the parser advances through the file: its trips are bounded by the file's size.
+ * 2. LZW (device).  A frame's stream starts with an empty table whether or not its first code is a clear code.  With C = 2^mcs (the
+ *    clear code), C + 1 (end of information) and E0 = C + 2, between two clear codes:
+ *    a. the code at place r (0, 1, ... behind the clear code) is min(12, bit length of C + 1 + r) bits wide ("GIF LZW on the device",
+ *       rule 4) -- 12 once the table is full; codes are packed from the least significant bit;
+ *    b. it is valid if it is below C (a pixel), or if it is E0 + k with k <= min(r - 1, 4095 - E0); k = r - 1 names the entry being
+ *       made; the code at place 0 must be below C.  An INVALID code is read as the pixel 0;
+ *    c. entry E0 + k is the string of the code at place k plus the first pixel of the string at place k + 1; it is made only while
+ *       E0 + k <= 4095.  Behind a full table the codes stay 12 bits wide and make no entries (deferred clear) until a clear code comes;
+ *    d. the stream ends at the end-of-information code, at the first code that does not lie whole inside the data, or at the end of
+ *       the data.  Pixels beyond w h are ignored; pixels the stream does not reach are index 0.
+ * 3. Status, one word per frame, each bit marks only its own frame: TT_GIF_DEC_STATUS_CODE: an invalid code whose string would start
+ *    before pixel w h; TT_GIF_DEC_STATUS_SHORT: fewer than w h pixels; TT_GIF_DEC_STATUS_SPAN: an offset, length, pixel count or map
+ *    offset outside the uploaded bytes or the index maps (the frame is taken as empty and nothing of it is written).
+ * 4. Interlace: the rows of an interlaced image arrive in the four passes 0, 8, ... / 4, 12, ... / 2, 6, ... / 1, 3, ... and go to their
+ *    real rows; the index maps are in raster order.
+ * 5. Composition.  The canvas before frame 0 is, everywhere, frame 0's palette entry at frame 0's transparent index, entry 0 if it has
+ *    none.  Before frame f >= 1 is drawn, the disposal of frame f - 1 is applied to frame f - 1's rectangle: 2: filled with B(f - 1),
+ *    frame f - 1's palette at its transparent index if it has one, else at the logical screen's background index; 3: what the rectangle
+ *    held before frame f - 1 was drawn is put back; any other value: left.  Drawing: every pixel of the rectangle whose index is not
+ *    the frame's transparent index becomes the frame's palette entry.  Frame f of the output is the canvas after frame f is drawn.
+ *    This equals Pillow (Image.open, seek(f), convert("RGB")) except in two patterns where Pillow departs from GIF89a, and the library
+ *    follows the rule above in both: (a) frame 0 has disposal 3 and no transparent index: Pillow leaves frame 0 in place; (b) a frame
+ *    has disposal 0 and the nearest earlier frame with non-zero bits has 2 or 3: Pillow keeps applying the earlier method.
+ *
+ * tt_gif_decode_indices: data (device, data_bytes of them) holds frame f's LZW bytes at offsets[f] (int64) with lengths[f] bytes; npix[f]
+ * = w h; min_code_size[f]; rows[f] = the image's height when it is interlaced, else 0; map_offsets[f] (int64): where in maps (device,
+ * maps_bytes of them) the frame's w h indices go -- all device arrays of n entries -> maps and status [n].  Values the arrays hold
+ * are clamped or checked by the kernels: whatever they and the data hold, nothing is written outside maps, status and ws.  A memset of
+ * maps and of status, then four launches; no workgroup waits on another, no readback sizes a grid, and every loop's trip count is
+ * bounded before it starts (by the data length, the segment's code count, 4096, 12 or n):
+ *   clears  -- grid (n), one workgroup per frame follows the chain of clear codes: from a clear code the place of every later code is a
+ *              closed form (rule 2a), so the lanes extract a batch of codes a round and take the first clear code, end code or end of
+ *              data; the SEGMENT between two clear codes (its first bit, its code count) is recorded when it holds a code;
+ *   lengths -- workgroups stride over a frame's segments through the device-side count.  Per segment: parent(r) = code - E0 for the
+ *              places r < 4096; a binary-lifting table of 12 levels x 4096 x 2 bytes = 96 KiB in LDS, built in 11 doubling rounds; from
+ *              it every place's string length and first pixel in 12 lookups; then the length of every code of the segment, summed;
+ *   offsets -- grid (n): a scan over the frame's segments gives each its first pixel (clipped to w h), sets SHORT, and cuts the
+ *              segments' pixels into chunks of TT_GIF_DEC_CHUNK for the last launch;
+ *   pixels  -- workgroups stride over a frame's chunks.  The segment's tables are rebuilt as above; its codes are walked in tiles of
+ *              1024 with a scan of their lengths; every lane takes a pixel of the chunk, finds its code by a binary search of the tile
+ *              (10 steps) and the pixel by walking depth - place ancestors up in at most 12 lookups: the dependent work per pixel does
+ *              not grow with its string's length.  The index is stored at its raster (rule 4) place, guarded by w h.
+ * The workspace is a derived bound: a segment that holds a code costs its closing code too, at least 2 (mcs + 1) >= 6 bits, so a frame
+ * of b bytes has at most 8 b / 6 + 1 of them; tt_gif_decode_ws_bytes(n, data_bytes) holds 8 data_bytes / 6 + n segment records and n
+ * frame records (0 for arguments the entry point refuses).
+ * TT_EINVAL: a null pointer; n <= 0, data_bytes <= 0 or maps_bytes <= 0; offsets or map_offsets off an 8-byte, the other arrays and
+ * status off a 4-byte, ws off a 16-byte boundary; ws_bytes too small ("ws too small").  TT_EUNSUPPORTED: more than 65 535 frames;
+ * data_bytes of 2^29 or more (bit offsets are 32-bit); maps_bytes of 2^31 or more.
+ *
+ * tt_gif_compose: maps as above, table [n] TtGifComposeFrame and palettes [n][256][3] on the device, the initial colour 0x00BBGGRR ->
+ * out uint8 [n, height, width, 3].  One launch, one lane per canvas pixel: it walks f = 0 .. n - 1 with the running colour and the
+ * colour saved before the last draw (rule 5), reads each frame's map once and writes each output byte once.  A table entry whose
+ * rectangle leaves the canvas or whose map leaves maps draws nothing.  TT_EINVAL: a null pointer; n, width, height or maps_bytes <= 0;
+ * table off an 8-byte boundary.  TT_EUNSUPPORTED: more than 65 535 frames; a canvas above TT_GIF_MAX_PIXELS.
+ * Every entry point refuses before the first HIP call; no allocation, no synchronisation. */
+#define TT_GIF_DEC_STATUS_CODE 1u
+#define TT_GIF_DEC_STATUS_SHORT 2u
+#define TT_GIF_DEC_STATUS_SPAN 4u
+#define TT_GIF_DEC_CHUNK 16384
+#define TT_GIF_MAX_FRAMES 65535
+typedef struct TtGifHeader {
+  int32_t width, height, background, loop;         /* loop: -1 without a NETSCAPE2.0 block */
+  int32_t global_colors, frames, version;           /* version: 87 or 89 */
+  int32_t reserved;
+  int64_t data_bytes;                               /* the LZW bytes of all frames, end to end */
+} TtGifHeader;
+typedef struct TtGifFrame {
+  int32_t left, top, w, h;
+  int32_t interlace, transparent, disposal, delay;  /* transparent: -1 for none; delay in 1/100 s */
+  int32_t min_code_size, local_colors;              /* local_colors: 0 when the frame uses the global table */
+  int64_t data_offset, data_bytes;                  /* in upload */
+  uint8_t palette[256][3];
+} TtGifFrame;
+typedef struct TtGifComposeFrame {
+  int32_t left, top, w, h, transparent, disposal;   /* transparent: -1 for none */
+  uint32_t fill;                                     /* B of rule 5, 0x00BBGGRR */
+  int32_t reserved;
+  int64_t map_offset;
+} TtGifComposeFrame;
+int tt_gif_parse(const uint8_t* data /* host */, int64_t size, TtGifHeader* header /* host */, TtGifFrame* frames /* host [frame_cap] or NULL */,
+                 int64_t frame_cap, uint8_t* upload /* host [upload_cap] or NULL */, int64_t upload_cap);
+int64_t tt_gif_decode_ws_bytes(int32_t n, int64_t data_bytes);
+int tt_gif_decode_indices(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const uint32_t* lengths, const uint32_t* npix,
+                          const int32_t* min_code_size, const int32_t* rows, const int64_t* map_offsets, int32_t n, uint8_t* maps,
+                          int64_t maps_bytes, uint32_t* status, void* ws, int64_t ws_bytes, tt_stream_t stream);
+int tt_gif_compose(const uint8_t* maps, int64_t maps_bytes, const TtGifComposeFrame* table, const uint8_t* palettes, int32_t n, int32_t height,
+                   int32_t width, uint32_t initial, uint8_t* out, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

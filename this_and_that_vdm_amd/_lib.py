@@ -114,6 +114,30 @@ TT_JPEG_STATUS = {1: "a marker inside the scan", 2: "an invalid Huffman code", 4
                   16: "a scan outside the buffer"}
 
 
+TT_GIF_DEC_STATUS = {1: "an invalid LZW code", 2: "fewer pixels than the rectangle holds", 4: "a data span or an index map outside the buffers"}
+TT_GIF_DEC_CHUNK, TT_GIF_MAX_FRAMES, TT_GIF_MAX_PIXELS = 16384, 65535, 16843009
+
+
+class TtGifHeader(C.Structure):
+    """What tt_gif_parse reads of the logical screen: the field order of include/ttvdm.h."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("background", C.c_int32), ("loop", C.c_int32),
+                ("global_colors", C.c_int32), ("frames", C.c_int32), ("version", C.c_int32), ("reserved", C.c_int32), ("data_bytes", C.c_int64)]
+
+
+class TtGifFrame(C.Structure):
+    """One image of a GIF file as tt_gif_parse reads it (824 bytes): the field order of include/ttvdm.h."""
+    _fields_ = [("left", C.c_int32), ("top", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("interlace", C.c_int32), ("transparent", C.c_int32), ("disposal", C.c_int32), ("delay", C.c_int32),
+                ("min_code_size", C.c_int32), ("local_colors", C.c_int32), ("data_offset", C.c_int64), ("data_bytes", C.c_int64),
+                ("palette", (C.c_uint8 * 3) * 256)]
+
+
+class TtGifComposeFrame(C.Structure):
+    """One row of tt_gif_compose's device table (40 bytes): the field order of include/ttvdm.h."""
+    _fields_ = [("left", C.c_int32), ("top", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("transparent", C.c_int32), ("disposal", C.c_int32),
+                ("fill", C.c_uint32), ("reserved", C.c_int32), ("map_offset", C.c_int64)]
+
+
 class TtJpegHeader(C.Structure):
     """What tt_jpeg_parse reads from one baseline JPEG file: the field order of include/ttvdm.h."""
     _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("ch", C.c_int32), ("subsampling", C.c_int32),
@@ -248,6 +272,11 @@ SIGNATURES = {
     # ... with restart intervals: the scan's spans on the host, one workgroup per span on the device (additive as well)
     "tt_jpeg_parse_spans": (C.c_int, [_vp, _i64, C.POINTER(TtJpegHeader), C.POINTER(C.c_int32), _vp, _vp, _i64, C.POINTER(C.c_int64)]),
     "tt_jpeg_entropy_spans": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    # the GIF import: the container on the host, LZW, interlace and composition on the device (additive as well)
+    "tt_gif_parse": (C.c_int, [_vp, _i64, C.POINTER(TtGifHeader), _vp, _i64, _vp, _i64]),
+    "tt_gif_decode_ws_bytes": (_i64, [_i32, _i64]),
+    "tt_gif_decode_indices": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tt_gif_compose": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, C.c_uint32, _vp, _vp]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 // libttvdm: the host half of the GIF export -- tt_palette_median_cut (a median cut over the occupied bins of one colour histogram) and
-// tt_gif_lzw (the image data of one GIF frame).  include/ttvdm.h states both rule by rule; integers only.
+// tt_gif_lzw (the image data of one GIF frame) -- and of the GIF import: tt_gif_parse (the container).  include/ttvdm.h states all three
+// rule by rule; integers only.
 #include "gif_host.h"
 
 #include <string.h>
@@ -182,5 +183,141 @@ extern "C" int tt_gif_lzw(const uint8_t* indices, int64_t npix, int32_t min_code
   sink.finish();
   if (sink.full) TT_FAIL(TT_EINVAL, "tt_gif_lzw: cap = %lld bytes is too small (tt_gif_lzw_bound: %lld)", (long long)cap, (long long)tt_gif_lzw_bound(npix));
   *nbytes_out = sink.pos;
+  return TT_OK;
+}
+
+// ---- the GIF import's container (include/ttvdm.h, "GIF import", rule 1).  `at` only ever grows, so every loop ends with the file.
+namespace {
+
+struct Reader {
+  const uint8_t* p;
+  int64_t size, at = 0;
+  bool has(int64_t n) const { return n >= 0 && n <= size - at; }
+  uint8_t u8() { return p[at++]; }
+  int u16() { const int v = p[at] | (p[at + 1] << 8); at += 2; return v; }
+};
+
+// skips a chain of sub-blocks behind `r.at`; false when the file ends inside it
+bool skip_blocks(Reader& r) {
+  for (;;) {
+    if (!r.has(1)) return false;
+    const int n = r.u8();
+    if (n == 0) return true;
+    if (!r.has(n)) return false;
+    r.at += n;
+  }
+}
+
+}  // namespace
+
+extern "C" int tt_gif_parse(const uint8_t* data, int64_t size, TtGifHeader* header, TtGifFrame* frames, int64_t frame_cap, uint8_t* upload,
+                            int64_t upload_cap) {
+  if (!data || !header) TT_FAIL(TT_EINVAL, "tt_gif_parse: null %s", !data ? "data" : "header");
+  if (size <= 0) TT_FAIL(TT_EINVAL, "tt_gif_parse: size = %lld", (long long)size);
+  if ((frames == nullptr) != (upload == nullptr)) TT_FAIL(TT_EINVAL, "tt_gif_parse: frames and upload go together (both, or neither to count)");
+  if (frames && (frame_cap < 0 || upload_cap < 0)) TT_FAIL(TT_EINVAL, "tt_gif_parse: frame_cap = %lld, upload_cap = %lld", (long long)frame_cap, (long long)upload_cap);
+  Reader r{data, size};
+  if (!r.has(6)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside the signature (%lld bytes)", (long long)size);
+  if (memcmp(data, "GIF87a", 6) != 0 && memcmp(data, "GIF89a", 6) != 0) TT_FAIL(TT_EINVAL, "tt_gif_parse: bad signature (neither GIF87a nor GIF89a)");
+  r.at = 6;
+  TtGifHeader hd = {};
+  hd.version = data[4] == '7' ? 87 : 89;
+  hd.loop = -1;
+  if (!r.has(7)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside the logical screen descriptor");
+  hd.width = r.u16();
+  hd.height = r.u16();
+  const int packed = r.u8();
+  hd.background = r.u8();
+  r.u8();                                                          // the pixel aspect ratio
+  uint8_t global[256][3];
+  memset(global, 0, sizeof global);
+  if (packed & 0x80) {
+    hd.global_colors = 2 << (packed & 7);
+    if (!r.has(3 * hd.global_colors)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside the global colour table");
+    memcpy(global, data + r.at, (size_t)(3 * hd.global_colors));
+    r.at += 3 * hd.global_colors;
+  }
+  if ((int64_t)hd.width * hd.height > TT_GIF_MAX_PIXELS)
+    TT_FAIL(TT_EUNSUPPORTED, "tt_gif_parse: a canvas of %d x %d pixels (at most TT_GIF_MAX_PIXELS = %d)", hd.width, hd.height, TT_GIF_MAX_PIXELS);
+  int transparent = -1, disposal = 0, delay = 0;                    // of the graphic control extension before the next image
+  int64_t nframes = 0, nbytes = 0;
+  while (r.has(1)) {
+    const int block = r.u8();
+    if (block == 0x3b) break;                                       // the trailer
+    if (block == 0x21) {
+      if (!r.has(1)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside an extension (before frame %lld)", (long long)nframes);
+      const int label = r.u8();
+      if (label == 0xf9 && r.has(6) && data[r.at] == 4) {           // graphic control: size 4, packed, delay, transparent index
+        const int gp = data[r.at + 1];
+        disposal = (gp >> 2) & 7;
+        delay = data[r.at + 2] | (data[r.at + 3] << 8);
+        transparent = (gp & 1) ? data[r.at + 4] : -1;
+      } else if (label == 0xff && r.has(17) && data[r.at] == 11 && memcmp(data + r.at + 1, "NETSCAPE2.0", 11) == 0 && data[r.at + 12] == 3 &&
+                 data[r.at + 13] == 1) {
+        hd.loop = data[r.at + 14] | (data[r.at + 15] << 8);
+      }
+      if (!skip_blocks(r)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside an extension's sub-block (before frame %lld)", (long long)nframes);
+      continue;
+    }
+    if (block != 0x2c) {
+      if (nframes > 0) break;                                       // bytes behind a complete image: taken as a missing trailer
+      TT_FAIL(TT_EINVAL, "tt_gif_parse: unknown block 0x%02x at byte %lld", block, (long long)(r.at - 1));
+    }
+    const long long f = (long long)nframes;
+    if (nframes >= TT_GIF_MAX_FRAMES) TT_FAIL(TT_EUNSUPPORTED, "tt_gif_parse: more than %d frames", TT_GIF_MAX_FRAMES);
+    if (!r.has(9)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside the image descriptor of frame %lld", f);
+    TtGifFrame fr = {};
+    fr.left = r.u16();
+    fr.top = r.u16();
+    fr.w = r.u16();
+    fr.h = r.u16();
+    const int ip = r.u8();
+    fr.interlace = (ip >> 6) & 1;
+    fr.transparent = transparent;
+    fr.disposal = disposal;
+    fr.delay = delay;
+    transparent = -1, disposal = 0, delay = 0;
+    if (fr.w == 0 || fr.h == 0) TT_FAIL(TT_EINVAL, "tt_gif_parse: frame %lld has a rectangle of zero size (%d x %d)", f, fr.w, fr.h);
+    if (fr.left + fr.w > hd.width || fr.top + fr.h > hd.height)
+      TT_FAIL(TT_EINVAL, "tt_gif_parse: frame %lld's rectangle (%d, %d, %d x %d) leaves the logical screen of %d x %d", f, fr.left, fr.top, fr.w, fr.h, hd.width,
+              hd.height);
+    const uint8_t* table = &global[0][0];
+    int colors = hd.global_colors;
+    if (ip & 0x80) {
+      fr.local_colors = colors = 2 << (ip & 7);
+      if (!r.has(3 * colors)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside the local colour table of frame %lld", f);
+      table = data + r.at;
+      r.at += 3 * colors;
+    }
+    if (colors == 0) TT_FAIL(TT_EINVAL, "tt_gif_parse: frame %lld has no colour table, neither a local nor a global one", f);
+    if (!r.has(1)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside the image data of frame %lld", f);
+    fr.min_code_size = r.u8();
+    if (fr.min_code_size < 2 || fr.min_code_size > 8) TT_FAIL(TT_EINVAL, "tt_gif_parse: frame %lld has a minimum code size of %d (2 to 8)", f, fr.min_code_size);
+    fr.data_offset = nbytes;
+    for (;;) {
+      if (!r.has(1)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside the image data of frame %lld (no block terminator)", f);
+      const int n = r.u8();
+      if (n == 0) break;
+      if (!r.has(n)) TT_FAIL(TT_EINVAL, "tt_gif_parse: the file ends inside a sub-block of frame %lld", f);
+      if (upload) {
+        if (nbytes + n > upload_cap) TT_FAIL(TT_EINVAL, "tt_gif_parse: upload_cap too small: %lld bytes", (long long)upload_cap);
+        memcpy(upload + nbytes, data + r.at, (size_t)n);
+      }
+      nbytes += n;
+      r.at += n;
+    }
+    fr.data_bytes = nbytes - fr.data_offset;
+    if (fr.data_bytes >= (1ll << 29)) TT_FAIL(TT_EUNSUPPORTED, "tt_gif_parse: frame %lld has %lld data bytes (fewer than 2^29 = 536870912)", f, (long long)fr.data_bytes);
+    if (frames) {
+      if (nframes >= frame_cap) TT_FAIL(TT_EINVAL, "tt_gif_parse: frame_cap too small: %lld", (long long)frame_cap);
+      memcpy(fr.palette, table, (size_t)(3 * colors));              // the rest of the 256 entries stays zero
+      frames[nframes] = fr;
+    }
+    ++nframes;
+  }
+  if (nframes == 0) TT_FAIL(TT_EINVAL, "tt_gif_parse: no image at all in %lld bytes", (long long)size);
+  hd.frames = (int32_t)nframes;
+  hd.data_bytes = nbytes;
+  *header = hd;
   return TT_OK;
 }

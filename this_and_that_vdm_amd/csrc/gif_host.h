@@ -1,5 +1,6 @@
-// The host half of the GIF export (gif_host.cpp): plain C++17, no HIP include -- it also compiles on its own with any host compiler
-// (together with lib.cpp, which holds tt_set_error), which is how tests/test_gif_export_cpu.py builds it under the sanitizers.
+// The host half of the GIF export and import (gif_host.cpp): plain C++17, no HIP include -- it also compiles on its own with any host
+// compiler (together with lib.cpp, which holds tt_set_error), which is how tests/test_gif_export_cpu.py and tests/test_gif_decode_cpu.py
+// build it under the sanitizers.
 #pragma once
 #include "ttvdm.h"
 #include "host_common.h"

@@ -9,7 +9,11 @@ the spans between its markers, and the entropy decoder gives every span a workgr
 without them is one span and decodes through the same launches as before; the reference dataset's own im_0.jpg files carry none.
 
 Not applied: EXIF orientation (``load_image`` of the reference applies it; rotate the result when the files carry one).  Refused by
-name: progressive, arithmetic and 12-bit files, several scans, 4:2:2, CMYK / Adobe files, restart markers out of order or count."""
+name: progressive, arithmetic and 12-bit files, several scans, 4:2:2, CMYK / Adobe files, restart markers out of order or count.
+
+Animated GIFs (include/ttvdm.h, "GIF import"): ``decode_gif`` / ``read_gif`` turn the file ``export.write_gif`` (or Pillow, or imageio)
+wrote into uint8 [F, H, W, 3] on the device, per frame the canvas Pillow shows after ``seek(f)``.  The host walks the container
+(tt_gif_parse); the LZW streams, the interlace and the composition run on the device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -194,3 +198,106 @@ def read_mjpeg_video(path, device="cuda") -> torch.Tensor:
     """The frames of a Motion-JPEG AVI (``export.write_mjpeg``'s) decoded by ``decode_jpeg``."""
     from . import export
     return decode_jpeg(export.read_mjpeg_frames(path), device)
+
+
+# ---- animated GIFs (include/ttvdm.h, "GIF import"): the container on the host, LZW, interlace and composition on the device
+@dataclass
+class GifHeader:
+    """What ``parse_gif`` reads from one file: the logical screen (``height``, ``width``, ``background`` index), ``loop`` (the NETSCAPE2.0
+    count, 0 for ever; None without the block), and per frame ``rectangles`` int32 [F, 4] (left, top, w, h), ``durations`` (seconds),
+    ``disposal`` (bits 0 .. 7), ``transparent`` (index, -1 for none), ``interlace``, ``min_code_size``, ``palettes`` uint8 [F, 256, 3] (the
+    local table, else the global one, zero-padded), ``local`` (the frame has a table of its own), and ``spans`` int64 [F, 2]: where the
+    frame's LZW bytes lie in ``data`` (the sub-blocks' payload of all frames, end to end) and how many they are."""
+    height: int
+    width: int
+    background: int
+    loop: object
+    version: int
+    rectangles: np.ndarray
+    durations: list
+    disposal: list
+    transparent: list
+    interlace: list
+    min_code_size: list
+    palettes: np.ndarray
+    local: list
+    spans: np.ndarray
+    data: np.ndarray
+
+    @property
+    def frames(self) -> int:
+        return len(self.disposal)
+
+
+def parse_gif(data: bytes) -> GifHeader:
+    """One GIF87a / GIF89a file -> its header, its frames' tables and their LZW bytes (tt_gif_parse: once to count, once to take them);
+    ValueError with the library's text, which names the cause and the frame, for what is refused."""
+    lib = _lib.load()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    at = buf.ctypes.data if buf.size else None
+    hd = _lib.TtGifHeader()
+    rc = lib.tt_gif_parse(at, buf.size, C.byref(hd), None, 0, None, 0)
+    if rc == 0:
+        frames = (_lib.TtGifFrame * hd.frames)()
+        upload = np.zeros(max(hd.data_bytes, 1), dtype=np.uint8)
+        rc = lib.tt_gif_parse(at, buf.size, C.byref(hd), C.cast(frames, C.c_void_p), hd.frames, upload.ctypes.data, hd.data_bytes)
+    if rc != 0:
+        raise ValueError(lib.tt_last_error().decode(errors="replace"))
+    rec = np.frombuffer(frames, dtype=np.uint8).reshape(hd.frames, C.sizeof(_lib.TtGifFrame))
+    ints = rec[:, :40].copy().view(np.int32)                                                       # left .. local_colors
+    spans = rec[:, 40:56].copy().view(np.int64)
+    return GifHeader(hd.height, hd.width, hd.background, None if hd.loop < 0 else hd.loop, hd.version, ints[:, 0:4].copy(),
+                     [v / 100.0 for v in ints[:, 7].tolist()], ints[:, 6].tolist(), ints[:, 5].tolist(), [bool(v) for v in ints[:, 4].tolist()],
+                     ints[:, 8].tolist(), rec[:, 56:].reshape(hd.frames, 256, 3).copy(), [bool(v) for v in ints[:, 9].tolist()], spans,
+                     upload[:hd.data_bytes])
+
+
+def decode_gif(file, device, info: bool = False):
+    """One GIF file -- bytes or a path -- -> uint8 [F, H, W, 3] on ``device``: per frame the canvas after it is drawn, byte for byte
+    what Pillow's ``seek(f)`` + ``convert("RGB")`` holds (outside Pillow's two departures from GIF89a that include/ttvdm.h names).  One
+    upload of the compressed bytes, a small upload of the tables, one readback (a status word per frame).  ``info=True``: also the
+    ``GifHeader``.  ValueError: a file the parser refuses (its text names the cause and the frame), a frame whose LZW stream is corrupt
+    or short (the frame is named), a ``device`` that is not the HIP device."""
+    from . import ops
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"decode_gif: decodes on the HIP device, got {device} (there is no CPU fallback)")
+    try:
+        hd = parse_gif(_read(file))
+    except ValueError as e:
+        raise ValueError(f"decode_gif: {e}") from None
+    n = hd.frames
+    if hd.data.size < 1:
+        raise ValueError("decode_gif: frame 0 is corrupt or short (no image data at all)")
+    rect = hd.rectangles.astype(np.int64)
+    npix = rect[:, 2] * rect[:, 3]
+    map_offsets = np.concatenate([[0], np.cumsum(npix)[:-1]]).astype(np.int64)
+    rows = np.where(np.array(hd.interlace), rect[:, 3], 0)
+    cols = np.stack([hd.spans[:, 0], map_offsets, hd.spans[:, 1], npix, np.array(hd.min_code_size, dtype=np.int64), rows]).astype(np.int64)
+    # rule 5: the fill colour of disposal 2 and the canvas before frame 0
+    pal = hd.palettes.astype(np.uint32)
+    packed = pal[:, :, 0] | (pal[:, :, 1] << 8) | (pal[:, :, 2] << 16)
+    table = (_lib.TtGifComposeFrame * n)()
+    for f in range(n):
+        t = hd.transparent[f]
+        table[f] = _lib.TtGifComposeFrame(*hd.rectangles[f].tolist(), t, hd.disposal[f], int(packed[f, t if t >= 0 else hd.background]), 0, int(map_offsets[f]))
+    initial = int(packed[0, hd.transparent[0] if hd.transparent[0] >= 0 else 0])
+    blob = np.concatenate([cols.view(np.uint8).reshape(-1), np.frombuffer(table, dtype=np.uint8), hd.palettes.reshape(-1)])      # the tables: one upload
+    data = torch.from_numpy(hd.data.copy()).to(device)
+    small = torch.from_numpy(blob).to(device)
+    words = small[:cols.size * 8].view(torch.int64).view(6, n)
+    at = cols.size * 8
+    rowsize = C.sizeof(_lib.TtGifComposeFrame)
+    maps, status = ops.gif_indices(data, words[0].contiguous(), words[2].to(torch.int32), words[3].to(torch.int32), words[4].to(torch.int32),
+                                   words[5].to(torch.int32), words[1].contiguous(), int(npix.sum()))
+    frames = ops.gif_compose(maps, small[at:at + n * rowsize].view(n, rowsize), small[at + n * rowsize:].view(n, 256, 3), (hd.height, hd.width), initial)
+    for i, s in enumerate(status.cpu().tolist()):
+        if s:
+            why = ", ".join(text for bit, text in _lib.TT_GIF_DEC_STATUS.items() if s & bit)
+            raise ValueError(f"decode_gif: frame {i} is corrupt or short ({why}; status {s})")
+    return (frames, hd) if info else frames
+
+
+def read_gif(path, device="cuda") -> torch.Tensor:
+    """The frames of a GIF file (``export.write_gif``'s, Pillow's, imageio's) decoded by ``decode_gif``."""
+    return decode_gif(path, device)

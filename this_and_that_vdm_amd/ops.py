@@ -1452,3 +1452,59 @@ def jpeg_pixels(coeffs: torch.Tensor, shape, subsampling, quant: torch.Tensor) -
     check(lib.tt_jpeg_pixels(_p(coeffs), n, h, w, ch, sub, _p(quant), quant.shape[0], _p(frames), _stream()), "tt_jpeg_pixels")
     _wrote(frames, "jpeg_pixels")
     return frames
+
+
+# ---- the GIF import's device half (tt_gif_decode_indices / tt_gif_compose; ingest.py parses the file and builds the tables)
+def gif_indices(data: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, npix: torch.Tensor, min_code_size: torch.Tensor, rows: torch.Tensor,
+                map_offsets: torch.Tensor, maps_bytes: int):
+    """The LZW bytes of N images -> (uint8 device tensor [maps_bytes]: image f's w h indices in raster order, interlace undone, at
+    ``map_offsets[f]``; int32 device tensor [N]: every image's status bits, 0 for a clean decode) (tt_gif_decode_indices).  ``data``: uint8
+    device tensor holding image f's bytes at ``offsets[f]`` (int64 [N]) with ``lengths[f]`` bytes; ``npix[f]`` = w h; ``min_code_size[f]``;
+    ``rows[f]``: the height of an interlaced image, else 0 (int32 device tensors [N]); ``map_offsets``: int64 [N]; ``maps_bytes``: a host
+    integer.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    for t in (data, offsets, lengths, npix, min_code_size, rows, map_offsets):
+        _p(t)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous() or data.numel() < 1:
+        raise RuntimeError(f"gif_indices: data must be a contiguous uint8 tensor [bytes], got {tuple(data.shape)} {data.dtype}")
+    n = offsets.numel()
+    for name, t, dt in (("offsets", offsets, torch.int64), ("map_offsets", map_offsets, torch.int64), ("lengths", lengths, torch.int32), ("npix", npix, torch.int32),
+                        ("min_code_size", min_code_size, torch.int32), ("rows", rows, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (n,) or n < 1 or not t.is_contiguous() or t.device != data.device:
+            raise RuntimeError(f"gif_indices: {name} must be a contiguous {dt} tensor [{n}] on {data.device}, got {tuple(t.shape)} {t.dtype}")
+    if isinstance(maps_bytes, bool) or not isinstance(maps_bytes, int) or maps_bytes < 1:
+        raise RuntimeError(f"gif_indices: maps_bytes {maps_bytes!r} (a positive integer)")
+    maps = torch.empty((maps_bytes,), dtype=torch.uint8, device=data.device)
+    status = torch.empty((n,), dtype=torch.int32, device=data.device)
+    ws = torch.empty((max(lib.tt_gif_decode_ws_bytes(n, data.numel()), 16),), dtype=torch.uint8, device=data.device)
+    check(lib.tt_gif_decode_indices(_p(data), data.numel(), _p(offsets), _p(lengths), _p(npix), _p(min_code_size), _p(rows), _p(map_offsets), n, _p(maps),
+                                    maps_bytes, _p(status), _p(ws), ws.numel(), _stream()), "tt_gif_decode_indices")
+    _wrote(maps, "gif_indices")
+    _wrote(status, "gif_indices")
+    return maps, status
+
+
+def gif_compose(maps: torch.Tensor, table: torch.Tensor, palettes: torch.Tensor, size, initial: int) -> torch.Tensor:
+    """``gif_indices``' maps, ``table`` (uint8 device tensor [N, 40]: the bytes of N TtGifComposeFrame rows) and ``palettes`` (uint8 device
+    tensor [N, 256, 3]) drawn onto a canvas of ``size`` (height, width) that starts as the colour ``initial`` (0x00BBGGRR) -> uint8 device
+    tensor [N, height, width, 3]: the canvas after every frame (tt_gif_compose).  Asynchronous on the current stream."""
+    lib = _lib.load()
+    for t in (maps, table, palettes):
+        _p(t)
+    if maps.dtype != torch.uint8 or maps.dim() != 1 or not maps.is_contiguous() or maps.numel() < 1:
+        raise RuntimeError(f"gif_compose: maps must be a contiguous uint8 tensor [bytes], got {tuple(maps.shape)} {maps.dtype}")
+    rowsize = C.sizeof(_lib.TtGifComposeFrame)
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != rowsize or table.shape[0] < 1 or not table.is_contiguous():
+        raise RuntimeError(f"gif_compose: table must be a contiguous uint8 tensor [N, {rowsize}], got {tuple(table.shape)} {table.dtype}")
+    n = table.shape[0]
+    if palettes.dtype != torch.uint8 or tuple(palettes.shape) != (n, 256, 3) or not palettes.is_contiguous():
+        raise RuntimeError(f"gif_compose: palettes must be a contiguous uint8 tensor [{n}, 256, 3], got {tuple(palettes.shape)} {palettes.dtype}")
+    if table.device != maps.device or palettes.device != maps.device:
+        raise RuntimeError("gif_compose: maps, table and palettes must be on one device")
+    height, width = (int(v) for v in size)
+    if height < 1 or width < 1:
+        raise RuntimeError(f"gif_compose: size {size!r} (height, width; positive)")
+    out = torch.empty((n, height, width, 3), dtype=torch.uint8, device=maps.device)
+    check(lib.tt_gif_compose(_p(maps), maps.numel(), _p(table), _p(palettes), n, height, width, int(initial) & 0xffffff, _p(out), _stream()), "tt_gif_compose")
+    _wrote(out, "gif_compose")
+    return out

@@ -162,6 +162,18 @@ class DevicePixels:
         pixels = ingest.decode_jpeg(files, device)
         return cls(pixels.expand(-1, -1, -1, 3) if pixels.shape[-1] == 1 else pixels)          # a grey file: L -> RGB repeats the channel
 
+    @classmethod
+    def from_gif(cls, path, device, frame=0) -> "DevicePixels":
+        """Frame ``frame`` (an index, or None for all frames) of a GIF file -- a path or bytes -- decoded on the device
+        (``ingest.decode_gif``): the canvas ``PIL.Image.open(f)`` shows after ``seek(frame)``, as ``convert("RGB")`` holds it."""
+        from .. import ingest
+        pixels = ingest.decode_gif(path, device)
+        if frame is None:
+            return cls(pixels)
+        if not -pixels.shape[0] <= int(frame) < pixels.shape[0]:
+            raise ValueError(f"DevicePixels.from_gif: frame {frame} of a file with {pixels.shape[0]} frames")
+        return cls(pixels[int(frame):int(frame) + 1] if int(frame) >= 0 else pixels[pixels.shape[0] + int(frame):][:1])
+
     @property
     def shape(self):
         return self.pixels.shape
