@@ -1397,6 +1397,122 @@ int tt_gif_decode_indices(const uint8_t* data, int64_t data_bytes, const int64_t
 int tt_gif_compose(const uint8_t* maps, int64_t maps_bytes, const TtGifComposeFrame* table, const uint8_t* palettes, int32_t n, int32_t height,
                    int32_t width, uint32_t initial, uint8_t* out, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PNG import: 8-bit PNG files decoded on the device to uint8 [F, H, W, ch] NHWC frames, byte for byte what Pillow's Image.open holds
+ * (this_and_that_vdm_amd/ingest.py drives it: decode_png / read_pngs / read_apng).  Only the compressed bytes cross to the device.  One
+ * host routine (tt_png_parse; plain C++, it touches no device), two device entry points (tt_png_inflate, tt_png_unfilter) and one size
+ * query.  Integers only: the same bytes on every call and every stream.  Additive: the ABI version is unchanged.
+ *
+ * 1. Container -- tt_png_parse (host).  The signature, then chunks (length, type, payload, CRC) up to IEND.  IHDR must come first and
+ *    its CRC-32 is verified; the CRCs of all other chunks are NOT (Pillow does not verify IDAT's either; the data's integrity is held
+ *    by the Adler-32, rule 4).  Accepted: bit depth 8, colour types 0 / 4 / 2 / 6 (channels 1 / 2 / 3 / 4), not interlaced; any number
+ *    of IDAT chunks of any length, zero included, one behind the other; ancillary chunks are skipped, tRNS and PLTE (a suggested palette)
+ *    included.  Animated files: acTL (plays, announced frames), every fcTL (sequence, width, height, x, y, delay, dispose, blend) and
+ *    the fdAT chunks behind it (their payload without the 4-byte sequence number); an fcTL before the IDAT makes the default image
+ *    frame 0.  The payloads are copied contiguously into `upload` in file order: the default image's zlib stream is upload[idat_offset,
+ *    idat_offset + idat_bytes), frame f's is upload[data_offset, data_offset + data_bytes).  spans[s] names chunk s's payload in the
+ *    file and its frame (-1: the IDAT of a default image that is no frame).
+ *    Two calls, as tt_gif_parse: spans, frames and upload all NULL count (header->spans, header->frames, header->data_bytes); else
+ *    span_cap >= header->spans, frame_cap >= header->frames entries and upload_cap >= header->data_bytes bytes are filled, and nothing
+ *    beyond them is written (frames may be NULL when header->frames is 0).
+ *    TT_EINVAL, the text names the cause: null data / header; size <= 0; a bad signature ("signature"); a file that ends inside a
+ *    chunk or before IEND ("ends inside"); no IHDR first ("IHDR"); an IHDR of another length or with a bad CRC ("CRC"); zero size
+ *    ("zero size"); no IDAT ("no IDAT"); IDAT chunks with other chunks between them ("apart"); an unknown critical chunk ("unknown
+ *    critical chunk"); a zlib stream of fewer than 2 bytes or whose header is not method 8 ("method 8"), names a window above 32 KiB
+ *    ("window"), has a preset dictionary ("preset dictionary") or fails its check bits ("check bits"), the default image's and every
+ *    frame's; an fcTL or acTL of the wrong length, an fdAT before any fcTL or shorter than 4 bytes; outputs that do not go together
+ *    or caps too small.  TT_EUNSUPPORTED: bit depths 1 / 2 / 4 / 16 ("bit depth"); palette files ("colour type 3"); Adam7
+ *    ("interlaced"); a compression or filter method other than 0; a stream of 2^29 bytes or more; more than 65 535 frames.
+ *    Every loop of the parser advances through the file: its trips are bounded by the file's size.
+ * 2. Inflate -- tt_png_inflate (device): n zlib streams (RFC 1950 / 1951), stream f at data[offsets[f], + lengths[f]), with the number
+ *    of bytes each must give, expected[f] <= max_out -> those bytes at out[out_offsets[f] ...] and status[n].  It knows nothing of PNG.
+ *    For a PNG, expected = tt_png_stream_bytes, out_offsets[f] = f tt_png_frame_stride: the layout tt_png_filter writes.  Every window
+ *    size, stored, fixed and dynamic blocks in any order.  Bytes the stream does not reach are 0; bytes beyond expected are dropped.
+ *    A memset of status, then 3 + ceil(log2(max_out)) launches:
+ *      tokens -- grid (n), one workgroup of 1024 lanes per stream walks its blocks in order.  A stored block is a byte-aligned copy by
+ *                all lanes.  A dynamic block's code lengths are read by one lane (at most 320 symbols) into canonical codes in LDS
+ *                (counts per length and symbols by code, decoded length by length in at most 15 steps); the fixed block's codes are
+ *                built the same way from its constant lengths.  The block's symbols are decoded in windows of 16 KiB staged in LDS:
+ *                lane i starts at bit 128 i of the window, decodes the tokens that START in its 128 bits and records where it leaves
+ *                them; then every lane takes its neighbour's exit as its start and decodes again if that moved, until nothing moves
+ *                (lane k is right from round k on: at most 1024 rounds, a handful on real data, because a Huffman stream decoded
+ *                from a wrong bit falls into step).  The state a lane inherits is the one bit position.  The first lane that meets
+ *                the end of block (or an error, or the end of the data) ends the window; a scan of the lanes' byte counts places
+ *                every token, and the lanes decode once more to write the SOURCE WORD of every byte: a literal (bit 31 set, the byte
+ *                below) or the index in `out` of the byte it copies, its own position less the distance;
+ *      jumps  -- ceil(log2(max_out)) launches of src[i] <- src[src[i]] over every byte that is not yet a literal: a byte's chain of
+ *                copies is shorter than max_out, and after round k a word is a literal or names a byte 2^k copies back or more.  A
+ *                constant stream (one chain as long as the stream) takes the same rounds as noise;
+ *      bytes  -- per chunk of TT_INFLATE_CHUNK bytes: the literals leave as bytes, and the chunk's Adler-32 pair (sum b, sum (L - i) b);
+ *      adler  -- grid (n): s1 = 1 + sum of the chunks' first sums, s2 = expected + sum of (second sum + bytes behind the chunk x first
+ *                sum), mod 65 521, against the stream's big-endian trailer.
+ *    No workgroup waits on another, no readback sizes a grid, every loop's trip count is bounded before it starts (by the stream's
+ *    bits, 1024, 320, 258, 15 or the chunk count), and the dependent work per output byte grows neither with its chain of copies nor
+ *    with the length of its Huffman stream.
+ * 3. Status of tt_png_inflate, one word per stream, each bit marks only its own stream:
+ *    TT_INFLATE_STATUS_BLOCK: a zlib header rule 1 names as refused, a reserved block type, or a stored LEN / NLEN mismatch;
+ *    TT_INFLATE_STATUS_CODE: more than 286 / 30 codes, an over-subscribed or incomplete set of code lengths (incomplete is allowed for
+ *      a literal/length or distance set whose longest code is 1 bit, as zlib allows it), a repeat with nothing before it or past the
+ *      last length, no end-of-block code, bits that are no code of the set, the symbols 286 / 287 or the distance symbols 30 / 31;
+ *    TT_INFLATE_STATUS_DIST: a distance that reaches before the stream's first byte (the bytes are 0 and the decode goes on);
+ *    TT_INFLATE_STATUS_SHORT: fewer bytes than expected -- also where a BLOCK or CODE error or the end of the data stops the stream;
+ *    TT_INFLATE_STATUS_LONG: more bytes than expected;
+ *    TT_INFLATE_STATUS_ADLER: the stream ended with its final block and exactly the expected bytes, and its trailer is missing or is
+ *      not the Adler-32 of those bytes;
+ *    TT_INFLATE_STATUS_SPAN: offsets / lengths outside data, expected above max_out, or out_offsets / expected outside out (the
+ *      stream is taken as empty and nothing of it is written).
+ *    Whatever the data and the arrays hold, nothing is written outside out, status and ws.
+ * 4. Unfilter -- tt_png_unfilter (device): filtered streams in tt_png_filter's layout -> pixels [n, h, w, ch]; the exact inverse of
+ *    tt_png_filter for all five types (x = v + a; + b; + ((a + b) >> 1), the 9-bit sum floored; + paeth(a, b, c) with the tie order
+ *    a, b, c), mod 256.  A pixel needs its left, upper and upper-left neighbours, so the anti-diagonals x + y = t are independent:
+ *    one launch, grid (bands of TT_PNG_UNFILTER_BAND rows, n), a lane per row, step t handles x = t - row with all channels of the
+ *    pixel, the upper pixel handed down through LDS.  A band whose first row is of type 0 or 1 needs nothing of the row above: its
+ *    workgroup starts there and runs on through the following bands up to the next such band.  Status bit
+ *    TT_PNG_UNFILTER_STATUS_TYPE: a filter-type byte above 4 (the row is read as type 0).
+ *
+ * The workspace grows with the OUTPUT, which the host knows exactly, not with the compressed size: tt_png_decode_ws_bytes(n,
+ * out_bytes, max_out) = n records of 32 bytes + 4 out_bytes (a source word per byte of out) + 8 n ceil(max_out / TT_INFLATE_CHUNK) (a
+ * pair per chunk), each part rounded up to 16; 0 for arguments the entry point refuses.
+ * TT_EINVAL: a null pointer; n, data_bytes, out_bytes or max_out <= 0; max_out above out_bytes; offsets or out_offsets off an 8-byte,
+ * lengths, expected and status off a 4-byte, ws (and tt_png_unfilter's filtered) off a 16-byte boundary; ws_bytes too small ("ws too
+ * small"); tt_png_unfilter: n, h or w <= 0, ch outside 1 .. 4.  TT_EUNSUPPORTED: more than 65 535 streams; data_bytes of 2^29 or more
+ * (bit offsets are 32-bit); out_bytes of 2^31 or more (a source word's index is 31-bit).
+ * Every entry point refuses before the first HIP call; no allocation, no synchronisation. */
+#define TT_INFLATE_STATUS_BLOCK 1u
+#define TT_INFLATE_STATUS_CODE 2u
+#define TT_INFLATE_STATUS_DIST 4u
+#define TT_INFLATE_STATUS_SHORT 8u
+#define TT_INFLATE_STATUS_LONG 16u
+#define TT_INFLATE_STATUS_ADLER 32u
+#define TT_INFLATE_STATUS_SPAN 64u
+#define TT_PNG_UNFILTER_STATUS_TYPE 1u
+#define TT_INFLATE_CHUNK 4096
+#define TT_INFLATE_MAX_STREAMS 65535
+#define TT_PNG_UNFILTER_BAND 256
+typedef struct TtPngHeader {
+  int32_t width, height, channels, bit_depth, color_type, interlace;
+  int32_t spans, frames;                            /* IDAT + fdAT chunks; fcTL chunks (0: not animated) */
+  int32_t plays, announced;                         /* acTL's num_plays and num_frames; -1, 0 without acTL */
+  int32_t default_is_frame, reserved;               /* an fcTL stands before the IDAT */
+  int64_t idat_offset, idat_bytes, data_bytes;      /* in upload; data_bytes: all payloads, end to end */
+} TtPngHeader;
+typedef struct TtPngSpan {
+  int64_t file_offset, bytes;                       /* the payload in the file (an fdAT's without its sequence number) */
+  int32_t frame, reserved;                          /* -1: the IDAT of a default image that is no frame */
+} TtPngSpan;
+typedef struct TtPngFrame {
+  int32_t sequence, width, height, x, y, delay_num, delay_den, dispose, blend, spans;
+  int64_t data_offset, data_bytes;                  /* in upload */
+} TtPngFrame;
+int tt_png_parse(const uint8_t* data /* host */, int64_t size, TtPngHeader* header /* host */, TtPngSpan* spans /* host [span_cap] or NULL */,
+                 int64_t span_cap, TtPngFrame* frames /* host [frame_cap] or NULL */, int64_t frame_cap, uint8_t* upload /* host [upload_cap] or NULL */,
+                 int64_t upload_cap);
+int64_t tt_png_decode_ws_bytes(int32_t n, int64_t out_bytes, int64_t max_out);
+int tt_png_inflate(const uint8_t* data, int64_t data_bytes, const int64_t* offsets, const uint32_t* lengths, const uint32_t* expected,
+                   const int64_t* out_offsets, int32_t n, int64_t max_out, uint8_t* out, int64_t out_bytes, uint32_t* status, void* ws,
+                   int64_t ws_bytes, tt_stream_t stream);
+int tt_png_unfilter(const uint8_t* filtered, int32_t n, int32_t h, int32_t w, int32_t ch, uint8_t* out, uint32_t* status, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

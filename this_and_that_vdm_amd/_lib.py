@@ -138,6 +138,31 @@ class TtGifComposeFrame(C.Structure):
                 ("fill", C.c_uint32), ("reserved", C.c_int32), ("map_offset", C.c_int64)]
 
 
+TT_INFLATE_STATUS = {1: "a bad zlib header, a reserved block type or a stored block whose lengths disagree", 2: "an invalid set of code lengths or an invalid code",
+                     4: "a distance that reaches before the first byte", 8: "fewer bytes than the image holds", 16: "more bytes than the image holds",
+                     32: "an Adler-32 mismatch", 64: "a stream outside the buffers"}
+TT_PNG_UNFILTER_STATUS = {1: "a filter type above 4"}
+TT_INFLATE_CHUNK, TT_INFLATE_MAX_STREAMS, TT_PNG_UNFILTER_BAND = 4096, 65535, 256
+
+
+class TtPngHeader(C.Structure):
+    """What tt_png_parse reads of a PNG file: the field order of include/ttvdm.h."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("bit_depth", C.c_int32), ("color_type", C.c_int32), ("interlace", C.c_int32),
+                ("spans", C.c_int32), ("frames", C.c_int32), ("plays", C.c_int32), ("announced", C.c_int32), ("default_is_frame", C.c_int32), ("reserved", C.c_int32),
+                ("idat_offset", C.c_int64), ("idat_bytes", C.c_int64), ("data_bytes", C.c_int64)]
+
+
+class TtPngSpan(C.Structure):
+    """One IDAT / fdAT payload as tt_png_parse reads it (24 bytes): the field order of include/ttvdm.h."""
+    _fields_ = [("file_offset", C.c_int64), ("bytes", C.c_int64), ("frame", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TtPngFrame(C.Structure):
+    """One fcTL of an animated PNG as tt_png_parse reads it (56 bytes): the field order of include/ttvdm.h."""
+    _fields_ = [("sequence", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("delay_num", C.c_int32),
+                ("delay_den", C.c_int32), ("dispose", C.c_int32), ("blend", C.c_int32), ("spans", C.c_int32), ("data_offset", C.c_int64), ("data_bytes", C.c_int64)]
+
+
 class TtJpegHeader(C.Structure):
     """What tt_jpeg_parse reads from one baseline JPEG file: the field order of include/ttvdm.h."""
     _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("ch", C.c_int32), ("subsampling", C.c_int32),
@@ -277,6 +302,11 @@ SIGNATURES = {
     "tt_gif_decode_ws_bytes": (_i64, [_i32, _i64]),
     "tt_gif_decode_indices": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     "tt_gif_compose": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, C.c_uint32, _vp, _vp]),
+    # the PNG import: the container on the host, a general zlib inflate and the inverse row filters on the device (additive as well)
+    "tt_png_parse": (C.c_int, [_vp, _i64, C.POINTER(TtPngHeader), _vp, _i64, _vp, _i64, _vp, _i64]),
+    "tt_png_decode_ws_bytes": (_i64, [_i32, _i64, _i64]),
+    "tt_png_inflate": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tt_png_unfilter": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -301,3 +301,145 @@ def decode_gif(file, device, info: bool = False):
 def read_gif(path, device="cuda") -> torch.Tensor:
     """The frames of a GIF file (``export.write_gif``'s, Pillow's, imageio's) decoded by ``decode_gif``."""
     return decode_gif(path, device)
+
+
+# ---- PNG files (include/ttvdm.h, "PNG import"): the container on the host, a general zlib inflate and the inverse row filters on the device
+@dataclass
+class PngHeader:
+    """What ``parse_png`` reads from one file: the geometry, ``channels`` (1 / 2 / 3 / 4 for colour types 0 / 4 / 2 / 6), ``bit_depth``,
+    ``color_type``, ``interlace``; ``spans`` int64 [S, 2]: every IDAT / fdAT payload's byte offset in the file and its length, with
+    ``span_frames`` [S] (the frame it belongs to; -1: the IDAT of a default image that is no frame); ``idat`` (offset, bytes): the default
+    image's zlib stream in ``data`` (all payloads end to end).  For an animated file ``plays`` (acTL; None without it), ``announced``
+    (acTL's frame count), ``default_is_frame`` and per fcTL ``frames``: dicts of sequence, width, height, x, y, delay_num, delay_den,
+    dispose, blend, spans, data_offset, data_bytes (the frame's zlib stream in ``data``)."""
+    height: int
+    width: int
+    channels: int
+    bit_depth: int
+    color_type: int
+    interlace: int
+    spans: np.ndarray
+    span_frames: list
+    idat: tuple
+    plays: object
+    announced: int
+    default_is_frame: bool
+    frames: list
+    data: np.ndarray
+
+
+def parse_png(data: bytes) -> PngHeader:
+    """One PNG / APNG file -> its header, its spans and its compressed bytes (tt_png_parse: once to count, once to take them); ValueError
+    with the library's text, which names the cause, for what is refused."""
+    lib = _lib.load()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    at = buf.ctypes.data if buf.size else None
+    hd = _lib.TtPngHeader()
+    rc = lib.tt_png_parse(at, buf.size, C.byref(hd), None, 0, None, 0, None, 0)
+    if rc == 0:
+        spans = (_lib.TtPngSpan * max(hd.spans, 1))()
+        frames = (_lib.TtPngFrame * max(hd.frames, 1))()
+        upload = np.zeros(max(hd.data_bytes, 1), dtype=np.uint8)
+        rc = lib.tt_png_parse(at, buf.size, C.byref(hd), C.cast(spans, C.c_void_p), hd.spans, C.cast(frames, C.c_void_p), hd.frames, upload.ctypes.data, hd.data_bytes)
+    if rc != 0:
+        raise ValueError(lib.tt_last_error().decode(errors="replace"))
+    names = [n for n, _ in _lib.TtPngFrame._fields_]
+    return PngHeader(hd.height, hd.width, hd.channels, hd.bit_depth, hd.color_type, hd.interlace,
+                     np.array([[spans[i].file_offset, spans[i].bytes] for i in range(hd.spans)], dtype=np.int64).reshape(-1, 2),
+                     [spans[i].frame for i in range(hd.spans)], (hd.idat_offset, hd.idat_bytes), None if hd.plays < 0 else hd.plays, hd.announced,
+                     bool(hd.default_is_frame), [{n: getattr(frames[i], n) for n in names} for i in range(hd.frames)], upload[:hd.data_bytes])
+
+
+def _png_decode_streams(who: str, heads: list, streams: list, device, label: str) -> torch.Tensor:
+    """zlib streams of one geometry (``streams[i]``: a uint8 array) -> uint8 [N, H, W, ch]: one upload of the bytes, one of five numbers a
+    stream, the inflate and the unfilter, one readback of the status words"""
+    from . import ops
+    lib = _lib.load()
+    h0 = heads[0]
+    shape = (h0.height, h0.width, h0.channels)
+    n = len(streams)
+    if n > _lib.TT_INFLATE_MAX_STREAMS:
+        raise ValueError(f"{who}: {n} {label}s: more than one call decodes ({_lib.TT_INFLATE_MAX_STREAMS})")
+    expected, stride = lib.tt_png_stream_bytes(*shape), lib.tt_png_frame_stride(*shape)
+    if expected < 1 or n * stride >= 1 << 31:
+        raise ValueError(f"{who}: {n} {label}s of {shape[0]} x {shape[1]} x {shape[2]}: {n * stride} bytes of filtered rows (fewer than 2^31 in one call)")
+    lens = np.array([len(s) for s in streams], dtype=np.int64)
+    if int(lens.sum()) >= 1 << 29:
+        raise ValueError(f"{who}: {int(lens.sum())} compressed bytes in one call (fewer than 2^29)")
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    cols = np.stack([offs, np.arange(n, dtype=np.int64) * stride, lens, np.full(n, expected, dtype=np.int64)])
+    blob = torch.from_numpy(np.concatenate([np.asarray(s, dtype=np.uint8).reshape(-1) for s in streams])).to(device)
+    words = torch.from_numpy(cols).to(device)                                                       # the small upload: four numbers a stream
+    filtered, status = ops.png_inflate(blob, words[0].contiguous(), words[2].to(torch.int32), words[3].to(torch.int32), words[1].contiguous(), int(expected),
+                                       int(n * stride))
+    pixels, bad_rows = ops.png_unfilter(filtered.view(n, stride), shape)
+    both = torch.stack([status, bad_rows]).cpu().tolist()                                            # the one readback
+    for i, (s, t) in enumerate(zip(*both)):
+        if s or t:
+            why = [text for bit, text in _lib.TT_INFLATE_STATUS.items() if s & bit] + [text for bit, text in _lib.TT_PNG_UNFILTER_STATUS.items() if t & bit]
+            raise ValueError(f"{who}: {label} {i} is corrupt or truncated ({', '.join(why)}; status {s}, rows {t})")
+    return pixels
+
+
+def decode_png(files, device) -> torch.Tensor:
+    """8-bit PNG files of ONE geometry and colour type -- bytes or paths, one or a list -- -> uint8 [F, H, W, ch] on ``device``, ch 1 / 2 /
+    3 / 4 for grey / grey + alpha / RGB / RGBA: ``np.asarray(PIL.Image.open(f))``, byte for byte (a grey file comes back as [..., 1]).  One
+    upload of the compressed bytes, one small upload of per-file numbers, one readback (the status words).  Of an animated PNG the default
+    image (IDAT) is decoded, as ``Image.open`` shows it.  The CRCs of the IDAT chunks are not verified (Pillow does not either); the
+    Adler-32 of the data is, on the device.  ValueError: a file the parser refuses (its text names the cause: palette, 16-bit and
+    sub-byte depths, interlace, ...), files that differ in size or colour type, a file whose stream is corrupt or truncated (the file is
+    named), a ``device`` that is not the HIP device."""
+    items = list(files) if isinstance(files, (list, tuple)) else [files]
+    if not items:
+        raise ValueError("decode_png: no files")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"decode_png: decodes on the HIP device, got {device} (there is no CPU fallback)")
+    heads, streams = [], []
+    for i, f in enumerate(items):
+        try:
+            hd = parse_png(_read(f))
+        except ValueError as e:
+            raise ValueError(f"decode_png: file {i}: {e}") from None
+        if heads and (hd.height, hd.width, hd.channels) != (heads[0].height, heads[0].width, heads[0].channels):
+            raise ValueError(f"decode_png: file {i} is {hd.height} x {hd.width} x {hd.channels}, file 0 is {heads[0].height} x {heads[0].width} x "
+                             f"{heads[0].channels}: one geometry and colour type per call")
+        heads.append(hd)
+        streams.append(hd.data[hd.idat[0]:hd.idat[0] + hd.idat[1]])
+    return _png_decode_streams("decode_png", heads, streams, device, "file")
+
+
+def read_pngs(folder, pattern: str = "{idx}.png", device="cuda") -> torch.Tensor:
+    """``folder/pattern.format(idx=i)`` for i = 0, 1, ... up to the first missing index -- the layout ``export.write_pngs`` writes and the
+    reference's scripts pass clips around in -- decoded by ``decode_png``."""
+    paths = []
+    while os.path.exists(os.path.join(folder, pattern.format(idx=len(paths)))):
+        paths.append(os.path.join(folder, pattern.format(idx=len(paths))))
+        if len(paths) > 1 and paths[-1] == paths[-2]:
+            raise ValueError(f"read_pngs: pattern {pattern!r} names two frames alike (use {{idx}})")
+    if not paths:
+        raise ValueError(f"read_pngs: {os.path.join(folder, pattern.format(idx=0))} does not exist")
+    return decode_png(paths, device)
+
+
+def read_apng(path, device="cuda") -> torch.Tensor:
+    """Every frame of an animated PNG -- a path or bytes -- whose frames all cover the canvas with dispose 0 and blend 0 (what
+    ``export.write_apng`` writes) -> uint8 [F, H, W, ch].  ValueError: a file without fcTL chunks, or an fcTL that names a region, a
+    dispose or a blend operation (the frame and the field are named: those are not built)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"read_apng: decodes on the HIP device, got {device} (there is no CPU fallback)")
+    try:
+        hd = parse_png(_read(path))
+    except ValueError as e:
+        raise ValueError(f"read_apng: {e}") from None
+    if not hd.frames:
+        raise ValueError("read_apng: not an animated PNG (no fcTL chunk); decode_png reads it")
+    for i, fr in enumerate(hd.frames):
+        if (fr["width"], fr["height"], fr["x"], fr["y"]) != (hd.width, hd.height, 0, 0):
+            raise ValueError(f"read_apng: frame {i}'s fcTL names the region {fr['width']} x {fr['height']} at ({fr['x']}, {fr['y']}) of a {hd.width} x {hd.height} "
+                             "canvas: frames that do not cover the canvas are not built")
+        if fr["dispose"] != 0 or fr["blend"] != 0:
+            raise ValueError(f"read_apng: frame {i}'s fcTL names dispose {fr['dispose']} / blend {fr['blend']}: only dispose 0 and blend 0 are built")
+    streams = [hd.data[fr["data_offset"]:fr["data_offset"] + fr["data_bytes"]] for fr in hd.frames]
+    return _png_decode_streams("read_apng", [hd], streams, device, "frame")

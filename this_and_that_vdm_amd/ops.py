@@ -1508,3 +1508,45 @@ def gif_compose(maps: torch.Tensor, table: torch.Tensor, palettes: torch.Tensor,
     check(lib.tt_gif_compose(_p(maps), maps.numel(), _p(table), _p(palettes), n, height, width, int(initial) & 0xffffff, _p(out), _stream()), "tt_gif_compose")
     _wrote(out, "gif_compose")
     return out
+
+
+# ---- the PNG import's device half (tt_png_inflate / tt_png_unfilter; ingest.py parses the files)
+def png_inflate(data: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, expected: torch.Tensor, out_offsets: torch.Tensor, max_out: int, out_bytes: int):
+    """N zlib streams -> (uint8 device tensor [out_bytes]: stream f's ``expected[f]`` bytes at ``out_offsets[f]``; int32 device tensor [N]: every
+    stream's status bits, 0 for a clean decode) (tt_png_inflate; a general inflate that knows nothing of PNG).  ``data``: uint8 device tensor
+    holding stream f at ``offsets[f]`` (int64 [N]) with ``lengths[f]`` bytes (int32 [N]); ``expected``: int32 [N], none above the host integer
+    ``max_out``; ``out_offsets``: int64 [N]; ``out_bytes``: a host integer.  Bytes of ``out`` that belong to no stream are not written.
+    Asynchronous on the current stream."""
+    lib = _lib.load()
+    for t in (data, offsets, lengths, expected, out_offsets):
+        _p(t)
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous() or data.numel() < 1:
+        raise RuntimeError(f"png_inflate: data must be a contiguous uint8 tensor [bytes], got {tuple(data.shape)} {data.dtype}")
+    n = offsets.numel()
+    for name, t, dt in (("offsets", offsets, torch.int64), ("out_offsets", out_offsets, torch.int64), ("lengths", lengths, torch.int32), ("expected", expected, torch.int32)):
+        if t.dtype != dt or tuple(t.shape) != (n,) or n < 1 or not t.is_contiguous() or t.device != data.device:
+            raise RuntimeError(f"png_inflate: {name} must be a contiguous {dt} tensor [{n}] on {data.device}, got {tuple(t.shape)} {t.dtype}")
+    for name, v in (("max_out", max_out), ("out_bytes", out_bytes)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise RuntimeError(f"png_inflate: {name} {v!r} (a positive integer)")
+    out = torch.empty((out_bytes,), dtype=torch.uint8, device=data.device)
+    status = torch.empty((n,), dtype=torch.int32, device=data.device)
+    ws = torch.empty((max(lib.tt_png_decode_ws_bytes(n, out_bytes, max_out), 16),), dtype=torch.uint8, device=data.device)
+    check(lib.tt_png_inflate(_p(data), data.numel(), _p(offsets), _p(lengths), _p(expected), _p(out_offsets), n, max_out, _p(out), out_bytes, _p(status), _p(ws),
+                             ws.numel(), _stream()), "tt_png_inflate")
+    _wrote(out, "png_inflate")
+    _wrote(status, "png_inflate")
+    return out, status
+
+
+def png_unfilter(filtered: torch.Tensor, shape):
+    """``png_filter``'s layout (uint8 device tensor [N, stride]) for frames of ``shape`` (h, w, ch) -> (uint8 device tensor [N, h, w, ch]: the
+    pixels, the exact inverse of ``png_filter``; int32 device tensor [N]: bit 0 where a row's filter type is above 4) (tt_png_unfilter).
+    Asynchronous on the current stream."""
+    lib, n, h, w, ch, _ = _png_filtered(filtered, shape, "png_unfilter")
+    out = torch.empty((n, h, w, ch), dtype=torch.uint8, device=filtered.device)
+    status = torch.empty((n,), dtype=torch.int32, device=filtered.device)
+    check(lib.tt_png_unfilter(_p(filtered), n, h, w, ch, _p(out), _p(status), _stream()), "tt_png_unfilter")
+    _wrote(out, "png_unfilter")
+    _wrote(status, "png_unfilter")
+    return out, status

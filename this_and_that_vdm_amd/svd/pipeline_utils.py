@@ -163,6 +163,16 @@ class DevicePixels:
         return cls(pixels.expand(-1, -1, -1, 3) if pixels.shape[-1] == 1 else pixels)          # a grey file: L -> RGB repeats the channel
 
     @classmethod
+    def from_png(cls, files, device) -> "DevicePixels":
+        """8-bit PNG file(s) of one size and colour type -- paths or bytes -- decoded on the device (``ingest.decode_png``): only the
+        compressed bytes are uploaded, and the pixels are the ones ``PIL.Image.open(f).convert("RGB")`` holds: grey is repeated, alpha
+        is dropped."""
+        from .. import ingest
+        pixels = ingest.decode_png(files, device)
+        ch = pixels.shape[-1]
+        return cls(pixels[..., :1].expand(-1, -1, -1, 3) if ch <= 2 else pixels[..., :3])
+
+    @classmethod
     def from_gif(cls, path, device, frame=0) -> "DevicePixels":
         """Frame ``frame`` (an index, or None for all frames) of a GIF file -- a path or bytes -- decoded on the device
         (``ingest.decode_gif``): the canvas ``PIL.Image.open(f)`` shows after ``seek(frame)``, as ``convert("RGB")`` holds it."""
