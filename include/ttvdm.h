@@ -1171,8 +1171,9 @@ int tt_jpeg_scan_restart(const int16_t* coeffs, int32_t n, int32_t h, int32_t w,
  * (tt_jpeg_entropy, tt_jpeg_pixels) and two size queries.  Integers from end to end: equality is the bound.  Additive: the ABI version
  * is unchanged.  Accepted: SOF0, 8-bit samples, one interleaved scan, one component (any sampling factor, taken as 1 x 1) or three
  * (YCbCr, sampling 1x1 / 1x1 / 1x1 or 2x2 / 1x1 / 1x1), 8-bit DQT, up to two DC and two AC Huffman tables, any component -> table map;
- * APPn and COM segments are skipped; restart intervals through tt_jpeg_parse_spans / tt_jpeg_entropy_spans (rules 1a, 4a).  Not here:
- * progressive, arithmetic and 12-bit files, several scans, 4:2:2, CMYK / Adobe files, EXIF orientation (not applied).  Coefficients whose inverse DCT leaves 0 .. 255 clamp to 0 / 255; libjpeg's range-limit
+ * APPn and COM segments are skipped; restart intervals through tt_jpeg_parse_spans / tt_jpeg_entropy_spans (rules 1a, 4a);
+ * progressive (SOF2) files through tt_jpeg_parse_progressive / tt_jpeg_entropy_progressive (rules 1b, 4b, behind the prototypes).  Not here:
+ * arithmetic and 12-bit files, several scans in a baseline file, 4:2:2, CMYK / Adobe files, EXIF orientation (not applied).  Coefficients whose inverse DCT leaves 0 .. 255 clamp to 0 / 255; libjpeg's range-limit
  * table wraps there, so such crafted files are not held to it.
  *
  * 1. Parse -- tt_jpeg_parse (host): one file -> TtJpegHeader: the geometry, the subsampling, the byte range of the entropy-coded
@@ -1286,6 +1287,91 @@ int tt_jpeg_entropy_spans(const uint8_t* scans, int64_t scans_bytes, const int64
                           const uint32_t* span_first, const uint32_t* span_blocks, int64_t max_bytes, int32_t nspans, int32_t n, int32_t h, int32_t w,
                           int32_t ch, int32_t subsampling, const uint32_t* tables, int32_t ntables, int16_t* coeffs, uint32_t* status, void* ws,
                           int64_t ws_bytes, tt_stream_t stream);
+/* Progressive files (SOF2; additive: tt_jpeg_parse and tt_jpeg_parse_spans keep refusing them, and a baseline file takes the launches
+ * above).  A progressive file ends where a baseline one does: every scan is absorbed into the coefficient layout of rule 4, then rule 5
+ * (tt_jpeg_pixels) runs unchanged.  Equal to libjpeg for every file whose progression is COMPLETE (below).
+ * 1b. Parse -- tt_jpeg_parse_progressive (host): one file -> TtJpegProgressiveHeader (geometry, subsampling, per component its quantiser
+ *    table in natural order, the scan count) and per scan a TtJpegScan: `comps` (bit c: component c of the frame is in the scan), Ss, Se,
+ *    Ah, Al, the byte offset and stuffed length of its entropy-coded segment, and BITS / HUFFVAL of the tables in force AT THAT SOS (DHT
+ *    segments between scans redefine the slots 0 .. 3 of either class, so the tables are snapshotted per scan): a DC-first scan (Ss = 0,
+ *    Ah = 0) has component c's DC table at [c], an AC scan its one AC table at [0], a DC-refine scan none (zeros).  Two calls, as
+ *    tt_jpeg_parse_spans: scans == NULL counts (*nscans); else scan_cap >= *nscans entries are filled.
+ *    Validation (T.81 G.1.1.1.1, libjpeg's progression bookkeeping), TT_EINVAL, each by name: Ss = 0 with Se != 0 ("a DC scan with Se");
+ *    Ss > 0 with more than one component ("an AC scan of"); Se < Ss or Se > 63 ("band"); Al > 13 ("Al ="); Ah != 0 on a coefficient's
+ *    first visit, or on a later one Ah != the coefficient's previous Al or Al != Ah - 1 ("successive approximation"); an AC scan of a
+ *    component before its DC-first scan ("before its DC"); a DC scan holding some but not all components, or not in frame order
+ *    ("component subset"); a scan naming a component the frame does not have, or twice.
+ *    TT_EUNSUPPORTED, each by name: what tt_jpeg_parse refuses other than SOF2 and several scans (12-bit, arithmetic, four components /
+ *    Adobe, 16-bit DQT, other sampling, missing tables); a non-zero DRI ("restart intervals in a progressive file"); a DQT behind the
+ *    first SOS ("a DQT behind"); more than TT_JPEG_MAX_SCANS = 256 scans; a baseline SOF0 file ("tt_jpeg_parse_spans" decodes it); and an
+ *    INCOMPLETE PROGRESSION: at EOI every coefficient 0 .. 63 of every component must have reached Al = 0 ("incomplete progression").
+ *    libjpeg smooths the blocks of files that stop earlier (jdcoefct.c, smoothing_ok), so their pixels are not the inverse DCT of their
+ *    coefficients; they are refused, not decoded differently.  Every loop advances through the file.
+ * 4b. Entropy decode of progressive scans -- tt_jpeg_entropy_progressive (device).  ITEMS are (frame, scan) pairs: item f nscans + s is
+ *    scan s of frame f; offsets / lengths [n nscans] place its stuffed segment in `scans`; desc [n nscans][TT_JPEG_SCAN_WORDS = 8]
+ *    uint32 = comps, Ss, Se, Ah, Al, 0, 0, 0 (comps = 0: the frame has no scan s); tables [n nscans][3][TT_JPEG_DECODE_WORDS] as rule
+ *    1b lays them out.  All items are unstuffed at once by rule 3's three kernels; coeffs and status are zero-filled; then nscans ROUNDS
+ *    follow, one launch each, grid (n): round s applies scan s of every frame that has one, ONE workgroup of 256 lanes per frame, the
+ *    scan's kind read from desc.  Frames with different scan scripts share a call; stream order is the scan-to-scan dependency.
+ *    Block map.  An interleaved scan (all components) walks the MCUs: its k-th block is block k of the layout.  A single-component scan
+ *    walks the component's ceil(ceil(w Hi / Hmax) / 8) x ceil(ceil(h Vi / Vmax) / 8) REAL blocks in raster order: 4:2:0 Y block (by, bx)
+ *    is block (by & 1) 2 + (bx & 1) of MCU (by / 2, bx / 2); a chroma block or a 4:4:4 block k is block k of its component in MCU k;
+ *    grey: block k.  Dummy blocks keep zero AC (and the DC the interleaved DC scans give them).
+ *    DC first (Ss = 0, Ah = 0): rule 4's lanes and passes with the state (p, block within the MCU); a symbol is a DC size code and its
+ *    magnitude bits; the differences are written through the block map, then prefix-summed per component over the scan's own block order
+ *    in int32 and stored as pred << Al.
+ *    AC first (Ss > 0, Ah = 0): rule 4's lanes and passes with the state (p, z), z in Ss .. Se.  A symbol RS is as in baseline except
+ *    S = 0, R < 15: EOBn, a run of (1 << R) + receive(R) blocks that end here, this one included: the lane's blocks-completed count
+ *    advances by the run (saturating at 2^22 a lane, 2^31 a scan), so the exclusive scan that gives every lane its first block works
+ *    unchanged.  Values are stored as value << Al; a run that passes Se ends the block and sets TT_JPEG_STATUS_CODE on the true path.
+ *    DC refine (Ss = 0, Ah > 0): no Huffman code: bit k of the plain stream belongs to the scan's k-th block; one lane per block does
+ *    coef |= bit << Al.  A stream shorter than the block count sets TT_JPEG_STATUS_BLOCKS.
+ *    AC refine (Ss > 0, Ah > 0; T.81 G.1.2.3, libjpeg's decode_mcu_AC_refine), p1 = 1 << Al.  A code with S = 1 reads a sign bit for a new
+ *    coefficient +-p1; S = 0, R = 15 skips 16 zero-history coefficients; S = 0, R < 15 starts an EOB run of (1 << R) + receive(R) blocks;
+ *    S > 1 sets TT_JPEG_STATUS_CODE (and is taken as 1).  While R zero-history coefficients are skipped, every already-nonzero
+ *    coefficient passed takes one correction bit: if it is 1 and (coef & p1) == 0, coef += coef >= 0 ? p1 : -p1; the blocks of an EOB
+ *    run still take correction bits for the nonzero coefficients of their band.  The bits a block takes depend on which coefficients
+ *    were nonzero BEFORE the scan, so a lane that guesses its block cannot resynchronise.  Instead of lanes and passes:
+ *      masks  -- every lane takes blocks of the scan and stores per block a 64-bit mask of its nonzero coefficients inside Ss .. Se;
+ *      walk   -- ONE lane walks the stream from the true state (0, block 0, Ss, no run).  It never reads a coefficient or a correction
+ *                bit: a code moves z to the (R + 1)-th zero bit of the mask at or behind z and p by the code, the sign bit and the
+ *                popcount of the mask bits passed; an EOB run moves p by a popcount a block.  It stores, per block, the bit position its
+ *                first code (or, inside a run, its first correction bit) has, and a flag "inside a run".  The stream (a window of
+ *                tt_jpeg_sequence_bits + 64 bits) and the masks (1024 a time) are staged in LDS by all lanes; the stages are bounded by
+ *                L / (sequence bits - 31) + blocks / 1024 + 2, a stage's steps by sequence bits + 1024: every step takes a bit or a block;
+ *      replay -- every lane takes blocks: from its block's recorded position it decodes the block's codes and correction bits again,
+ *                now with the coefficients, and writes only that block.
+ *    The serial chain is thus bit-position arithmetic alone, one table lookup, one or two popcounts a code; what it replaces is a pass
+ *    per lane, each a full decode.  The walk stops at the first bit pattern that is no code (TT_JPEG_STATUS_CODE) or symbol that would
+ *    read beyond L; blocks it did not reach are not touched and set TT_JPEG_STATUS_BLOCKS.
+ *    All kinds: TT_JPEG_STATUS_TAIL as in rule 4; a descriptor whose numbers no scan has (an AC scan with several components or Se < Ss)
+ *    sets TT_JPEG_STATUS_SPAN and is skipped; Ss, Se are held to 0 .. 63, Al to 0 .. 13.  No workgroup waits on another; every loop's
+ *    bound is computed before it starts; every table and buffer index is masked or guarded; no host readback; status stays one word per
+ *    frame with rule 4's bits.  Two memsets, one fill, three unstuffing launches, nscans round launches.
+ *    ws: tt_jpeg_entropy_progressive_ws_bytes: tt_jpeg_entropy_ws_bytes(n nscans, max_bytes), then per item its frame (int32), then per
+ *    frame tt_jpeg_blocks masks (uint64) and positions (uint32).
+ *    TT_EINVAL: null pointer; n, nscans, h, w, max_bytes or scans_bytes <= 0; ch, subsampling as tt_jpeg_entropy; tables, coeffs, ws or
+ *    desc off a 16-byte boundary; offsets off 8, lengths or status off 4; ws_bytes too small.  TT_EUNSUPPORTED: as tt_jpeg_coeffs;
+ *    max_bytes of 2^28 or more; nscans above TT_JPEG_MAX_SCANS; n nscans above 65535 (a grid dimension).  Refused before any HIP call. */
+#define TT_JPEG_MAX_SCANS 256
+#define TT_JPEG_SCAN_WORDS 8
+typedef struct {
+  int32_t comps, ss, se, ah, al, reserved;
+  int64_t offset, bytes;
+  uint8_t bits[3][16];
+  uint8_t huffval[3][256];
+} TtJpegScan;
+typedef struct {
+  int32_t h, w, ch, subsampling, nscans, reserved;
+  uint8_t quant[3][64];
+} TtJpegProgressiveHeader;
+int tt_jpeg_parse_progressive(const uint8_t* data /* host */, int64_t size, TtJpegProgressiveHeader* header /* host */,
+                              TtJpegScan* scans /* host [scan_cap] or NULL */, int64_t scan_cap, int64_t* nscans /* host */);
+int64_t tt_jpeg_entropy_progressive_ws_bytes(int32_t n, int32_t nscans, int64_t max_bytes, int32_t h, int32_t w, int32_t ch,
+                                             int32_t subsampling);                       /* 0 for arguments the entry point refuses */
+int tt_jpeg_entropy_progressive(const uint8_t* scans, int64_t scans_bytes, const int64_t* offsets, const uint32_t* lengths, const uint32_t* desc,
+                                const uint32_t* tables, int64_t max_bytes, int32_t n, int32_t nscans, int32_t h, int32_t w, int32_t ch,
+                                int32_t subsampling, int16_t* coeffs, uint32_t* status, void* ws, int64_t ws_bytes, tt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GIF import: an animated GIF decoded on the device to uint8 [F, H, W, 3] RGB frames, each the canvas a viewer shows after drawing

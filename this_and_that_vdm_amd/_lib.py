@@ -110,6 +110,7 @@ TT_PNG_STRIPE, TT_PNG_SYMS, TT_PNG_RECORD_WORDS, TT_PNG_TABLE_WORDS, TT_PNG_HEAD
 TT_JPEG_444, TT_JPEG_420, TT_JPEG_TABLE_WORDS, TT_JPEG_COUNT_WORDS = 0, 2, 256, 1024
 TT_JPEG_CHUNK, TT_JPEG_DECODE_WORDS, TT_JPEG_DECODE_SET_WORDS = 4096, 256, 1028
 TT_JPEG_MAX_SPANS = 65535
+TT_JPEG_MAX_SCANS, TT_JPEG_SCAN_WORDS, TT_JPEG_MAX_ITEMS = 256, 8, 65535
 TT_JPEG_STATUS = {1: "a marker inside the scan", 2: "an invalid Huffman code", 4: "the wrong number of blocks", 8: "bits left over behind the last block",
                   16: "a scan outside the buffer"}
 
@@ -169,6 +170,18 @@ class TtJpegHeader(C.Structure):
                 ("scan_offset", C.c_int64), ("scan_bytes", C.c_int64),
                 ("dc_table", C.c_int32 * 3), ("ac_table", C.c_int32 * 3),
                 ("quant", (C.c_uint8 * 64) * 3), ("bits", (C.c_uint8 * 16) * 4), ("huffval", (C.c_uint8 * 256) * 4)]
+
+
+class TtJpegScan(C.Structure):
+    """One scan of a progressive JPEG file as tt_jpeg_parse_progressive reads it (856 bytes): the field order of include/ttvdm.h."""
+    _fields_ = [("comps", C.c_int32), ("ss", C.c_int32), ("se", C.c_int32), ("ah", C.c_int32), ("al", C.c_int32), ("reserved", C.c_int32),
+                ("offset", C.c_int64), ("bytes", C.c_int64), ("bits", (C.c_uint8 * 16) * 3), ("huffval", (C.c_uint8 * 256) * 3)]
+
+
+class TtJpegProgressiveHeader(C.Structure):
+    """What tt_jpeg_parse_progressive reads of the frame: the field order of include/ttvdm.h."""
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("ch", C.c_int32), ("subsampling", C.c_int32), ("nscans", C.c_int32), ("reserved", C.c_int32),
+                ("quant", (C.c_uint8 * 64) * 3)]
 
 
 _i32, _i64, _f32, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
@@ -297,6 +310,10 @@ SIGNATURES = {
     # ... with restart intervals: the scan's spans on the host, one workgroup per span on the device (additive as well)
     "tt_jpeg_parse_spans": (C.c_int, [_vp, _i64, C.POINTER(TtJpegHeader), C.POINTER(C.c_int32), _vp, _vp, _i64, C.POINTER(C.c_int64)]),
     "tt_jpeg_entropy_spans": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    # ... progressive files: every scan's place and tables on the host, the scans applied round by round on the device (additive as well)
+    "tt_jpeg_parse_progressive": (C.c_int, [_vp, _i64, C.POINTER(TtJpegProgressiveHeader), _vp, _i64, C.POINTER(C.c_int64)]),
+    "tt_jpeg_entropy_progressive_ws_bytes": (_i64, [_i32, _i32, _i64, _i32, _i32, _i32, _i32]),
+    "tt_jpeg_entropy_progressive": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     # the GIF import: the container on the host, LZW, interlace and composition on the device (additive as well)
     "tt_gif_parse": (C.c_int, [_vp, _i64, C.POINTER(TtGifHeader), _vp, _i64, _vp, _i64]),
     "tt_gif_decode_ws_bytes": (_i64, [_i32, _i64]),

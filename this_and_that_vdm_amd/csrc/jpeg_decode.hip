@@ -3,38 +3,14 @@
 // tt_jpeg_entropy_spans -- the same per span between restart markers (rule 4a), of which tt_jpeg_entropy is "one span a frame" -- and
 // tt_jpeg_pixels -- dequantiser, the jidctint inverse DCT, fancy 4:2:0 chroma upsampling and the colour conversion in one launch.
 // Integer arithmetic only; the one atomic is an OR into a frame's status word: every call gives the same bytes.
-#include "common.h"
-#include "block_scan.h"
-#include "jpeg_host.h"
+#include "jpeg_device.h"
 
 namespace {
 
-constexpr int UBLOCK = 256;                         // lanes of an unstuffing chunk: 16 bytes a lane
-constexpr int CHUNK = TT_JPEG_CHUNK;
-static_assert(CHUNK == 16 * UBLOCK, "a lane holds one 16-byte unit of an unstuffing chunk");
-constexpr int SCAN_BLOCK = 1024, SCAN_WAVES = SCAN_BLOCK / 64;
-constexpr int ELANES = TT_JPEG_DECODE_LANES, EWAVES = ELANES / 64;
-constexpr int SUBSEQ = TT_JPEG_SUBSEQ_BITS;
-constexpr unsigned SEQ_BITS = (unsigned)SUBSEQ * ELANES, SEQ_WORDS = SEQ_BITS / 32;
-static_assert(SUBSEQ % 32 == 0 && SUBSEQ >= 64, "a subsequence is whole dwords and longer than any symbol (16 + 15 bits)");
 constexpr int PBLOCK = 256, TILE_W = 256;           // the reconstruction's tile: one MCU row down, TILE_W pixels across
 
 // ZZ[k]: the natural (row-major) index of the k-th coefficient of the zig-zag scan
 __device__ constexpr int ZZ[64] = TT_JPEG_ZIGZAG;
-
-// ---------------------------------------------------------------- rule 3: unstuffing
-// frame f's stuffed scan: its first byte and its length, both held inside `scans`; a span that is not gives an empty frame
-__device__ __forceinline__ long long span_of(long long scans_bytes, const long long* __restrict__ offsets, const unsigned* __restrict__ lengths,
-                                             long long max_bytes, int f, unsigned& len, bool& bad) {
-  const long long off = offsets[f], l = (long long)lengths[f];
-  bad = off < 0 || l > max_bytes || off > scans_bytes || l > scans_bytes - off;
-  len = bad ? 0u : (unsigned)l;
-  return bad ? 0 : off;
-}
-__device__ __forceinline__ const unsigned char* frame_span(const unsigned char* __restrict__ scans, long long scans_bytes, const long long* __restrict__ offsets,
-                                                           const unsigned* __restrict__ lengths, long long max_bytes, int f, unsigned& len, bool& bad) {
-  return scans + span_of(scans_bytes, offsets, lengths, max_bytes, f, len, bad);
-}
 
 // Items.  tt_jpeg_entropy's items are frames; tt_jpeg_entropy_spans' are the spans between restart markers, each with its frame, its
 // first block there and its block count (device arrays).  A span whose place is not inside its frame is taken as empty (`bad`), and its
@@ -49,85 +25,7 @@ __device__ __forceinline__ ItemPlace item_place(const int* __restrict__ span_fra
   return {min(max(f, 0), nframes - 1), bad ? 0u : first, bad ? 0u : count, bad};
 }
 
-// the chunk's bytes (and the one before them) into LDS, then per lane: the 0x00 bytes behind an 0xFF among its 16, as a bit mask
-__device__ __forceinline__ unsigned chunk_drops(const unsigned char* __restrict__ src, unsigned len, unsigned char* raw_s, bool& marker) {
-  const unsigned c0 = blockIdx.x * (unsigned)CHUNK;
-  for (int i = threadIdx.x; i < CHUNK + 1; i += UBLOCK) {
-    const long long g = (long long)c0 + i - 1;
-    raw_s[i] = (g >= 0 && g < (long long)len) ? src[g] : (unsigned char)0;
-  }
-  __syncthreads();
-  unsigned mask = 0u;
-  marker = false;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const unsigned at = c0 + 16 * threadIdx.x + j;
-    if (at < len) {
-      const unsigned b = raw_s[1 + 16 * threadIdx.x + j], before = raw_s[16 * threadIdx.x + j];
-      if (before == 0xffu && b == 0u) mask |= 1u << j;
-      marker = marker || (before == 0xffu && b != 0u) || (at == len - 1 && b == 0xffu);
-    }
-  }
-  return mask;
-}
-
-// grid (chunks, n)
-__global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_count_kernel(const unsigned char* __restrict__ scans, long long scans_bytes, const long long* __restrict__ offsets,
-                                                                   const unsigned* __restrict__ lengths, long long max_bytes, unsigned* __restrict__ chunk_drop,
-                                                                   int chunks, unsigned* __restrict__ status, const int* __restrict__ span_frame, int nframes) {
-  __shared__ unsigned char raw_s[CHUNK + 16];
-  __shared__ unsigned red_s[UBLOCK / 64];
-  unsigned len;
-  bool bad, marker;
-  const unsigned char* src = frame_span(scans, scans_bytes, offsets, lengths, max_bytes, blockIdx.y, len, bad);
-  const unsigned drops = __popc(chunk_drops(src, len, raw_s, marker));
-  const unsigned flags = (marker ? TT_JPEG_STATUS_MARKER : 0u) | ((bad && blockIdx.x == 0 && threadIdx.x == 0) ? TT_JPEG_STATUS_SPAN : 0u);
-  if (flags) atomicOr(&status[span_frame ? min(max(span_frame[blockIdx.y], 0), nframes - 1) : (int)blockIdx.y], flags);
-  const unsigned all = block_sum<UBLOCK / 64>(drops, red_s);
-  if (threadIdx.x == 0) chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x] = all;
-}
-
-// grid (n): the dropped bytes before every chunk, and the frame's plain (unstuffed) length
-__global__ __launch_bounds__(SCAN_BLOCK) void jpeg_unstuff_scan_kernel(unsigned* __restrict__ chunk_drop, int chunks, const long long* __restrict__ offsets,
-                                                                      const unsigned* __restrict__ lengths, long long scans_bytes, long long max_bytes,
-                                                                      unsigned* __restrict__ plain_bytes) {
-  __shared__ unsigned red_s[SCAN_WAVES];
-  const unsigned total = scan_in_place<SCAN_WAVES>(chunk_drop + (long long)blockIdx.x * chunks, (long long)chunks, red_s);
-  if (threadIdx.x == 0) {
-    unsigned len;
-    bool bad;
-    span_of(scans_bytes, offsets, lengths, max_bytes, blockIdx.x, len, bad);
-    plain_bytes[blockIdx.x] = len - min(total, len);
-  }
-}
-
-// grid (chunks, n): every byte that stays moves down by the drops before it
-__global__ __launch_bounds__(UBLOCK) void jpeg_unstuff_gather_kernel(const unsigned char* __restrict__ scans, long long scans_bytes, const long long* __restrict__ offsets,
-                                                                    const unsigned* __restrict__ lengths, long long max_bytes, const unsigned* __restrict__ chunk_drop,
-                                                                    int chunks, unsigned char* __restrict__ plain, long long plain_stride) {
-  __shared__ unsigned char raw_s[CHUNK + 16];
-  __shared__ unsigned red_s[UBLOCK / 64];
-  unsigned len, all;
-  bool bad, marker;
-  const unsigned char* src = frame_span(scans, scans_bytes, offsets, lengths, max_bytes, blockIdx.y, len, bad);
-  const unsigned mask = chunk_drops(src, len, raw_s, marker);
-  const unsigned before = chunk_drop[(long long)blockIdx.y * chunks + blockIdx.x] + block_scan_excl<UBLOCK / 64>((unsigned)__popc(mask), red_s, all);
-  const unsigned at0 = blockIdx.x * (unsigned)CHUNK + 16 * threadIdx.x;
-  unsigned char* __restrict__ dst = plain + (long long)blockIdx.y * plain_stride;
-  long long pos = (long long)at0 - before;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    if (at0 + j < len && !((mask >> j) & 1u)) {
-      if (pos >= 0 && pos < plain_stride) dst[pos] = raw_s[1 + 16 * threadIdx.x + j];
-      ++pos;
-    }
-  }
-}
-
 // ---------------------------------------------------------------- rule 4: the entropy decoder
-struct DecState { unsigned p, mz; };                 // bit position; block within the MCU << 6 | zig-zag index
-__device__ __forceinline__ bool same(const DecState& a, const DecState& b) { return a.p == b.p && a.mz == b.mz; }
-
 // a frame's constants, uniform over the workgroup
 struct DecFrame {
   unsigned L;                                        // bits of the plain stream
@@ -146,27 +44,13 @@ __device__ __forceinline__ unsigned decode_span(const unsigned* win_s, unsigned 
   unsigned p = st.p, m = st.mz >> 6, z = st.mz & 63u, done = 0u;
   if (p < start) return 0u;                          // a lane before this one stopped at the end of the stream: pass the state on
   for (int it = 0; it < SUBSEQ && p < end; ++it) {
-    const unsigned rel = p - win0, wi = rel >> 5;
-    const unsigned long long two = ((unsigned long long)win_s[wi] << 32) | win_s[wi + 1];
-    const unsigned v = (unsigned)((two << (rel & 31u)) >> 32);          // the 32 bits at p
+    const unsigned v = window_bits(win_s, win0, p);                     // the 32 bits at p
     const unsigned avail = fr.L - p;
     const unsigned comp = fr.bpm == 6 ? (m < 4u ? 0u : m - 3u) : m;
     const unsigned id = (fr.map >> (2u * comp + (z ? 1u : 0u))) & 1u;
     const unsigned* t = tab_s + (id * 2u + (z ? 1u : 0u)) * TT_JPEG_DECODE_WORDS;
-    const unsigned pair = t[v >> 25];
-    const unsigned e = ((v >> 24) & 1u) ? pair >> 16 : pair & 0xffffu;
-    unsigned len = e >> 8, sym = e & 0xffu;
-    if (len == 0u) {
-#pragma unroll
-      for (unsigned l = 9; l <= 16; ++l) {
-        const unsigned code = v >> (32 - l);
-        if (len == 0u && (int)code <= (int)t[128 + l]) {
-          len = l;
-          const unsigned at = (code + t[145 + l]) & 255u;
-          sym = (t[192 + (at >> 2)] >> (8u * (at & 3u))) & 0xffu;
-        }
-      }
-    }
+    unsigned len, sym;
+    huff_lookup(t, v, len, sym);
     if (len == 0u) {
       if (avail < 16u) break;                        // no code within the bits left: the lane stops
       if (WRITE) err |= TT_JPEG_STATUS_CODE;

@@ -328,6 +328,196 @@ extern "C" int tt_jpeg_parse_spans(const uint8_t* data, int64_t size, TtJpegHead
   return parse_file(data, size, header, restart_interval, span_offsets, span_lengths, span_cap, nspans);
 }
 
+// ---------------------------------------------------------------- JPEG import, rule 1b: progressive files
+// One walk over the file's markers: the tables in force are snapshotted at every SOS, the progression is checked scan by scan as libjpeg
+// does (coef_al: per component and coefficient the Al it has reached, -1 before its first visit).  Every trip of both loops advances `at`.
+extern "C" int tt_jpeg_parse_progressive(const uint8_t* data, int64_t size, TtJpegProgressiveHeader* header, TtJpegScan* scans, int64_t scan_cap,
+                                         int64_t* nscans) {
+  const char* who = "tt_jpeg_parse_progressive";
+  if (!data || !header || !nscans) TT_FAIL(TT_EINVAL, "%s: null %s", who, !data ? "data" : (!header ? "header" : "nscans"));
+  if (size <= 0) TT_FAIL(TT_EINVAL, "%s: size = %lld", who, (long long)size);
+  if (scans && scan_cap < 1) TT_FAIL(TT_EINVAL, "%s: scan_cap = %lld (1 or more)", who, (long long)scan_cap);
+  if (size < 2 || data[0] != 0xff || data[1] != 0xd8) TT_FAIL(TT_EINVAL, "%s: no SOI marker: not a JPEG file", who);
+  TtJpegProgressiveHeader hd;
+  memset(&hd, 0, sizeof(hd));
+  uint8_t quant[4][64], bits[2][4][16], huffval[2][4][256];
+  bool have_quant[4] = {false, false, false, false}, have_huff[2][4] = {{false, false, false, false}, {false, false, false, false}}, have_frame = false;
+  int comp_id[3] = {0, 0, 0}, comp_quant[3] = {0, 0, 0};
+  int8_t coef_al[3][64];
+  memset(coef_al, -1, sizeof(coef_al));
+  int64_t count = 0, at = 2;
+  for (;;) {
+    if (at + 2 > size) TT_FAIL(TT_EINVAL, "%s: the file ends before EOI (%lld bytes)", who, (long long)size);
+    if (data[at] != 0xff) TT_FAIL(TT_EINVAL, "%s: byte %lld is 0x%02x where a marker begins", who, (long long)at, data[at]);
+    const int marker = data[at + 1];
+    if (marker == 0xff) { ++at; continue; }                          // fill bytes before a marker
+    if (marker == 0xd9) break;
+    if (marker == 0x01 || (marker >= 0xd0 && marker <= 0xd8)) TT_FAIL(TT_EINVAL, "%s: marker 0x%02x at byte %lld, outside a scan", who, marker, (long long)at);
+    if (at + 4 > size) TT_FAIL(TT_EINVAL, "%s: the file ends before EOI (a marker segment at byte %lld)", who, (long long)at);
+    const int64_t len = ((int64_t)data[at + 2] << 8) | data[at + 3];
+    if (len < 2 || at + 2 + len > size) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of segment 0x%02x at byte %lld", who, marker, (long long)at);
+    const uint8_t* p = data + at + 4;
+    const int64_t n = len - 2;
+    if (marker == 0xc0) {
+      TT_FAIL(TT_EUNSUPPORTED, "%s: a baseline (SOF0) file: tt_jpeg_parse_spans and tt_jpeg_entropy_spans decode it", who);
+    } else if (marker == 0xc2) {
+      if (have_frame) TT_FAIL(TT_EUNSUPPORTED, "%s: a second frame header", who);
+      if (n < 6) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of its SOF2 segment", who);
+      if (p[0] != 8) TT_FAIL(TT_EUNSUPPORTED, "%s: %d-bit samples (8-bit only; 12-bit files are not decoded)", who, p[0]);
+      hd.h = (p[1] << 8) | p[2];
+      hd.w = (p[3] << 8) | p[4];
+      const int nc = p[5];
+      if (nc == 4) TT_FAIL(TT_EUNSUPPORTED, "%s: four components (CMYK / YCCK files are not decoded)", who);
+      if (nc != 1 && nc != 3) TT_FAIL(TT_EUNSUPPORTED, "%s: %d components (1: grey, or 3: YCbCr)", who, nc);
+      if (n < 6 + 3 * nc) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of its SOF2 segment", who);
+      if (hd.h <= 0 || hd.w <= 0) TT_FAIL(TT_EUNSUPPORTED, "%s: a frame of %d x %d (a height of 0 waits for a DNL marker)", who, hd.h, hd.w);
+      hd.ch = nc;
+      int samp[3] = {0x11, 0x11, 0x11};
+      for (int c = 0; c < nc; ++c) {
+        comp_id[c] = p[6 + 3 * c];
+        samp[c] = p[7 + 3 * c];
+        comp_quant[c] = p[8 + 3 * c];
+        if (comp_quant[c] > 3) TT_FAIL(TT_EINVAL, "%s: component %d names quantiser table %d (0 to 3)", who, c, comp_quant[c]);
+      }
+      if (nc == 3 && (comp_id[0] == comp_id[1] || comp_id[0] == comp_id[2] || comp_id[1] == comp_id[2]))
+        TT_FAIL(TT_EINVAL, "%s: two components with the identifier %d", who, comp_id[comp_id[0] == comp_id[2] ? 0 : 1]);
+      if (nc == 1) hd.subsampling = TT_JPEG_444;                     // one component: whatever its sampling factors say, 1 x 1
+      else if (samp[0] == 0x11 && samp[1] == 0x11 && samp[2] == 0x11) hd.subsampling = TT_JPEG_444;
+      else if (samp[0] == 0x22 && samp[1] == 0x11 && samp[2] == 0x11) hd.subsampling = TT_JPEG_420;
+      else TT_FAIL(TT_EUNSUPPORTED, "%s: sampling %dx%d / %dx%d / %dx%d (4:4:4 or 4:2:0; 4:2:2 and others are not decoded)", who, samp[0] >> 4,
+                   samp[0] & 15, samp[1] >> 4, samp[1] & 15, samp[2] >> 4, samp[2] & 15);
+      have_frame = true;
+    } else if ((marker >= 0xc1 && marker <= 0xcf) && marker != 0xc4 && marker != 0xc8 && marker != 0xcc) {
+      TT_FAIL(TT_EUNSUPPORTED, "%s: %s (Huffman-coded progressive SOF2 only)", who, frame_kind(marker));
+    } else if (marker == 0xcc) {
+      TT_FAIL(TT_EUNSUPPORTED, "%s: arithmetic coding (a DAC segment)", who);
+    } else if (marker == 0xdb) {
+      if (count) TT_FAIL(TT_EUNSUPPORTED, "%s: a DQT behind the first SOS (byte %lld): quantiser tables that change between scans are not decoded", who, (long long)at);
+      int64_t k = 0;
+      while (k < n) {
+        const int pq = p[k] >> 4, tq = p[k] & 15;
+        if (pq != 0) TT_FAIL(TT_EUNSUPPORTED, "%s: a 16-bit DQT (8-bit quantiser tables only)", who);
+        if (tq > 3) TT_FAIL(TT_EINVAL, "%s: DQT defines table %d (0 to 3)", who, tq);
+        if (k + 65 > n) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of a DQT table", who);
+        for (int z = 0; z < 64; ++z) quant[tq][ZIGZAG[z]] = p[k + 1 + z];
+        have_quant[tq] = true;
+        k += 65;
+      }
+    } else if (marker == 0xc4) {
+      int64_t k = 0;
+      while (k < n) {
+        const int tc = p[k] >> 4, th = p[k] & 15;
+        if (tc > 1) TT_FAIL(TT_EINVAL, "%s: DHT table class %d (0: DC, or 1: AC)", who, tc);
+        if (th > 3) TT_FAIL(TT_EINVAL, "%s: Huffman table index %d (0 to 3)", who, th);
+        if (k + 17 > n) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of a DHT table", who);
+        int total = 0;
+        for (int l = 0; l < 16; ++l) total += p[k + 1 + l];
+        if (total > 256) TT_FAIL(TT_EINVAL, "%s: a DHT table of %d codes (256 at most)", who, total);
+        if (k + 17 + total > n) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of a DHT table", who);
+        memcpy(bits[tc][th], p + k + 1, 16);
+        memset(huffval[tc][th], 0, 256);
+        memcpy(huffval[tc][th], p + k + 17, (size_t)total);
+        have_huff[tc][th] = true;
+        k += 17 + total;
+      }
+    } else if (marker == 0xdd) {
+      if (n < 2) TT_FAIL(TT_EINVAL, "%s: the file ends before the end of its DRI segment", who);
+      const int v = (p[0] << 8) | p[1];
+      if (v) TT_FAIL(TT_EUNSUPPORTED, "%s: restart intervals in a progressive file (DRI of %d MCUs) are not decoded", who, v);
+    } else if (marker == 0xee) {
+      if (n >= 5 && memcmp(p, "Adobe", 5) == 0) TT_FAIL(TT_EUNSUPPORTED, "%s: an Adobe APP14 segment (Adobe colour transforms are not decoded)", who);
+    } else if (marker == 0xda) {
+      if (!have_frame) TT_FAIL(TT_EINVAL, "%s: SOS before SOF2", who);
+      if (n < 1 || p[0] < 1 || p[0] > 4 || n != 4 + 2 * p[0]) TT_FAIL(TT_EINVAL, "%s: an SOS segment of %lld bytes for %d components", who, (long long)n, n < 1 ? 0 : p[0]);
+      if (count >= TT_JPEG_MAX_SCANS) TT_FAIL(TT_EUNSUPPORTED, "%s: more than %d scans", who, TT_JPEG_MAX_SCANS);
+      const int ns = p[0];
+      const uint8_t* t = p + 1 + 2 * ns;
+      const int ss = t[0], se = t[1], ah = t[2] >> 4, al = t[2] & 15;
+      TtJpegScan sc;
+      memset(&sc, 0, sizeof(sc));
+      int which[4] = {0, 0, 0, 0};
+      for (int i = 0; i < ns; ++i) {
+        int c = 0;
+        while (c < hd.ch && comp_id[c] != p[1 + 2 * i]) ++c;
+        if (c == hd.ch) TT_FAIL(TT_EINVAL, "%s: scan %lld names component %d, which the frame does not have", who, (long long)count, p[1 + 2 * i]);
+        if (sc.comps & (1 << c)) TT_FAIL(TT_EINVAL, "%s: scan %lld names component %d twice", who, (long long)count, p[1 + 2 * i]);
+        sc.comps |= 1 << c;
+        which[i] = c;
+      }
+      if (al > 13) TT_FAIL(TT_EINVAL, "%s: scan %lld: Al = %d (13 at most)", who, (long long)count, al);
+      if (ss == 0) {
+        if (se != 0) TT_FAIL(TT_EINVAL, "%s: scan %lld: a DC scan with Se = %d (Ss = 0 goes with Se = 0)", who, (long long)count, se);
+        bool ordered = ns == 1 || ns == hd.ch;
+        for (int i = 0; i < ns && ns > 1; ++i) ordered = ordered && which[i] == i;
+        if (!ordered) TT_FAIL(TT_EINVAL, "%s: scan %lld: a component subset (a DC scan holds every component in frame order, or one)", who, (long long)count);
+      } else {
+        if (ns != 1) TT_FAIL(TT_EINVAL, "%s: scan %lld: an AC scan of %d components (one only)", who, (long long)count, ns);
+        if (se < ss || se > 63) TT_FAIL(TT_EINVAL, "%s: scan %lld: band %d to %d (Ss <= Se <= 63)", who, (long long)count, ss, se);
+        if (coef_al[which[0]][0] < 0) TT_FAIL(TT_EINVAL, "%s: scan %lld: an AC scan of component %d before its DC scan", who, (long long)count, which[0]);
+      }
+      for (int i = 0; i < ns; ++i) {
+        const int c = which[i];
+        for (int k = ss; k <= se; ++k) {
+          const int before = coef_al[c][k];
+          if (before < 0 ? ah != 0 : (ah != before || al != ah - 1))
+            TT_FAIL(TT_EINVAL, "%s: scan %lld: successive approximation Ah = %d, Al = %d where coefficient %d of component %d %s %d", who, (long long)count, ah,
+                    al, k, c, before < 0 ? "is new: Ah" : "stands at Al", before < 0 ? 0 : before);
+          coef_al[c][k] = (int8_t)al;
+        }
+        const int td = p[2 + 2 * i] >> 4, ta = p[2 + 2 * i] & 15;
+        if (ss == 0 && ah == 0) {
+          if (td > 3) TT_FAIL(TT_EINVAL, "%s: Huffman table index %d (0 to 3)", who, td);
+          if (!have_huff[0][td]) TT_FAIL(TT_EUNSUPPORTED, "%s: missing DC Huffman table %d (scan %lld, component %d)", who, td, (long long)count, c);
+          memcpy(sc.bits[c], bits[0][td], 16);
+          memcpy(sc.huffval[c], huffval[0][td], 256);
+        } else if (ss > 0) {
+          if (ta > 3) TT_FAIL(TT_EINVAL, "%s: Huffman table index %d (0 to 3)", who, ta);
+          if (!have_huff[1][ta]) TT_FAIL(TT_EUNSUPPORTED, "%s: missing AC Huffman table %d (scan %lld, component %d)", who, ta, (long long)count, c);
+          memcpy(sc.bits[0], bits[1][ta], 16);
+          memcpy(sc.huffval[0], huffval[1][ta], 256);
+        }
+      }
+      if (count == 0)
+        for (int c = 0; c < hd.ch; ++c) {
+          if (!have_quant[comp_quant[c]]) TT_FAIL(TT_EUNSUPPORTED, "%s: missing quantiser table %d (component %d)", who, comp_quant[c], c);
+          memcpy(hd.quant[c], quant[comp_quant[c]], 64);
+        }
+      sc.ss = ss; sc.se = se; sc.ah = ah; sc.al = al;
+      sc.offset = at + 2 + len;
+      // the entropy-coded segment ends at the first marker that is neither a stuffed FF 00 nor fill
+      int64_t i = sc.offset;
+      for (;; ++i) {
+        if (i + 1 >= size) TT_FAIL(TT_EINVAL, "%s: the file ends before EOI (inside scan %lld, %lld bytes)", who, (long long)count, (long long)size);
+        if (data[i] == 0xff && data[i + 1] != 0x00) break;           // fill bytes (FF FF) are the next marker's
+      }
+      if (data[i + 1] >= 0xd0 && data[i + 1] <= 0xd7)
+        TT_FAIL(TT_EINVAL, "%s: a restart marker (RST%d at byte %lld) in a file with no restart interval", who, data[i + 1] - 0xd0, (long long)i);
+      sc.bytes = i - sc.offset;
+      if (scans && count < scan_cap) scans[count] = sc;
+      ++count;
+      at = i;
+      continue;
+    }                                                               // APPn, COM and anything else with a length: skipped
+    at += 2 + len;
+  }
+  if (!have_frame) TT_FAIL(TT_EINVAL, "%s: EOI before SOF2", who);
+  if (!count) TT_FAIL(TT_EINVAL, "%s: the file ends before its first scan (EOI at byte %lld)", who, (long long)at);
+  for (int c = 0; c < hd.ch; ++c)
+    for (int k = 0; k < 64; ++k)
+      if (coef_al[c][k] != 0)
+        TT_FAIL(TT_EUNSUPPORTED, "%s: incomplete progression: coefficient %d of component %d %s at EOI (libjpeg smooths such files; they are not decoded)", who, k, c,
+                coef_al[c][k] < 0 ? "was never sent" : "has not reached Al = 0");
+  if (scans && scan_cap < count) TT_FAIL(TT_EINVAL, "%s: scan_cap too small: %lld for %lld scans", who, (long long)scan_cap, (long long)count);
+  hd.nscans = (int32_t)count;
+  *header = hd;
+  *nscans = count;
+  return TT_OK;
+}
+
+extern "C" int64_t tt_jpeg_entropy_progressive_ws_bytes(int32_t n, int32_t nscans, int64_t max_bytes, int32_t h, int32_t w, int32_t ch, int32_t subsampling) {
+  return TtJpegProgressiveWs(n, nscans, max_bytes, h, w, ch, subsampling).total;
+}
+
 extern "C" int tt_jpeg_decode_table(const uint8_t* bits, const uint8_t* huffval, uint32_t* table) {
   if (!bits || !huffval || !table) TT_FAIL(TT_EINVAL, "tt_jpeg_decode_table: null %s", !bits ? "bits" : (!huffval ? "huffval" : "table"));
   int total = 0;

@@ -93,3 +93,21 @@ struct TtJpegEntropyWs {
     total = plain + n * plain_stride;
   }
 };
+// tt_jpeg_entropy_progressive: tt_jpeg_entropy's layout over the n x nscans items, then per item its frame, then the AC-refine scans'
+// per-block masks and positions, one set a frame (a frame runs one scan at a time)
+constexpr int TT_JPEG_MAX_ITEMS = 65535;           // (frame, scan) pairs of a call: a grid dimension
+struct TtJpegProgressiveWs {
+  TtJpegEntropyWs items;
+  int64_t item_frame, masks, starts;               // int32 per item; uint64 per frame and block; uint32 per frame and block
+  int64_t total;
+  TtJpegProgressiveWs(int32_t n, int32_t nscans, int64_t max_bytes, int32_t h, int32_t w, int32_t ch, int32_t subsampling)
+      : items(n > 0 && nscans > 0 && nscans <= TT_JPEG_MAX_SCANS && (int64_t)n * nscans <= TT_JPEG_MAX_ITEMS ? n * nscans : 0, max_bytes), item_frame(0), masks(0),
+        starts(0), total(0) {
+    const int64_t blocks = tt_jpeg_blocks(h, w, ch, subsampling);
+    if (!items.total || !blocks) return;
+    item_frame = items.total;
+    masks = item_frame + tt_jpeg_up16(4 * (int64_t)n * nscans);
+    starts = masks + tt_jpeg_up16(8 * n * blocks);
+    total = starts + tt_jpeg_up16(4 * n * blocks);
+  }
+};

@@ -1,4 +1,4 @@
-"""Baseline JPEG files decoded on the device (include/ttvdm.h, "JPEG import"): a clip folder im_0.jpg .. im_{F-1}.jpg, a folder
+"""Baseline and progressive JPEG files decoded on the device (include/ttvdm.h, "JPEG import"): a clip folder im_0.jpg .. im_{F-1}.jpg, a folder
 ``export.write_jpegs`` wrote, a Motion-JPEG AVI or a request's image become uint8 [F, H, W, ch] NHWC device tensors holding byte for
 byte what ``np.asarray(PIL.Image.open(f))`` holds.  The host reads the files' headers (tt_jpeg_parse_spans) and builds the decode tables
 (tt_jpeg_decode_table); only the compressed scans cross to the device, where they are unstuffed, entropy-decoded, dequantised,
@@ -8,8 +8,16 @@ Restart intervals: a file with a DRI segment and RSTn markers (``export.write_jp
 the spans between its markers, and the entropy decoder gives every span a workgroup of its own instead of one per frame.  A file
 without them is one span and decodes through the same launches as before; the reference dataset's own im_0.jpg files carry none.
 
+Progressive files (SOF2: what web images usually are, ``PIL.save(progressive=True)``'s): ``decode_jpeg(..., progressive=True)`` reads
+every scan's place, band, Ah / Al and tables (tt_jpeg_parse_progressive), uploads the scans' bytes, and the device applies them round by
+round into the baseline route's coefficient buffer (tt_jpeg_entropy_progressive: DC first, DC refine, AC first, AC refine); the same
+reconstruction then runs.  A call may mix baseline and progressive files and scan scripts.  Without the keyword a progressive file is
+refused by name, as before; ``DevicePixels.from_jpeg`` -- the request path -- passes it.
+
 Not applied: EXIF orientation (``load_image`` of the reference applies it; rotate the result when the files carry one).  Refused by
-name: progressive, arithmetic and 12-bit files, several scans, 4:2:2, CMYK / Adobe files, restart markers out of order or count.
+name: arithmetic and 12-bit files, 4:2:2, CMYK / Adobe files, restart markers out of order or count, several scans in a baseline file;
+in a progressive file restart intervals, a DQT between scans and an INCOMPLETE progression (libjpeg smooths those; they are not decoded
+differently); progressive files altogether unless ``progressive=True``.
 
 Animated GIFs (include/ttvdm.h, "GIF import"): ``decode_gif`` / ``read_gif`` turn the file ``export.write_gif`` (or Pillow, or imageio)
 wrote into uint8 [F, H, W, 3] on the device, per frame the canvas Pillow shows after ``seek(f)``.  The host walks the container
@@ -70,6 +78,53 @@ def parse_jpeg(data: bytes) -> JpegHeader:
                       np.ctypeslib.as_array(hd.bits).copy(), np.ctypeslib.as_array(hd.huffval).copy(), ri.value, np.stack([offs, lens], axis=1))
 
 
+@dataclass
+class JpegScan:
+    """One scan of a progressive file: ``components`` (indices into the frame's components, ascending), the band ``ss`` .. ``se``, ``ah`` /
+    ``al``, the byte range of its entropy-coded segment in the file, and the Huffman tables in force at its SOS as ``bits`` uint8 [3, 16]
+    / ``huffval`` uint8 [3, 256]: a DC-first scan's DC table of component c at [c], an AC scan's AC table at [0], zeros for a DC-refine scan."""
+    components: tuple
+    ss: int
+    se: int
+    ah: int
+    al: int
+    offset: int
+    bytes: int
+    bits: np.ndarray
+    huffval: np.ndarray
+
+
+@dataclass
+class JpegProgressiveHeader:
+    """What ``parse_jpeg_progressive`` reads from one progressive (SOF2) file: the geometry, ``subsampling``, ``quant`` uint8 [3, 64] (per
+    component, natural order) and the ``scans`` in file order."""
+    height: int
+    width: int
+    channels: int
+    subsampling: str
+    quant: np.ndarray
+    scans: list
+
+
+def parse_jpeg_progressive(data: bytes) -> JpegProgressiveHeader:
+    """One progressive JPEG file -> its header and scans (tt_jpeg_parse_progressive: once to count the scans, once to take them);
+    ValueError with the library's text for what is refused -- a baseline file, an incomplete progression and the rest of rule 1b."""
+    lib = _lib.load()
+    hd = _lib.TtJpegProgressiveHeader()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    at = buf.ctypes.data if buf.size else None
+    count = C.c_int64(0)
+    rc = lib.tt_jpeg_parse_progressive(at, buf.size, C.byref(hd), None, 0, C.byref(count))
+    if rc == 0:
+        rows = (_lib.TtJpegScan * count.value)()
+        rc = lib.tt_jpeg_parse_progressive(at, buf.size, C.byref(hd), C.cast(rows, C.c_void_p), count.value, C.byref(count))
+    if rc != 0:
+        raise ValueError(lib.tt_last_error().decode(errors="replace"))
+    scans = [JpegScan(tuple(c for c in range(3) if r.comps >> c & 1), r.ss, r.se, r.ah, r.al, r.offset, r.bytes,
+                      np.ctypeslib.as_array(r.bits).copy(), np.ctypeslib.as_array(r.huffval).copy()) for r in rows]
+    return JpegProgressiveHeader(hd.h, hd.w, hd.ch, _SUBSAMPLING[hd.subsampling], np.ctypeslib.as_array(hd.quant).copy(), scans)
+
+
 def jpeg_decode_table(bits, huffval) -> np.ndarray:
     """BITS [16] and HUFFVAL (up to 256 symbols by ascending code) -> uint32 [256]: the table the decoder reads (tt_jpeg_decode_table)"""
     b = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
@@ -107,33 +162,66 @@ def _read(f) -> bytes:
         return fh.read()
 
 
-def decode_jpeg(files, device) -> torch.Tensor:
-    """Baseline JPEG files of ONE geometry and subsampling -- bytes or paths, one or a list -- -> uint8 [F, H, W, ch] on ``device``, ch 1
+def decode_jpeg(files, device, progressive: bool = False) -> torch.Tensor:
+    """JPEG files of ONE geometry and subsampling -- bytes or paths, one or a list -- -> uint8 [F, H, W, ch] on ``device``, ch 1
     (grey) or 3 (RGB): Pillow's decoded pixels, byte for byte.  One upload (the scans, end to end), one readback (a status word per
     frame).  Files with restart markers are decoded span by span, one workgroup each; the files of a call may carry different restart
-    intervals, or none.  ValueError: a file the parser refuses (its text names the cause), files that differ in size or subsampling,
-    more than 65535 spans in all, a frame whose scan is corrupt or truncated (the frame is named)."""
-    from . import ops
+    intervals, or none.  ``progressive=True``: a progressive (SOF2) file is accepted as well and takes the scan-by-scan route
+    (tt_jpeg_parse_progressive / tt_jpeg_entropy_progressive); the files of a call may mix baseline and progressive files and scan
+    scripts, every baseline file goes through the launches it goes through without the keyword, and the frames come back in file order.
+    The default refuses progressive files by name, as before.  ValueError: a file the parser refuses (its text names the cause), files
+    that differ in size or subsampling, more than 65535 spans in all, a frame whose scan is corrupt or truncated (the frame is named)."""
     items = list(files) if isinstance(files, (list, tuple)) else [files]
     if not items:
         raise ValueError("decode_jpeg: no files")
     device = torch.device(device)
     if device.type != "cuda":
         raise ValueError(f"decode_jpeg: decodes on the HIP device, got {device} (there is no CPU fallback)")
-    blobs, heads = [], []
+    datas, heads = [], []
     for i, f in enumerate(items):
         data = _read(f)
         try:
-            hd = parse_jpeg(data)
+            try:
+                hd = parse_jpeg(data)
+            except ValueError as e:
+                if not (progressive and "SOF2: progressive" in str(e)):
+                    raise
+                hd = parse_jpeg_progressive(data)
         except ValueError as e:
             raise ValueError(f"decode_jpeg: file {i}: {e}") from None
         if heads and (hd.height, hd.width, hd.channels, hd.subsampling) != (heads[0].height, heads[0].width, heads[0].channels, heads[0].subsampling):
             raise ValueError(f"decode_jpeg: file {i} is {hd.height} x {hd.width} x {hd.channels} {hd.subsampling}, file 0 is {heads[0].height} x "
                              f"{heads[0].width} x {heads[0].channels} {heads[0].subsampling}: one geometry and subsampling per call")
-        if hd.scan_bytes < 1:
+        if isinstance(hd, JpegHeader) and hd.scan_bytes < 1:
             raise ValueError(f"decode_jpeg: file {i}: an empty scan")
         heads.append(hd)
-        blobs.append(data[hd.scan_offset:hd.scan_offset + hd.scan_bytes])
+        datas.append(data)
+    base = [i for i, h in enumerate(heads) if isinstance(h, JpegHeader)]
+    prog = [i for i, h in enumerate(heads) if not isinstance(h, JpegHeader)]
+    parts = []
+    if base:
+        parts.append((base, _decode_baseline([heads[i] for i in base], [datas[i] for i in base], device, base)))
+    if prog:
+        parts.append((prog, _decode_progressive([heads[i] for i in prog], [datas[i] for i in prog], device, prog)))
+    for index, (status, _) in parts:                                                               # one readback a route
+        for k, s in enumerate(status.cpu().tolist()):
+            if s:
+                why = ", ".join(text for bit, text in _lib.TT_JPEG_STATUS.items() if s & bit)
+                raise ValueError(f"decode_jpeg: frame {index[k]} is corrupt or truncated ({why}; status {s})")
+    if len(parts) == 1:
+        return parts[0][1][1]
+    h0 = heads[0]
+    out = torch.empty((len(heads), h0.height, h0.width, h0.channels), dtype=torch.uint8, device=device)
+    for index, (_, frames) in parts:
+        out[torch.tensor(index, device=device)] = frames
+    return out
+
+
+def _decode_baseline(heads, datas, device, index):
+    """decode_jpeg's baseline route: the files' scans (or restart spans) -> (status int32 [F], frames); ``index``: the files' places in
+    the call, for the texts"""
+    from . import ops
+    blobs = [d[h.scan_offset:h.scan_offset + h.scan_bytes] for h, d in zip(heads, datas)]
     h0 = heads[0]
     lens = np.array([len(b) for b in blobs], dtype=np.int64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
@@ -151,7 +239,7 @@ def decode_jpeg(files, device) -> torch.Tensor:
             raise ValueError(f"decode_jpeg: {len(rows)} restart intervals in {len(heads)} files: more spans than one call decodes ({_lib.TT_JPEG_MAX_SPANS})")
         rows = np.array(rows, dtype=np.int64)
         if rows[:, 1].min() < 1:
-            i = int(rows[int(rows[:, 1].argmin()), 2])
+            i = index[int(rows[int(rows[:, 1].argmin()), 2])]
             raise ValueError(f"decode_jpeg: file {i}: an empty restart interval")
     same_tables = all(np.array_equal(h.bits, h0.bits) and np.array_equal(h.huffval, h0.huffval) and h.dc_table == h0.dc_table and h.ac_table == h0.ac_table
                       for h in heads[1:])
@@ -173,17 +261,63 @@ def decode_jpeg(files, device) -> torch.Tensor:
     else:
         coeffs, status = ops.jpeg_entropy(scans, torch.from_numpy(offs).to(device), torch.from_numpy(lens.astype(np.int32)).to(device), int(lens.max()), shape,
                                           h0.subsampling, tables)
-    frames = ops.jpeg_pixels(coeffs, shape, h0.subsampling, torch.from_numpy(quant).to(device))
-    for i, s in enumerate(status.cpu().tolist()):
-        if s:
-            why = ", ".join(text for bit, text in _lib.TT_JPEG_STATUS.items() if s & bit)
-            raise ValueError(f"decode_jpeg: frame {i} is corrupt or truncated ({why}; status {s})")
-    return frames
+    return status, ops.jpeg_pixels(coeffs, shape, h0.subsampling, torch.from_numpy(quant).to(device))
 
 
-def read_jpegs(folder, pattern: str = "im_{idx}.jpg", device="cuda") -> torch.Tensor:
+def _progressive_items(heads, datas, index):
+    """The (file, scan) items of tt_jpeg_entropy_progressive: item f S + s is scan s of file f, S the most scans a file has -> (the
+    segments end to end, offsets int64 [F S], lengths int32 [F S], desc int32 [F S, 8], tables uint32 [F S, 3, 256])"""
+    n, most = len(heads), max(len(h.scans) for h in heads)
+    if n * most > _lib.TT_JPEG_MAX_ITEMS:
+        raise ValueError(f"decode_jpeg: {n} progressive files of up to {most} scans: more scans than one call decodes ({_lib.TT_JPEG_MAX_ITEMS})")
+    offs, lens = np.zeros(n * most, dtype=np.int64), np.zeros(n * most, dtype=np.int32)
+    desc = np.zeros((n * most, _lib.TT_JPEG_SCAN_WORDS), dtype=np.int32)
+    tables = np.zeros((n * most, 3, _lib.TT_JPEG_DECODE_WORDS), dtype=np.uint32)
+    blobs, at, made = [], 0, {}
+
+    def table(bits, huffval):
+        key = bits.tobytes() + huffval.tobytes()
+        if key not in made:
+            made[key] = jpeg_decode_table(bits, huffval)
+        return made[key]
+
+    for i, (h, data) in enumerate(zip(heads, datas)):
+        for s, sc in enumerate(h.scans):
+            item = i * most + s
+            blobs.append(data[sc.offset:sc.offset + sc.bytes])
+            offs[item], lens[item] = at, sc.bytes
+            at += sc.bytes
+            desc[item, :5] = (sum(1 << c for c in sc.components), sc.ss, sc.se, sc.ah, sc.al)
+            try:
+                if sc.ss == 0 and sc.ah == 0:
+                    for c in sc.components:
+                        tables[item, c] = table(sc.bits[c], sc.huffval[c])
+                elif sc.ss > 0:
+                    tables[item, 0] = table(sc.bits[0], sc.huffval[0])
+            except RuntimeError as e:
+                raise ValueError(f"decode_jpeg: file {index[i]}: scan {s}: {e}") from None
+    if at < 1:
+        raise ValueError(f"decode_jpeg: file {index[0]}: empty scans")
+    return np.frombuffer(b"".join(blobs), dtype=np.uint8).copy(), offs, lens, desc, tables
+
+
+def _decode_progressive(heads, datas, device, index):
+    """decode_jpeg's progressive route: every scan of every file in one call -> (status int32 [F], frames)"""
+    from . import ops
+    h0 = heads[0]
+    blob, offs, lens, desc, tables = _progressive_items(heads, datas, index)
+    shape = (h0.height, h0.width, h0.channels)
+    coeffs, status = ops.jpeg_entropy_progressive(torch.from_numpy(blob).to(device), torch.from_numpy(offs).to(device), torch.from_numpy(lens).to(device),
+                                                  torch.from_numpy(desc).to(device), torch.from_numpy(tables.view(np.int32)).to(device), max(int(lens.max()), 1),
+                                                  len(heads), shape, h0.subsampling)
+    same_quant = all(np.array_equal(h.quant, h0.quant) for h in heads[1:])
+    quant = np.stack([h.quant for h in (heads[:1] if same_quant else heads)])
+    return status, ops.jpeg_pixels(coeffs, shape, h0.subsampling, torch.from_numpy(quant).to(device))
+
+
+def read_jpegs(folder, pattern: str = "im_{idx}.jpg", device="cuda", progressive: bool = False) -> torch.Tensor:
     """``folder/pattern.format(idx=i)`` for i = 0, 1, ... up to the first missing index -- the layout the data loaders read a clip from
-    and ``export.write_jpegs`` writes -- decoded by ``decode_jpeg``."""
+    and ``export.write_jpegs`` writes -- decoded by ``decode_jpeg``; ``progressive`` is passed on to it."""
     paths = []
     while os.path.exists(os.path.join(folder, pattern.format(idx=len(paths)))):
         paths.append(os.path.join(folder, pattern.format(idx=len(paths))))
@@ -191,7 +325,7 @@ def read_jpegs(folder, pattern: str = "im_{idx}.jpg", device="cuda") -> torch.Te
             raise ValueError(f"read_jpegs: pattern {pattern!r} names two frames alike (use {{idx}})")
     if not paths:
         raise ValueError(f"read_jpegs: {os.path.join(folder, pattern.format(idx=0))} does not exist")
-    return decode_jpeg(paths, device)
+    return decode_jpeg(paths, device, progressive=progressive)
 
 
 def read_mjpeg_video(path, device="cuda") -> torch.Tensor:

@@ -1433,6 +1433,48 @@ def jpeg_entropy_spans(scans: torch.Tensor, offsets: torch.Tensor, lengths: torc
     return coeffs, status
 
 
+def jpeg_entropy_progressive(scans: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, desc: torch.Tensor, tables: torch.Tensor, max_bytes: int,
+                             frames: int, shape, subsampling):
+    """The scans of N progressive frames -> (coeffs int16 [N, blocks, 64], status int32 [N]) as ``jpeg_entropy`` gives them
+    (tt_jpeg_entropy_progressive).  Item f S + s is scan s of frame f, S = the most scans a frame of the call has: ``offsets`` / ``lengths``
+    (int64 / int32 device tensors [N S]) place its stuffed segment in ``scans``; ``desc`` int32 [N S, 8] = component mask, Ss, Se, Ah, Al,
+    0, 0, 0 (mask 0: the frame has no scan s); ``tables`` int32 [N S, 3, 256]: a DC-first scan's DC table of component c at [c], an AC
+    scan's table at [0] (ingest.jpeg_decode_table).  ``max_bytes``: a host integer no length exceeds.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    h, w, ch, sub = _jpeg_shape(shape, subsampling, "jpeg_entropy_progressive")
+    for t in (scans, offsets, lengths, desc, tables):
+        _p(t)
+    if scans.dtype != torch.uint8 or not scans.is_contiguous() or scans.numel() < 1:
+        raise RuntimeError(f"jpeg_entropy_progressive: scans must be a contiguous uint8 tensor, got {tuple(scans.shape)} {scans.dtype}")
+    n = frames
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise RuntimeError(f"jpeg_entropy_progressive: frames {frames!r} (a positive integer)")
+    items = offsets.numel()
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or items < 1 or items % n or not offsets.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy_progressive: offsets int64 [{n} x scans], got {tuple(offsets.shape)} {offsets.dtype}")
+    nscans = items // n
+    if nscans > _lib.TT_JPEG_MAX_SCANS or items > _lib.TT_JPEG_MAX_ITEMS:
+        raise RuntimeError(f"jpeg_entropy_progressive: {n} frames of {nscans} scans (at most {_lib.TT_JPEG_MAX_SCANS} scans a frame, {_lib.TT_JPEG_MAX_ITEMS} in all)")
+    if lengths.dtype != torch.int32 or tuple(lengths.shape) != (items,) or not lengths.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy_progressive: lengths int32 [{items}], got {tuple(lengths.shape)} {lengths.dtype}")
+    if desc.dtype != torch.int32 or tuple(desc.shape) != (items, _lib.TT_JPEG_SCAN_WORDS) or not desc.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy_progressive: desc int32 [{items}, {_lib.TT_JPEG_SCAN_WORDS}], got {tuple(desc.shape)} {desc.dtype}")
+    if tables.dtype != torch.int32 or tuple(tables.shape) != (items, 3, _lib.TT_JPEG_DECODE_WORDS) or not tables.is_contiguous():
+        raise RuntimeError(f"jpeg_entropy_progressive: tables int32 [{items}, 3, {_lib.TT_JPEG_DECODE_WORDS}], got {tuple(tables.shape)} {tables.dtype}")
+    if any(t.device != scans.device for t in (offsets, lengths, desc, tables)):
+        raise RuntimeError("jpeg_entropy_progressive: scans, offsets, lengths, desc and tables must be on one device")
+    if isinstance(max_bytes, bool) or not isinstance(max_bytes, int) or max_bytes < 1:
+        raise RuntimeError(f"jpeg_entropy_progressive: max_bytes {max_bytes!r} (a positive integer)")
+    coeffs = torch.empty((n, lib.tt_jpeg_blocks(h, w, ch, sub), 64), dtype=torch.int16, device=scans.device)
+    status = torch.empty((n,), dtype=torch.int32, device=scans.device)
+    ws = torch.empty((max(lib.tt_jpeg_entropy_progressive_ws_bytes(n, nscans, max_bytes, h, w, ch, sub), 16),), dtype=torch.uint8, device=scans.device)
+    check(lib.tt_jpeg_entropy_progressive(_p(scans), scans.numel(), _p(offsets), _p(lengths), _p(desc), _p(tables), max_bytes, n, nscans, h, w, ch, sub,
+                                          _p(coeffs), _p(status), _p(ws), ws.numel(), _stream()), "tt_jpeg_entropy_progressive")
+    _wrote(coeffs, "jpeg_entropy_progressive")
+    _wrote(status, "jpeg_entropy_progressive")
+    return coeffs, status
+
+
 def jpeg_pixels(coeffs: torch.Tensor, shape, subsampling, quant: torch.Tensor) -> torch.Tensor:
     """``jpeg_entropy``'s (or ``jpeg_coeffs``') coefficients of frames of ``shape`` (h, w, ch) and quantiser tables [1 or N, 3, 64] (uint8
     device tensor: per component, natural order) -> uint8 device tensor [N, h, w, ch]: dequantised, inverse DCT, 4:2:0 chroma upsampled,

@@ -156,10 +156,11 @@ class DevicePixels:
 
     @classmethod
     def from_jpeg(cls, files, device) -> "DevicePixels":
-        """Baseline JPEG file(s) of one size -- paths or bytes -- decoded on the device (``ingest.decode_jpeg``): only the compressed
-        bytes are uploaded, and the pixels are the ones ``PIL.Image.open(f).convert("RGB")`` holds.  EXIF orientation is not applied."""
+        """Baseline or progressive JPEG file(s) of one size -- paths or bytes -- decoded on the device (``ingest.decode_jpeg`` with
+        ``progressive=True``: a request's image is whatever the user has): only the compressed bytes are uploaded, and the pixels are
+        the ones ``PIL.Image.open(f).convert("RGB")`` holds.  EXIF orientation is not applied."""
         from .. import ingest
-        pixels = ingest.decode_jpeg(files, device)
+        pixels = ingest.decode_jpeg(files, device, progressive=True)
         return cls(pixels.expand(-1, -1, -1, 3) if pixels.shape[-1] == 1 else pixels)          # a grey file: L -> RGB repeats the channel
 
     @classmethod

@@ -20,6 +20,12 @@ standard tables), and the 640 x 480 fixture tests/golden/bridge_task1_im_0.jpg, 
                    files, and ``sooner``: whether the marked files' time is below the marker-less files' of the same run.  The result
                    goes under "decode" of profiles/jpeg_restart_bench.json (tools/jpeg_export_bench.py fills "encode").
 
+  --progressive     Pillow's ``progressive=True`` files (quality 75, 4:2:0) of 14 generator frames at 256 x 384 and at 576 x 1024 and of
+                   the 640 x 480 fixture's pixels, once: the whole ``decode_jpeg(files, progressive=True)`` from the files' bytes against
+                   Pillow on the same bytes; entropy_us (every round) and first_scans_us (the same call with the refinement scans' items
+                   masked out: their rounds are launched and return at once) by device events, refine_us their difference: the
+                   refinement rounds on their own.  The result goes to profiles/jpeg_progressive_bench.json.
+
 The last row is ONE file, a request's image: without markers one workgroup decodes it, the case in which the scheme has the least to offer.
 
 A record, not a gate.  Prints one JSON line and writes it to --out (default profiles/jpeg_decode_bench.json)."""
@@ -146,6 +152,62 @@ def merge_out(path, key, res):
         f.write("\n")
 
 
+def progressive_row(name, files, iters):
+    from this_and_that_vdm_amd import ingest, ops
+    heads = [ingest.parse_jpeg_progressive(d) for d in files]
+    h0 = heads[0]
+    shape = (h0.height, h0.width, h0.channels)
+    blob, offs, lens, desc, tables = ingest._progressive_items(heads, files, list(range(len(files))))
+    first = desc.copy()
+    first[desc[:, 3] != 0] = 0                                                               # the refinement scans' items masked out
+    dev = lambda x: torch.from_numpy(x).cuda()
+    d_blob, d_offs, d_lens, d_desc, d_first, d_tables = dev(blob), dev(offs), dev(lens), dev(desc), dev(first), dev(tables.view(np.int32))
+    entropy = lambda which: ops.jpeg_entropy_progressive(d_blob, d_offs, d_lens, which, d_tables, int(lens.max()), len(files), shape, h0.subsampling)
+    coeffs, status = entropy(d_desc)
+    quant = dev(h0.quant[None])
+    got = ingest.decode_jpeg(files, "cuda", progressive=True)
+    row = dict(input=name, frames=[len(files), *shape], file_bytes=int(sum(len(d) for d in files)), raw_bytes=int(got.numel()), scans=len(h0.scans),
+               refinement_scans=int(sum(1 for s in h0.scans if s.ah)), longest_scan_bytes=int(lens.max()),
+               equal=bool(torch.equal(got, pillow_decode(files))) and not bool(status.any()),
+               pillow_ms=round(wall_ms(lambda: pillow_decode(files), iters), 2),
+               decode_jpeg_ms=round(wall_ms(lambda: ingest.decode_jpeg(files, "cuda", progressive=True), iters), 2),
+               stages=dict(host_parse_ms=round(wall_ms(lambda: ingest._progressive_items([ingest.parse_jpeg_progressive(d) for d in files], files,
+                                                                                        list(range(len(files)))), iters), 3),
+                           entropy_us=round(events_us(lambda: entropy(d_desc), iters), 1), first_scans_us=round(events_us(lambda: entropy(d_first), iters), 1),
+                           pixels_us=round(events_us(lambda: ops.jpeg_pixels(coeffs, shape, h0.subsampling, quant), iters), 1)))
+    row["stages"]["refine_us"] = round(row["stages"]["entropy_us"] - row["stages"]["first_scans_us"], 1)
+    row["faster_than_pillow"] = bool(row["decode_jpeg_ms"] < row["pillow_ms"])
+    return row
+
+
+def progressive_main(a):
+    """--progressive: the rows of the issue -> profiles/jpeg_progressive_bench.json"""
+    from PIL import Image
+    from tests import png_reference as ref
+
+    def save(frame):
+        buf = io.BytesIO()
+        Image.fromarray(frame).save(buf, format="JPEG", quality=75, subsampling=2, progressive=True)
+        return buf.getvalue()
+    rows = [progressive_row(f"Pillow progressive {h}x{w} quality 75 4:2:0 x {n}", [save(ref.generator_frame(h, w, f)) for f in range(n)], a.iters)
+            for n, h, w in [(14, 256, 384), (14, 576, 1024)]]
+    with Image.open(os.path.join(REPO, "tests", "golden", "bridge_task1_im_0.jpg")) as im:
+        pixels = np.asarray(im.convert("RGB"))
+    rows.append(progressive_row("fixture bridge_task1_im_0.jpg's pixels as a progressive file x 1 (a request's image)", [save(pixels)], a.iters))
+    import PIL
+    res = dict(tool="jpeg_decode_bench --progressive", device=torch.cuda.get_device_name(0), cpu_threads=torch.get_num_threads(), pillow=PIL.__version__,
+               iters=a.iters, rows=rows,
+               says="a record, not a gate; medians of --iters in one process after a warm-up; decode_jpeg_ms is the whole call from the files' bytes by the "
+                    "host clock, status readback included; entropy_us is unstuffing + every round by device events, first_scans_us the same call with the "
+                    "refinement scans' items masked out, refine_us their difference; Pillow (libjpeg-turbo) runs on this machine's CPU, one thread, and "
+                    "its time includes the upload of the raw pixels")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def row_of(name, files, iters, passes):
     from tests import jpeg_decode_reference as dec
     from this_and_that_vdm_amd import _lib, ingest, ops
@@ -190,13 +252,18 @@ def main():
     ap.add_argument("--variant", action="append", default=[], metavar="S=PATH", help="a library built with another TT_JPEG_SUBSEQ_BITS")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--restart-rows", type=int, default=0, metavar="N", help="compare files written with restart_rows=N against the marker-less ones")
-    ap.add_argument("--out", default=None, help="default profiles/jpeg_decode_bench.json; with --restart-rows profiles/jpeg_restart_bench.json")
+    ap.add_argument("--progressive", action="store_true", help="Pillow's progressive files through decode_jpeg(progressive=True)")
+    ap.add_argument("--out", default=None, help="default profiles/jpeg_decode_bench.json; with --restart-rows profiles/jpeg_restart_bench.json; with "
+                                                "--progressive profiles/jpeg_progressive_bench.json")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(REPO, "profiles", "jpeg_restart_bench.json" if a.restart_rows else "jpeg_decode_bench.json")
+    a.out = a.out or os.path.join(REPO, "profiles", "jpeg_progressive_bench.json" if a.progressive else
+                                  ("jpeg_restart_bench.json" if a.restart_rows else "jpeg_decode_bench.json"))
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_decode_bench: needs a GPU (there is no CPU fallback)")
     if a.restart_rows:
         return restart_main(a)
+    if a.progressive:
+        return progressive_main(a)
     from tests import png_reference as ref
     from this_and_that_vdm_amd import export
     rows = []
